@@ -28,8 +28,12 @@ as in the real loop, t cycles 999 -> 0 with the real fp32 tables.
 
 Multi-GPU: particles shard across ranks, no collective inside the DPS step itself; what is exchanged is named above.
 
-Rank 0 prints ONE JSON line; `roofline` is for the dominant kernel from live HIP-event timing, `cpu_baseline`
-is the oracle (a CPU port of the reference path) on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline figures
+(`value`, `ms_per_step`, ...).  --full adds what takes runs of its own: `roofline` (the dominant kernel from live HIP-event
+timing, the one-chain schedule, the on-box copy ceiling) and `cpu_baseline` (the oracle, a CPU port of the reference path,
+on a bounded sample of the same workload).
+--dump-outputs DIR   after the timed steps, rank 0 writes what the timed path returned after its last step as DIR/<name>.npy
+                     (float32 / float64; seeded inputs, so two builds can be compared output for output)
 """
 import argparse
 import json
@@ -139,7 +143,12 @@ def parse(argv=None):
     ap.add_argument("--force-process-group", action="store_true",
                     help="initialise the torch.distributed process group even for ONE rank: every exchange of the workload "
                          "then runs through the backend (RCCL) as it would with eight -- how a one-GPU box exercises it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the one-chain schedule, per-launch timings and "
+                         "the roofline, the on-box copy ceiling, the CPU baselines and the parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path returned after its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-particles", type=int, default=64)
     ap.add_argument("--cpu-steps", type=int, default=5)
     return ap.parse_args(argv)
@@ -262,10 +271,39 @@ def load_traffic(operator):
         return {}
 
 
+DUMP_BYTES = 64 * 10 ** 6           # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, tensors, budget=DUMP_BYTES):
+    """--dump-outputs: each tensor as <dirname>/<name>.npy, floats as float32 and integers as float64.  If the set would
+    exceed `budget`, the largest array keeps a fixed, seeded sample of its rows (sorted; their indices go to
+    <name>_rows.npy) -- the same rows on every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    tensors = {k: v.detach().reshape(v.shape or (1,)) for k, v in tensors.items()}
+    total = sum(v.numel() * 8 if not v.is_floating_point() else v.numel() * 4 for v in tensors.values())
+    if total > budget:
+        big = max(tensors, key=lambda k: tensors[k].numel())
+        t = tensors[big]
+        rows, row_bytes = t.shape[0], t[0].numel() * 4
+        keep = (budget - (total - rows * row_bytes)) // (row_bytes + 8)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one row of {big} does not fit in {budget} bytes")
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        tensors[big] = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        tensors[big + "_rows"] = torch.from_numpy(idx)
+    for name, t in tensors.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32 if t.is_floating_point() else np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)
     rank = int(os.environ.get("RANK", "0"))
@@ -421,6 +459,7 @@ def main():
 
     def chain_steps(first, count):
         x = state["x"]
+        costs = None
         for i in range(count):
             k = first + i
             if wl == "search":
@@ -447,6 +486,8 @@ def main():
                 # TTC_DDIM._resample over the sharded particle set: scores all-gathered, identical host draw, states fetched
                 x, _, _ = dd.global_resample(x, buf.norm, 100.0, res_gen, fetch=args.resample_fetch)
         state["x"] = x
+        if costs is not None:
+            state["costs"] = costs          # the search step's per-proposal costs of the last step (--dump-outputs)
 
     def run_steps(first, count):
         if pg is not None:
@@ -474,6 +515,7 @@ def main():
         t0 = time.perf_counter()
         run_steps(first, count)
         winner, best_dev = closing_select()
+        state["winner"] = winner
         barrier()
         dt = time.perf_counter() - t0
         if use_pg:
@@ -487,6 +529,71 @@ def main():
     run_steps(0, args.warmup)
     closing_select()                                   # warm the select (and the collectives) too
     elapsed, best = timed(args.warmup, args.steps)
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step (rank 0's shard; the winner and its index are global),
+        # written before anything below reuses the buffers
+        outs = {"x_next": pg.x_next() if pg is not None else state["x"], "winner": state["winner"],
+                "best_of_n_index": torch.tensor(best)}
+        if wl == "search":
+            outs["costs"] = state["costs"]
+        else:
+            outs["norm"] = pg.full.norm if pg is not None else buf.norm
+        if "best" in state:
+            outs["score_argmin"] = state["best"]
+        dump_outputs(args.dump_outputs, outs)
+
+    x0_stored = want_x0 or args.operator == "inpainting"
+    value = total * args.steps / elapsed
+    step_s = elapsed / args.steps
+
+    def result_line(**extra):
+        what = {"dps": "'ps' scale 0.3, one global best-of-N select at the end",
+                "dps_scores": "'ps' scale 0.3, per-step all-gather of the particle scores + global argmin",
+                "search": "search_ddpm step: S1, scoring, per-step global select, " +
+                          ("ONE state particle kept (SearchDDPM.single_state)" if single else "winner replicated to all N"),
+                "resample": f"ttc_ddim step (DDIM S1) with 'ps' scale 0.3, global multinomial resampling every "
+                            f"{args.resample_every} steps"}[wl]
+        fetch = args.resample_fetch if args.resample_fetch != "auto" else ("selected" if world > 2 else "all")
+        exchange = {"dps": "ONE champion all-gather at the closing select (1 particle + its score and index per rank)",
+                    "dps_scores": "RCCL all-gather of the [N/G] scores every step",
+                    "search": "per step: ONE all-gather of one champion particle + its score per rank, device-side pick",
+                    "resample": f"every {args.resample_every} steps: all-gather of scores, identical device multinomial "
+                                f"draw on every rank, " + ("all-to-all of the drawn particles (each once per destination)"
+                                                           if fetch == "selected" else "all-gather of states") +
+                                " + HIP gather"}[wl]
+        return {
+            "metric": "particles×denoise-steps/sec @256×256 N=64; x0_hat rel-L2 vs ref",
+            "value": value, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"FFHQ-shaped 256x256 {WORKLOADS[args.operator]}, {what}, "
+                                   f"N={total} particles ({'/'.join(str(c) for c in sorted(set(counts)))} per GPU), "
+                                   f"t cycling 999->0" + (", stand-in semantic-guidance cotangent (anneal 10x)" if semantic else ""),
+                       "operator": args.operator, "step": wl, "particles_per_gpu": n, "global_particles": total,
+                       "image": "3x256x256",
+                       "chains_per_gpu": nch,
+                       "x0_hat_store": x0_stored,
+                       "semantic_stand_in": semantic,
+                       "process_group": (os.environ.get("DPSX_BENCH_BACKEND", "nccl") + f" x{world}") if use_pg else None,
+                       "parallelism": f"particles sharded x{world} ({args.scaling} scaling); per GPU {nch} independent "
+                                      f"particle group(s) (kernels.ParticleGroups), one HIP stream each; {exchange}"},
+            **extra,
+            "best_of_n_index": best,
+        }
+
+    def emit(line):
+        sys.stdout.flush()
+        os.dup2(real_stdout, 1)
+        print(json.dumps(line), flush=True)
+        os.dup2(2, 1)
+
+    if not args.full:
+        if rank == 0:
+            emit(result_line())
+        if use_pg:
+            dist.destroy_process_group()
+        return
 
     # ---- the same steps as ONE chain of all N particles (the schedule of sampler.particle_groups = 1), timed the same
     # way, so that the line carries both figures
@@ -586,13 +693,10 @@ def main():
         del src, dst
 
     if rank == 0:
-        x0_stored = want_x0 or args.operator == "inpainting"
         table = algo_p(args.operator, x0_store=x0_stored, workload="search_single" if single else wl, semantic=semantic)
         algo = {k: v * P_BYTES for k, v in table["algorithmic"].items()}
         survey_step_p = sum(table["survey"].values())
         algo_step_p = sum(table["algorithmic"].values())
-        value = total * args.steps / elapsed
-        step_s = elapsed / args.steps
         dom = max(dur, key=dur.get)
         names = dict(SEARCH_KERNELS) if wl == "search" else \
             dict(KERNELS[args.operator], upd="x_{t-1} = sample - (a g_pre + g_unet) (k_step_update)")
@@ -653,45 +757,10 @@ def main():
                                 "frac": {k: v / VALU_F32_PEAK_TFLOPS for k, v in valu.items()}}
             hb, vb = roofline["frac"], valu.get(dom, 0.0) / VALU_F32_PEAK_TFLOPS
             roofline["binding"] = "valu" if vb > hb else "hbm"
-        what = {"dps": "'ps' scale 0.3, one global best-of-N select at the end",
-                "dps_scores": "'ps' scale 0.3, per-step all-gather of the particle scores + global argmin",
-                "search": "search_ddpm step: S1, scoring, per-step global select, " +
-                          ("ONE state particle kept (SearchDDPM.single_state)" if single else "winner replicated to all N"),
-                "resample": f"ttc_ddim step (DDIM S1) with 'ps' scale 0.3, global multinomial resampling every "
-                            f"{args.resample_every} steps"}[wl]
-        fetch = args.resample_fetch if args.resample_fetch != "auto" else ("selected" if world > 2 else "all")
-        exchange = {"dps": "ONE champion all-gather at the closing select (1 particle + its score and index per rank)",
-                    "dps_scores": "RCCL all-gather of the [N/G] scores every step",
-                    "search": "per step: ONE all-gather of one champion particle + its score per rank, device-side pick",
-                    "resample": f"every {args.resample_every} steps: all-gather of scores, identical device multinomial "
-                                f"draw on every rank, " + ("all-to-all of the drawn particles (each once per destination)"
-                                                           if fetch == "selected" else "all-gather of states") +
-                                " + HIP gather"}[wl]
-        line = {
-            "metric": "particles×denoise-steps/sec @256×256 N=64; x0_hat rel-L2 vs ref",
-            "value": value, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"FFHQ-shaped 256x256 {WORKLOADS[args.operator]}, {what}, "
-                                   f"N={total} particles ({'/'.join(str(c) for c in sorted(set(counts)))} per GPU), "
-                                   f"t cycling 999->0" + (", stand-in semantic-guidance cotangent (anneal 10x)" if semantic else ""),
-                       "operator": args.operator, "step": wl, "particles_per_gpu": n, "global_particles": total,
-                       "image": "3x256x256",
-                       "chains_per_gpu": nch,
-                       "x0_hat_store": x0_stored,
-                       "semantic_stand_in": semantic,
-                       "process_group": (os.environ.get("DPSX_BENCH_BACKEND", "nccl") + f" x{world}") if use_pg else None,
-                       "parallelism": f"particles sharded x{world} ({args.scaling} scaling); per GPU {nch} independent "
-                                      f"particle group(s) (kernels.ParticleGroups), one HIP stream each; {exchange}"},
-            "roofline": roofline,
-            "best_of_n_index": best,
-        }
+        line = result_line(roofline=roofline)
         if world == 1 and not args.no_cpu_baseline and wl == "dps" and not semantic:
             line["cpu_baseline"], line["x0_hat_rel_l2"] = cpu_baseline(args, op, fkw, smp, ring, x_t, y, handle, device)
-        sys.stdout.flush()
-        os.dup2(real_stdout, 1)
-        print(json.dumps(line), flush=True)
-        os.dup2(2, 1)
+        emit(line)
     if use_pg:
         dist.destroy_process_group()
 

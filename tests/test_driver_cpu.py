@@ -154,9 +154,39 @@ def test_bench_byte_table_and_cli():
         sys.argv = ["bench.py"]
         a = bench.parse()
         assert (a.gpus, a.workload, a.operator, a.particles, a.chains) == (1, "dps", "gaussian_blur", 64, 0)
+        assert (a.full, a.dump_outputs) == (False, None)
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3", "--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, True, "out")
     finally:
         sys.argv = old
     assert abs(bench.semantic_scale(0.3, 10.0, 0.0) - 0.3 * (1 + 9 / (1 + np.exp(-3.0)))) < 1e-12
+
+
+def test_bench_dump_outputs_dtypes_and_budget(tmp_path):
+    """bench.dump_outputs: floats as float32, integers as float64; over the budget the largest array keeps the same seeded
+    sample of its rows on every call, the row indices beside it"""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.arange(40 * 6, dtype=torch.float32).reshape(40, 6)
+    ts = {"x_next": x, "norm": torch.linspace(0, 1, 40), "best_of_n_index": torch.tensor(5)}
+    bench.dump_outputs(str(tmp_path / "all"), ts)
+    a = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ts}
+    assert a["x_next"].dtype == np.float32 and np.array_equal(a["x_next"], x.numpy())
+    assert a["best_of_n_index"].dtype == np.float64 and a["best_of_n_index"].tolist() == [5.0]
+    budget = 10 * 6 * 4 + 10 * 8 + 40 * 4 + 8          # room for 10 rows of x_next and their indices
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), ts, budget=budget)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    assert sorted(s1) == ["best_of_n_index.npy", "norm.npy", "x_next.npy", "x_next_rows.npy"]
+    assert sum(v.nbytes for v in s1.values()) <= budget
+    rows = s1["x_next_rows.npy"].astype(np.int64)
+    assert len(rows) == 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s1["x_next.npy"], x.numpy()[rows])
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)
 
 
 def test_particle_groups_partition():

@@ -180,7 +180,7 @@ def test_bench_self_launch_two_ranks():
     env = dict(os.environ, DPSX_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--particles", "4", "--no-cpu-baseline"], env=env, capture_output=True, timeout=900)
+                        "--particles", "4", "--no-cpu-baseline", "--full"], env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -208,7 +208,7 @@ def test_bench_sharded_workloads_two_ranks(mode):
     env = dict(os.environ, DPSX_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", *mode], env=env, capture_output=True, timeout=900)
+                        "--no-cpu-baseline", "--full", *mode], env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -229,7 +229,8 @@ def test_bench_line_carries_both_schedules():
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+                        "--full"],
                        env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     rec = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.strip()][-1])
@@ -242,6 +243,39 @@ def test_bench_line_carries_both_schedules():
     for k, v in rf["per_launch"].items():
         assert v["moved_bytes"] and v["moved_GBps"] < 8000.0 and v["algorithmic_GBps"] < 8000.0, (k, v)
     assert rf["step_frac_moved"] < rf["step_frac_of_hbm_roofline"] <= 1.0
+
+
+def test_bench_plain_run_dumps_repeatable_outputs(tmp_path):
+    """a plain run (no --full) prints the headline line only; --dump-outputs writes what the timed path returned after its
+    last step, and two runs with the same arguments write the same arrays (24 particles: two particle groups)"""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    recs, outs = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--particles", "24", "--dump-outputs", str(d)], env=env, capture_output=True, timeout=900)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+        outs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["config"]["chains_per_gpu"] == 2 and "roofline" not in rec and "cpu_baseline" not in rec
+    o = outs[0]
+    assert sorted(o) == ["best_of_n_index", "norm", "winner", "x_next"]
+    assert o["x_next"].shape == (24, 3, 256, 256) and o["norm"].shape == (24,) and o["winner"].shape == (1, 3, 256, 256)
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values())
+    assert sum(a.nbytes for a in o.values()) <= 64 * 10 ** 6
+    best = int(o["best_of_n_index"][0])
+    assert best == rec["best_of_n_index"] and best == int(np.argmin(o["norm"]))
+    assert np.array_equal(o["winner"][0], o["x_next"][best]) and np.isfinite(o["x_next"]).all()
+    assert sorted(outs[1]) == sorted(o)
+    for k in o:
+        assert np.array_equal(outs[1][k], o[k]), k
 
 
 @pytest.mark.parametrize("operator", ["gaussian_blur", "motion_blur", "inpainting"])

@@ -13,6 +13,6 @@ for csr in 0 1; do
   if [ $csr = 1 ]; then export DPSX_RESIZE_ADJ_CSR=1; else unset DPSX_RESIZE_ADJ_CSR; fi
   for n in 64 16; do
     echo "== bench N=$n csr=$csr"
-    python bench.py --operator super_resolution --particles $n --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(r['value']), round(r['ms_per_step']*1e3,1), {k:round(v*1e3,1) for k,v in r['roofline']['all_launches_ms'].items()}, round(r['roofline']['one_chain_ms_per_step']*1e3,1))"
+    python bench.py --operator super_resolution --particles $n --steps 200 --warmup 20 --no-cpu-baseline --full 2>/dev/null | python3 -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(r['value']), round(r['ms_per_step']*1e3,1), {k:round(v*1e3,1) for k,v in r['roofline']['all_launches_ms'].items()}, round(r['roofline']['one_chain_ms_per_step']*1e3,1))"
   done
 done

@@ -15,12 +15,12 @@ for spec in "motion_blur fwd" "motion_blur bwd" "phase_retrieval fwd" "phase_ret
 done
 cat $OUT/${TAG}_sq_*_summary.txt
 # BASELINE configs at their own N
-python3 bench.py --operator super_resolution --particles 16 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_sr4_n16.json 2> $OUT/${TAG}_bench_misc.err; echo "sr16 rc=$?"
-python3 bench.py --operator super_resolution --particles 16 --chains 1 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_sr4_n16_one_chain.json 2>> $OUT/${TAG}_bench_misc.err
-python3 bench.py --operator motion_blur --particles 32 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_motion_n32.json 2>> $OUT/${TAG}_bench_misc.err; echo "motion32 rc=$?"
-python3 bench.py --operator motion_blur --particles 32 --workload dps_scores --semantic --steps 200 --warmup 20 > $OUT/${TAG}_bench_motion_n32_semantic_scores.json 2>> $OUT/${TAG}_bench_misc.err; echo "motion32 sem rc=$?"
-python3 bench.py --operator phase_retrieval --workload resample --steps 200 --warmup 20 > $OUT/${TAG}_bench_phase_resample.json 2>> $OUT/${TAG}_bench_misc.err; echo "phase resample rc=$?"
-python3 bench.py --workload search --steps 200 --warmup 20 > $OUT/${TAG}_bench_search.json 2>> $OUT/${TAG}_bench_misc.err; echo "search rc=$?"
+python3 bench.py --full --operator super_resolution --particles 16 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_sr4_n16.json 2> $OUT/${TAG}_bench_misc.err; echo "sr16 rc=$?"
+python3 bench.py --full --operator super_resolution --particles 16 --chains 1 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_sr4_n16_one_chain.json 2>> $OUT/${TAG}_bench_misc.err
+python3 bench.py --full --operator motion_blur --particles 32 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/${TAG}_bench_motion_n32.json 2>> $OUT/${TAG}_bench_misc.err; echo "motion32 rc=$?"
+python3 bench.py --full --operator motion_blur --particles 32 --workload dps_scores --semantic --steps 200 --warmup 20 > $OUT/${TAG}_bench_motion_n32_semantic_scores.json 2>> $OUT/${TAG}_bench_misc.err; echo "motion32 sem rc=$?"
+python3 bench.py --full --operator phase_retrieval --workload resample --steps 200 --warmup 20 > $OUT/${TAG}_bench_phase_resample.json 2>> $OUT/${TAG}_bench_misc.err; echo "phase resample rc=$?"
+python3 bench.py --full --workload search --steps 200 --warmup 20 > $OUT/${TAG}_bench_search.json 2>> $OUT/${TAG}_bench_misc.err; echo "search rc=$?"
 for f in sr4_n16 sr4_n16_one_chain motion_n32 motion_n32_semantic_scores phase_resample search; do
   python3 -c "import json;d=json.load(open('$OUT/${TAG}_bench_$f.json'));r=d['roofline'];print('$f', round(d['value']), 'p-s/s', round(d['ms_per_step']*1e3,1),'us/step', {k:round(v*1e3,1) for k,v in r['all_launches_ms'].items()}, 'step_frac', round(r['step_frac_of_hbm_roofline'],3), 'moved', r.get('step_frac_moved'))"
 done
