@@ -48,6 +48,7 @@ SIGNATURES = {
     "dpsx_op_create_resize": (c_int, [_i64, _i64, POINTER(c_float), POINTER(c_int64), _i64, _i64,
                                       POINTER(c_float), POINTER(c_int64), _i64, _i64, POINTER(c_void_p)]),
     "dpsx_op_create_mask": (c_int, [_f, _i64, _i64, POINTER(c_void_p)]),
+    "dpsx_op_create_mask_n": (c_int, [_f, _i64, _i64, _i64, POINTER(c_void_p)]),
     "dpsx_op_create_identity": (c_int, [POINTER(c_void_p)]),
     "dpsx_op_create_phase": (c_int, [_i64, _i64, _i64, POINTER(c_void_p)]),
     "dpsx_op_destroy": (None, [c_void_p]),
@@ -73,8 +74,13 @@ SIGNATURES = {
                                      POINTER(Coefs), _p, _i64, _p]),
     "dpsx_search_step_one_f32": (c_int, [c_void_p, _f, _f, _f, _f, _i64, _f, _f, _p, _f, _f, _i64, _i64, _i64, _i64,
                                          POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_search_step_seg_f32": (c_int, [c_void_p, _f, _f, _f, _f, _i64, _f, _f, _p, _f, _f, _i64, _i64, _i64, _i64,
+                                         _i64, POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_search_step_one_seg_f32": (c_int, [c_void_p, _f, _f, _f, _f, _i64, _f, _f, _p, _f, _f, _i64, _i64, _i64, _i64,
+                                             _i64, POINTER(Coefs), _p, _i64, _p]),
     "dpsx_resample_cost_f32": (c_int, [c_void_p, _f, _f, _i64, _f, c_int, _f, _f, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_argmin_f32": (c_int, [_f, _i64, _p, _f, _p]),
+    "dpsx_argmin_seg_f32": (c_int, [_f, _i64, _i64, _p, _f, _p]),
     "dpsx_gather_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
     "dpsx_replicate_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),

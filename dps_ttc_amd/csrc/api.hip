@@ -242,11 +242,17 @@ int dpsx_op_create_resize(int64_t in_h, int64_t in_w, const float *w_h_host, con
 
 int dpsx_op_create_mask(const float *mask_dev, int64_t h, int64_t w, dpsx_op **out)
 {
-    if (!mask_dev || !out || h < 1 || w < 1) return DPSX_EINVAL;
+    return dpsx_op_create_mask_n(mask_dev, 1, h, w, out);
+}
+
+int dpsx_op_create_mask_n(const float *mask_dev, int64_t mask_n, int64_t h, int64_t w, dpsx_op **out)
+{
+    if (!mask_dev || !out || mask_n < 1 || mask_n > (1 << 24) || h < 1 || w < 1) return DPSX_EINVAL;
     dpsx_op *op = new (std::nothrow) dpsx_op();
     if (!op) return DPSX_ENOMEM;
     op->kind = OP_MASK;
     op->mask = mask_dev;
+    op->mask_n = mask_n;
     op->in_h = h; op->in_w = w;
     return finish_create(op, out);
 }
@@ -384,9 +390,13 @@ static int carve(const dpsx_op *op, void *ws, int64_t ws_bytes, int64_t n, int64
     return DPSX_OK;
 }
 
+// a table of `rows` entries serves n particles when rows divides n (common.h: meas_row); rows == n == 0 stays valid
+static bool rows_ok(int64_t rows, int64_t n) { return rows == 1 || rows == n || (rows > 1 && n % rows == 0); }
+
 static int check_geom(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
 {
     if (!op || n < 0 || c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
+    if (op->kind == OP_MASK && !rows_ok(op->mask_n, n)) return DPSX_EINVAL;
     if (n * c > (1 << 24)) return DPSX_EUNSUPPORTED;
     int64_t oh, ow;
     return dpsx_op_out_shape(op, h, w, &oh, &ow);
@@ -403,7 +413,7 @@ int dpsx_op_forward_f32(dpsx_op *op, const float *x, float *y, int64_t n, int64_
     case OP_SEP:
     case OP_TAPS: return blur_forward(op, x, y, n * c, h, w, s);
     case OP_RESIZE: return resize_forward(op, x, y, n * c, s);
-    case OP_MASK: return mask_mul(x, op->mask, y, n * c, h * w, s);
+    case OP_MASK: return mask_mul(x, op->mask, y, n * c, h * w, s, c, row_div(op->mask_n, n));
     case OP_IDENT:
         DPSX_HIP_TRY(hipMemcpyAsync(y, x, (size_t)(n * c * h * w) * 4, hipMemcpyDeviceToDevice, s));
         return DPSX_OK;
@@ -431,7 +441,7 @@ int dpsx_op_adjoint_f32(dpsx_op *op, const float *u, const float *x, float *g, i
         return blur_adjoint(op, u, g, n * c, h, w, static_cast<float *>(ws.priv), ws.priv_bytes, s);
     }
     case OP_RESIZE: return resize_adjoint(op, u, g, n * c, s);
-    case OP_MASK: return mask_mul(u, op->mask, g, n * c, h * w, s);
+    case OP_MASK: return mask_mul(u, op->mask, g, n * c, h * w, s, c, row_div(op->mask_n, n));
     case OP_IDENT:
         DPSX_HIP_TRY(hipMemcpyAsync(g, u, (size_t)(n * c * h * w) * 4, hipMemcpyDeviceToDevice, s));
         return DPSX_OK;
@@ -449,7 +459,7 @@ int dpsx_op_adjoint_f32(dpsx_op *op, const float *u, const float *x, float *g, i
 int dpsx_residual_norm_f32(const float *y, int64_t y_n, const float *ax, float *r, float *norm, int64_t n,
                            int64_t m, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (!y || !ax || !norm || n < 0 || m < 0 || (y_n != 1 && y_n != n)) return DPSX_EINVAL;
+    if (!y || !ax || !norm || n < 0 || m < 0 || !rows_ok(y_n, n)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
     const int parts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (m + 4095) / 4096));
     if (!workspace || workspace_bytes < n * parts * 4) return DPSX_EWORKSPACE;
@@ -506,7 +516,7 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
         !(op->kind == OP_PHASE && phase_is_spectral(op)))
         return DPSX_EINVAL;
     if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if (y_n != 1 && y_n != n) return DPSX_EINVAL;
+    if (!rows_ok(y_n, n)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
     Ws ws;
     if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
@@ -515,6 +525,8 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
     const int64_t chw = c * h * w;
     StepFwdArgs a{x_t, model_out, noise, y, y_n, x0_hat, sample, inside, static_cast<float *>(resid),
                   ws.partials, n, c, h, w, k};
+    a.y_div = row_div(y_n, n);
+    a.mask_div = row_div(op->mask_n, n);
     int parts = (int)parts_per_particle(op, c, h, w);
     // norm != NULL: the launch itself finishes the per-particle reduction (each particle's last block re-sums its
     // partials in the order of k_finalize_norm -- bit-identical, no extra launch)
@@ -580,6 +592,7 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     if (rc != DPSX_OK) return rc;
     if (!resid || !inside || !g_model_out || !coefs_host || (power != 1 && power != 2)) return DPSX_EINVAL;
     if (!norm && !norm_out) return DPSX_EINVAL;
+    if (y && !rows_ok(y_n, n)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
     Ws ws;
     if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
@@ -597,12 +610,14 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     }
     StepBwdArgs b{static_cast<const float *>(resid), norm, ws.partials, parts, norm_out, inside, x0_hat, y, y_n,
                   scale, power, g_model_out, n, c, h, w, k, g_x0_extra};
+    b.y_div = row_div(y_n, n);
+    b.mask_div = row_div(op->mask_n, n);
     switch (op->kind) {
     case OP_SEP:
     case OP_TAPS: return blur_step_bwd(op, b, static_cast<float *>(ws.priv), ws.priv_bytes, s);
     case OP_RESIZE: return resize_step_bwd(op, b, s);
     case OP_MASK:
-        if (!x0_hat || !y || (y_n != 1 && y_n != n)) return DPSX_EINVAL;
+        if (!x0_hat || !y || !rows_ok(y_n, n)) return DPSX_EINVAL;
         if (!mask_fused_ok(op, c, h, w, {x0_hat, y, g_model_out}) || (reinterpret_cast<uintptr_t>(inside) & 3u))
             return DPSX_EUNSUPPORTED;
         return mask_step_bwd(op, b, s);
@@ -652,7 +667,8 @@ static int score_launch(dpsx_op *op, const Ws &ws, const float *x, const float *
     case OP_RESIZE: return resize_score(op, x, y, y_n, ws.partials, n, c, l1, tail, s);
     case OP_IDENT: return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, tail);
     case OP_MASK:      // y - mask * x in the reduction itself (one launch, no scratch)
-        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, tail, op->mask, h * w);
+        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, tail, op->mask, h * w,
+                                 op->mask_n);
     case OP_PHASE: {
         // A x into scratch, then the generic residual reduction
         const int64_t m = meas_elems(op, c, h, w);
@@ -697,7 +713,7 @@ static int score_impl(dpsx_op *op, const float *x, const float *y, int64_t y_n, 
 {
     int rc = check_geom(op, n, c, h, w);
     if (rc != DPSX_OK) return rc;
-    if (!x || !y || !costs || (y_n != 1 && y_n != n)) return DPSX_EINVAL;
+    if (!x || !y || !costs || !rows_ok(y_n, n)) return DPSX_EINVAL;
     if (n == 0) return best_idx ? DPSX_EINVAL : DPSX_OK;
     Ws ws;
     if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
@@ -716,7 +732,7 @@ int dpsx_search_step_f32(dpsx_op *op, const float *x_t, const float *model_out, 
     if (rc != DPSX_OK) return rc;
     if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
     if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if ((y_n != 1 && y_n != n) || n == 0 || x_next == sample) return DPSX_EINVAL;
+    if (!rows_ok(y_n, n) || n == 0 || x_next == sample) return DPSX_EINVAL;
     // S1 (no x0_hat store) -> scoring launch -> one launch for costs + select -> the winner's replication.
     // Measured and dropped (N = 64, Gaussian, 89.7 us for this sequence): S1 fused into the separable scoring kernel (the
     // proposal's halo needs all four input streams: 72 us for the fused launch against 37 + 30 for the two); costs +
@@ -745,7 +761,7 @@ int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_o
     if (rc != DPSX_OK) return rc;
     if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
     if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if ((y_n != 1 && y_n != n) || n == 0 || x_next == sample || x_next == x_t) return DPSX_EINVAL;
+    if (!rows_ok(y_n, n) || n == 0 || x_next == sample || x_next == x_t) return DPSX_EINVAL;
     // After a select every particle of SearchDDPM is a copy of the winner (img[best_path.repeat(n_paths)], :633), so the
     // loop's state is ONE particle: S1 reads that state and its model output once for all n proposals (the per-particle
     // noise makes them differ), the scoring launch and the select are the n-particle ones, and the winner is copied out
@@ -766,6 +782,72 @@ int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_o
     rc = finalize_select(tail, s);
     if (rc != DPSX_OK || !x_next) return rc;
     return gather_f32(sample, best_idx_dev, x_next, 1, n, chw, true, s);
+}
+
+// ------------------------------------------------------------------ multi-image search (segments of n / segments particles)
+// The argument checks of both segmented steps; y holds one row (broadcast) or one per segment.
+static int search_seg_args(const dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+                           int64_t y_n, const float *sample, const float *costs, const int64_t *best_idx_dev,
+                           const float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
+                           const dpsx_coefs *coefs_host)
+{
+    int rc = check_geom(op, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
+    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
+    if (n == 0 || segments < 1 || n % segments != 0 || (y_n != 1 && y_n != segments)) return DPSX_EINVAL;
+    if (x_next == sample || x_next == x_t) return DPSX_EINVAL;
+    return DPSX_OK;
+}
+
+int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+                             int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev, float *best_val_dev,
+                             float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
+                             const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = search_seg_args(op, x_t, model_out, noise, y, y_n, sample, costs, best_idx_dev, x_next, segments, n, c, h, w,
+                             coefs_host);
+    if (rc != DPSX_OK) return rc;
+    // the launches of dpsx_search_step_f32; the select runs one block per segment and the replication copies each
+    // segment's winner over that segment's particles
+    Ws ws;
+    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chw = c * h * w;
+    const int parts = score_parts(op, c, h, w);
+    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s);
+    if (rc != DPSX_OK) return rc;
+    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
+    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
+    rc = finalize_select_seg(tail, (int)segments, s);
+    if (rc != DPSX_OK || !x_next) return rc;
+    return replicate_seg_f32(sample, best_idx_dev, x_next, n, n / segments, n, chw, s);
+}
+
+int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                                 const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
+                                 float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h,
+                                 int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
+                                 void *stream)
+{
+    int rc = search_seg_args(op, x_t, model_out, noise, y, y_n, sample, costs, best_idx_dev, x_next, segments, n, c, h, w,
+                             coefs_host);
+    if (rc != DPSX_OK) return rc;
+    // one state per segment: proposal p reads state p / (n / segments); x_next receives each segment's winner once
+    Ws ws;
+    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chw = c * h * w;
+    const int parts = score_parts(op, c, h, w);
+    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments);
+    if (rc != DPSX_OK) return rc;
+    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
+    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
+    if (x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))   // costs + select + the winners' copies: one launch
+        return finalize_select_copy_seg(tail, (int)segments, sample, x_next, chw, s);
+    rc = finalize_select_seg(tail, (int)segments, s);
+    if (rc != DPSX_OK || !x_next) return rc;
+    return gather_f32(sample, best_idx_dev, x_next, segments, n, chw, false, s);
 }
 
 int dpsx_score_f32(dpsx_op *op, const float *x, const float *y, int64_t y_n, float *costs, int64_t n, int64_t c,
@@ -797,6 +879,13 @@ int dpsx_argmin_f32(const float *v, int64_t n, int64_t *idx_out_dev, float *val_
 {
     if (!v || !idx_out_dev || n < 1) return DPSX_EINVAL;
     return argmin_f32(v, n, idx_out_dev, val_out_dev, (hipStream_t)stream);
+}
+
+int dpsx_argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx_out_dev, float *val_out_dev,
+                        void *stream)
+{
+    if (!v || !idx_out_dev || segments < 1 || segments > (1 << 24) || k < 1) return DPSX_EINVAL;
+    return argmin_seg_f32(v, segments, k, idx_out_dev, val_out_dev, (hipStream_t)stream);
 }
 
 int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst, int64_t n_out, int64_t n_src,

@@ -35,7 +35,7 @@ struct BlurArgs {
     uint8_t *inside_w;
     // residual epilogue (RESID)
     const float *y;
-    int y_n;
+    unsigned y_div;       // row_div(y_n, n): particle q reads measurement row meas_row(q, y_div)
     float *partials;      // [planes * tiles]
     // adjoint epilogue (EPI)
     const float *norm_in; // [n] finalized norms, or nullptr: derive from norm_partials (fused bwd half)
@@ -194,7 +194,7 @@ __device__ __forceinline__ float resid_epilogue(const BlurArgs &a, int plane, in
     float ss = 0.0f;
     if (oy >= a.h) return 0.0f;
     const int n = plane / a.c, ch = plane % a.c;
-    const float *yp = a.y + ((int64_t)(a.y_n == 1 ? 0 : n) * a.c + ch) * hw + (int64_t)oy * a.w;
+    const float *yp = a.y + ((int64_t)meas_row((unsigned)n, a.y_div) * a.c + ch) * hw + (int64_t)oy * a.w;
     float *rp = a.out ? a.out + (int64_t)plane * hw + (int64_t)oy * a.w : nullptr;
     if (VEC4 && count == 4 && ox + 3 < a.w) {
         const float4 yv = *reinterpret_cast<const float4 *>(yp + ox);
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(NT, 4) void k_blur_taps(BlurArgs a, TapGeom g)
         // full tile: the lane's 8 x 2 measurement values are fetched together (one wait), then r = y - A(x0_hat)
         const unsigned hw = (unsigned)(a.h * a.w), o = (unsigned)((h0 + r0) * a.w + ox);
         const int n = plane / a.c, ch = plane % a.c;
-        const float *yp = a.y + ((int64_t)(a.y_n == 1 ? 0 : n) * a.c + ch) * hw + o;
+        const float *yp = a.y + ((int64_t)meas_row((unsigned)n, a.y_div) * a.c + ch) * hw + o;
         float *rp = a.out ? a.out + (int64_t)plane * hw + o : nullptr;
         v2f yv[PRW];
 #pragma unroll
@@ -1528,7 +1528,7 @@ int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     BlurArgs a{};
     a.x_t = f.x_t; a.model_out = f.model_out; a.noise = f.noise;
     a.x0_hat = f.x0_hat; a.sample = f.sample; a.inside_w = f.inside;
-    a.y = f.y; a.y_n = (int)f.y_n; a.out = f.resid; a.partials = f.partials;
+    a.y = f.y; a.y_div = f.y_div; a.out = f.resid; a.partials = f.partials;
     a.k = f.k;
     fill_geometry(a, f.n * f.c, f.c, f.h, f.w);
     a.tail = f.tail;
@@ -1559,7 +1559,7 @@ int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, f
     if (!geometry_ok(op, h, w)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
     BlurArgs a{};
-    a.x = x; a.y = y; a.y_n = (int)y_n; a.out = nullptr; a.partials = partials;
+    a.x = x; a.y = y; a.y_div = row_div(y_n, n); a.out = nullptr; a.partials = partials;
     fill_geometry(a, n * c, c, h, w);
     a.l1 = l1;
     a.tail = tail;

@@ -585,7 +585,7 @@ __global__ __launch_bounds__(NT, sep_waves_per_simd(R4, !POST && !RESID)) void k
         if (!ABL(8)) {
             const unsigned hw = (unsigned)(a.h * a.w), o = (unsigned)((h0 + 4 * rg) * a.w + ox);
             const int n = plane / a.c, ch = plane % a.c;
-            const float *yp = a.y + ((int64_t)(a.y_n == 1 ? 0 : n) * a.c + ch) * hw + o;
+            const float *yp = a.y + ((int64_t)meas_row((unsigned)n, a.y_div) * a.c + ch) * hw + o;
             float *rp = a.out ? a.out + (int64_t)plane * hw + o : nullptr;
             float4 yv[4];
 #pragma unroll

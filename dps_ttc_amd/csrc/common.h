@@ -361,6 +361,18 @@ __device__ __forceinline__ void tail_arrive(const Tail &t, int particle)
     }
 }
 
+// -------------------------------------------------------------------- measurement / mask rows
+// A table of `rows` entries (measurements y, inpainting masks) with rows | n: particle p reads entry p / (n / rows), so one
+// entry is broadcast, n entries are one per particle, and M entries serve M images of n / M particles each (image-major).
+// The launch carries the divisor `div` = n / rows, or 0 for one broadcast entry: the two old cases (0, 1) take no division;
+// the others one 32-bit division per tile / block, never per element.
+inline unsigned row_div(int64_t rows, int64_t n) { return rows == 1 ? 0u : (unsigned)(n / rows); }
+
+__device__ __forceinline__ unsigned meas_row(unsigned p, unsigned div)
+{
+    return div == 0 ? 0u : (div == 1 ? p : p / div);
+}
+
 // ReflectionPad2d index map (no edge repeat); valid while |overhang| < n.
 __device__ __forceinline__ int reflect_idx(int i, int n)
 {
@@ -411,8 +423,9 @@ struct dpsx_op {
     // ---- resize
     int64_t in_h = 0, in_w = 0, out_h = 0, out_w = 0, taps_h = 0, taps_w = 0;
     float *d_w_h = nullptr;  // resize.hip keeps its table owner (ResizeHost*) here
-    // ---- mask
+    // ---- mask: [mask_n, h, w], particle p of n uses mask p / (n / mask_n)
     const float *mask = nullptr;
+    int64_t mask_n = 1;
     // ---- "last block done" arrival counters (see Tail): [1 + kTailMaxParticles], zero between launches
     unsigned *d_counters = nullptr;
     // ---- phase
@@ -434,6 +447,7 @@ struct StepFwdArgs {
     int64_t n, c, h, w;
     Coefs k;
     Tail tail{};      // per-particle finalisation inside the launch (tail.counters == nullptr: not requested / not supported)
+    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
 };
 
 struct StepBwdArgs {
@@ -450,6 +464,7 @@ struct StepBwdArgs {
     int64_t n, c, h, w;
     Coefs k;
     const float *g_extra = nullptr;   // optional extra cotangent on x0_hat [n, c, h, w], added before the clamp gate
+    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
 };
 
 // blur.hip
@@ -477,21 +492,33 @@ int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n,
                  int64_t n, int64_t c, int l1, const Tail &tail, hipStream_t s);
 
 // elementwise.hip
-// one_state: x [1, chw] and mo [1, 2 chw] feed all n particles (z, x0, sample, inside stay per particle)
+// one_state: x [states, chw] and mo [states, 2 chw] feed all n particles, n / states consecutive particles per state
+// (z, x0, sample, inside stay per particle)
 int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, float *sample, uint8_t *inside,
-                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false);
+                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false, int64_t states = 1);
 int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const float *mo, const float *z,
                   float *g_x, float *g_mo, int64_t n, int64_t chw, const Coefs &k, hipStream_t s);
-int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_t hw, hipStream_t s);
+// mask [mask_n, hw]: plane q (of n * c) uses mask meas_row(q / c, mask_div), mask_div = row_div(mask_n, n)
+int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_t hw, hipStream_t s, int64_t c = 1,
+             unsigned mask_div = 0);
 // sums of squares of (y - ax) per particle in `parts` chunks -> partials[n*parts]; r optional
 int residual_partials(const float *y, int64_t y_n, const float *ax, float *r, float *partials,
                       int64_t n, int64_t m, int parts, hipStream_t s, int l1 = 0, const Tail &tail = Tail{},
-                      const float *mask = nullptr, int64_t hw = 0);
+                      const float *mask = nullptr, int64_t hw = 0, int64_t mask_n = 1);
 int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipStream_t s);
 // one small launch: per-particle values from the partials (t.partials / parts / mode / prev / potential -> raw_out, out)
 // and, if t.best_idx, the torch.argmin-order select over them (t.counters is not used)
 int finalize_select(const Tail &t, hipStream_t s);
 int finalize_select_copy(const Tail &t, const float *src, float *dst, int64_t chw, hipStream_t s);
+// the same per segment: `segments` consecutive groups of t.n / segments particles; t.best_idx / t.best_val are [segments]
+// and receive each segment's winner as a global particle index.  _copy: dst[m] = src[best[m]] (chw % 4 == 0, aligned)
+int finalize_select_seg(const Tail &t, int segments, hipStream_t s);
+int finalize_select_copy_seg(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
+// segmented argmin over v [segments, k] -> idx[m] = m * k + argmin (torch.argmin order), val[m] (nullable)
+int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s);
+// dst[p] = src[ids[p / per]] for p < n_out (per = particles per id); an id outside [0, n_src) fills dst[p] with NaN
+int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t per, int64_t n_src,
+                      int64_t chw, hipStream_t s);
 int norm_bwd(const float *r, const float *norm, const float *g_norm, int power, float *g_ax,
              int64_t n, int64_t m, hipStream_t s);
 // g_model_out[:, :c] = -b * (inside ? coef_p * g_x0 : 0),  g_x0 = A^T r

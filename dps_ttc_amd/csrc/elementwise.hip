@@ -24,13 +24,15 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
                                                             const float *__restrict__ z,
                                                             float *__restrict__ x0o, float *__restrict__ so,
                                                             uint8_t *__restrict__ ins, int64_t chw, Coefs k,
-                                                            int64_t xs)
+                                                            unsigned sdiv)
 {
-    // xs: particle stride of x (and half that of model_out): chw, or 0 when ONE state feeds all particles (search_ddpm)
+    // sdiv: particles per state of x / model_out -- 1: one state per particle; 0: ONE state feeds all particles
+    // (search_ddpm); else n / states: consecutive groups of sdiv particles share a state (search_ddpm over several images)
     const int64_t p = blockIdx.y;
     const int64_t i = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * (VEC ? 4 : 1);
     if (i >= chw) return;
-    const float *xp = x + p * xs + i, *ep = mo + p * 2 * xs + i, *vp = ep + chw;
+    const int64_t st = meas_row((unsigned)p, sdiv);
+    const float *xp = x + st * chw + i, *ep = mo + st * 2 * chw + i, *vp = ep + chw;
     const int64_t o = p * chw + i;
     if constexpr (VEC) {
         const float4 xv = *reinterpret_cast<const float4 *>(xp);
@@ -64,10 +66,10 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
 }
 
 int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, float *sample, uint8_t *inside,
-                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state)
+                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state, int64_t states)
 {
     if (n == 0 || chw == 0) return DPSX_OK;
-    const int64_t xs = one_state ? 0 : chw;
+    const unsigned xs = one_state ? row_div(states, n) : 1u;
     const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && aligned16(z) && aligned16(x0) &&
                      aligned16(sample) && (reinterpret_cast<uintptr_t>(inside) & 3u) == 0;
     if (vec)
@@ -152,19 +154,22 @@ int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const flo
 }
 
 // ===================================================================== inpainting mask
+// mask_div = row_div(mask_n, n): plane q = (particle, channel) reads mask row meas_row(q / c, mask_div)
 __global__ __launch_bounds__(kThreads) void k_mask_mul(const float *__restrict__ x, const float *__restrict__ m,
-                                                       float *__restrict__ y, int64_t hw)
+                                                       float *__restrict__ y, int64_t hw, unsigned c, unsigned mask_div)
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= hw) return;
     const int64_t o = (int64_t)blockIdx.y * hw + i;
-    y[o] = __fmul_rn(x[o], m[i]);
+    const float *mp = mask_div ? m + (int64_t)meas_row(blockIdx.y / c, mask_div) * hw : m;   // launch-uniform
+    y[o] = __fmul_rn(x[o], mp[i]);
 }
 
-int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_t hw, hipStream_t s)
+int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_t hw, hipStream_t s, int64_t c,
+             unsigned mask_div)
 {
     if (planes == 0 || hw == 0) return DPSX_OK;
-    k_mask_mul<<<grid_for(hw, planes), kThreads, 0, s>>>(x, mask, y, hw);
+    k_mask_mul<<<grid_for(hw, planes), kThreads, 0, s>>>(x, mask, y, hw, (unsigned)c, mask_div);
     return check_launch();
 }
 
@@ -173,19 +178,21 @@ int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_
 // mask (nullable, hw elements, broadcast over particles and channels): the inpainting operator applied on the fly,
 // d = y - mask * ax with the product rounded once, exactly as mask_mul + this kernel did in two launches (the search
 // step's scoring of a masked proposal: 44 -> one launch without the 2P round trip through scratch).
-__global__ __launch_bounds__(kThreads) void k_residual_partials(const float *__restrict__ y, int64_t y_n,
+// y_div = row_div(y_n, n); mask [mask_n, hw] with mask_div = row_div(mask_n, n) (per-image masks)
+__global__ __launch_bounds__(kThreads) void k_residual_partials(const float *__restrict__ y, unsigned y_div,
                                                                 const float *__restrict__ ax,
                                                                 float *__restrict__ r,
                                                                 float *__restrict__ partials, int64_t m,
                                                                 int64_t chunk, int l1, Tail tail,
-                                                                const float *__restrict__ mask, int hw)
+                                                                const float *__restrict__ mask, int hw, unsigned mask_div)
 {
     __shared__ float scratch[kThreads / kWave];
     const int64_t p = blockIdx.y, q = blockIdx.x;
-    const float *yp = y + (y_n == 1 ? 0 : p) * m, *ap = ax + p * m;
+    const float *yp = y + (int64_t)meas_row((unsigned)p, y_div) * m, *ap = ax + p * m;
     const int64_t lo = q * chunk, hi = min(m, lo + chunk);
     float acc = 0.0f;
     if (mask) {
+        mask += (int64_t)meas_row((unsigned)p, mask_div) * hw;
         int mi = (int)((lo + threadIdx.x) % hw);                 // walks the mask plane with the element index
         const int step = kThreads % hw;
         for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) {
@@ -208,15 +215,16 @@ __global__ __launch_bounds__(kThreads) void k_residual_partials(const float *__r
 }
 
 int residual_partials(const float *y, int64_t y_n, const float *ax, float *r, float *partials, int64_t n,
-                      int64_t m, int parts, hipStream_t s, int l1, const Tail &tail, const float *mask, int64_t hw)
+                      int64_t m, int parts, hipStream_t s, int l1, const Tail &tail, const float *mask, int64_t hw,
+                      int64_t mask_n)
 {
     if (n == 0) return DPSX_OK;
     if (mask && (hw < 1 || hw > (1 << 30))) return DPSX_EINVAL;
     const int64_t chunk = (m + parts - 1) / parts;
     Tail t = tail;
     t.blocks_per_particle = parts;
-    k_residual_partials<<<dim3(parts, (unsigned)n), kThreads, 0, s>>>(y, y_n, ax, r, partials, m, chunk, l1, t, mask,
-                                                                     (int)hw);
+    k_residual_partials<<<dim3(parts, (unsigned)n), kThreads, 0, s>>>(y, row_div(y_n, n), ax, r, partials, m, chunk, l1, t,
+                                                                     mask, (int)hw, row_div(mask_n, n));
     return check_launch();
 }
 
@@ -247,8 +255,12 @@ int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipS
 constexpr int kSelThreads = 1024;
 // the body of the finalisation + select; `writer`: this block stores the costs / the select's outputs (with several blocks
 // -- k_finalize_select_copy -- every block computes the same values in the same order and ONE of them stores).
-// -> the winner's index (block-uniform, valid in every thread), -1 when no select was asked for
-__device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const bool writer)
+// -> the winner's index (block-uniform, valid in every thread), -1 when no select was asked for.
+// [lo, hi): the particles this block finishes and selects over (a segment of a multi-image batch; 0, t.n otherwise) -- each
+// particle's value comes out of the same loads and adds whatever the range, so segmented and whole launches agree bit for
+// bit; the winner (a global particle index) goes to best_idx[slot] / best_val[slot].
+__device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const bool writer, const int lo, const int hi,
+                                                        const int slot)
 {
     __shared__ float s_v[kSelThreads / kWave];
     __shared__ int64_t s_i[kSelThreads / kWave];
@@ -256,7 +268,7 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nw = kSelThreads / kWave;
     ArgMin best{0.0f, -1};
     constexpr int B = 4;          // particles per wave in flight: their partial loads are issued together (one latency)
-    for (int p0 = wave; p0 < t.n; p0 += nw * B) {
+    for (int p0 = lo + wave; p0 < hi; p0 += nw * B) {
         double acc[B];
 #pragma unroll
         for (int b = 0; b < B; ++b) acc[b] = 0.0;
@@ -264,7 +276,7 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
             float v[B];
 #pragma unroll
             for (int b = 0; b < B; ++b) {
-                const int p = min(p0 + b * nw, t.n - 1);             // surplus slots re-read the last particle
+                const int p = min(p0 + b * nw, hi - 1);              // surplus slots re-read the last particle
                 v[b] = t.partials[(int64_t)p * t.parts + i];
             }
 #pragma unroll
@@ -273,7 +285,7 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
 #pragma unroll
         for (int b = 0; b < B; ++b) {
             const int p = p0 + b * nw;
-            if (p >= t.n) break;                                      // wave-uniform
+            if (p >= hi) break;                                       // wave-uniform
             double a = acc[b];
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, kWave);
@@ -300,10 +312,10 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
             const ArgMin c{s_v[w], s_i[w]};
             if (argmin_better(c, best)) best = c;
         }
-        s_best = best.i < 0 ? 0 : best.i;
+        s_best = best.i < 0 ? lo : best.i;
         if (writer) {
-            *t.best_idx = s_best;
-            if (t.best_val) *t.best_val = best.v;
+            t.best_idx[slot] = s_best;
+            if (t.best_val) t.best_val[slot] = best.v;
         }
     }
     __syncthreads();
@@ -312,7 +324,14 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
 
 __global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t)
 {
-    (void)finalize_select_body(t, true);
+    (void)finalize_select_body(t, true, 0, t.n, 0);
+}
+
+// segmented: block m finishes and selects over particles [m k, (m + 1) k)
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select_seg(Tail t, int k)
+{
+    const int m = blockIdx.x;
+    (void)finalize_select_body(t, true, m * k, (m + 1) * k, m);
 }
 
 // the same + ONE copy of the winner (the single-state search step: dpsx_search_step_one_f32): every block of the copy
@@ -321,15 +340,42 @@ __global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t)
 __global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(Tail t, const float *__restrict__ src,
                                                                       float *__restrict__ dst, int64_t chw4)
 {
-    const int64_t b = finalize_select_body(t, blockIdx.x == 0);
+    const int64_t b = finalize_select_body(t, blockIdx.x == 0, 0, t.n, 0);
     const int64_t i = (int64_t)blockIdx.x * kSelThreads + threadIdx.x;
     if (i < chw4) reinterpret_cast<float4 *>(dst)[i] = (reinterpret_cast<const float4 *>(src) + b * chw4)[i];
+}
+
+// segmented: block (x, m) finishes segment m's costs and select and copies slice x of its winner to dst[m]
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy_seg(Tail t, int k, const float *__restrict__ src,
+                                                                          float *__restrict__ dst, int64_t chw4)
+{
+    const int m = blockIdx.y;
+    const int64_t b = finalize_select_body(t, blockIdx.x == 0, m * k, (m + 1) * k, m);
+    const int64_t i = (int64_t)blockIdx.x * kSelThreads + threadIdx.x;
+    if (i < chw4)
+        (reinterpret_cast<float4 *>(dst) + (int64_t)m * chw4)[i] = (reinterpret_cast<const float4 *>(src) + b * chw4)[i];
 }
 
 int finalize_select(const Tail &t, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
     k_finalize_select<<<1, kSelThreads, 0, s>>>(t);
+    return check_launch();
+}
+
+int finalize_select_seg(const Tail &t, int segments, hipStream_t s)
+{
+    if (t.n == 0) return DPSX_OK;
+    k_finalize_select_seg<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments);
+    return check_launch();
+}
+
+int finalize_select_copy_seg(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s)
+{
+    if (t.n == 0) return DPSX_OK;
+    const int64_t chw4 = chw / 4;
+    const dim3 grid((unsigned)((chw4 + kSelThreads - 1) / kSelThreads), (unsigned)segments);
+    k_finalize_select_copy_seg<<<grid, kSelThreads, 0, s>>>(t, t.n / segments, src, dst, chw4);
     return check_launch();
 }
 
@@ -477,8 +523,9 @@ __global__ __launch_bounds__(kThreads) void k_mask_step_fwd(StepFwdArgs a, const
             vv = *reinterpret_cast<const float4 *>(a.model_out + e + chw);
             zv = *reinterpret_cast<const float4 *>(a.noise + o);
         }
-        const float4 mv = *reinterpret_cast<const float4 *>(mask + mask_index(i, chw, hw));
-        const float4 yv = *reinterpret_cast<const float4 *>(a.y + (a.y_n == 1 ? 0 : p) * chw + i);
+        const float4 mv = *reinterpret_cast<const float4 *>(mask + (int64_t)meas_row((unsigned)p, a.mask_div) * hw +
+                                                            mask_index(i, chw, hw));
+        const float4 yv = *reinterpret_cast<const float4 *>(a.y + (int64_t)meas_row((unsigned)p, a.y_div) * chw + i);
         bool b0, b1, b2, b3;
         float4 x0, sm;
         x0.x = post_x0(xv.x, ev.x, a.k, b0);
@@ -525,8 +572,9 @@ __global__ __launch_bounds__(kThreads) void k_mask_step_bwd(StepBwdArgs a, const
     const int64_t o = p * chw + i;
     const float coef = norm_coef(a.norm ? a.norm[p] : s_nrm[0], a.scale, a.power);  // cotangent on A x0 is coef * r
     const float4 x0 = *reinterpret_cast<const float4 *>(a.x0_hat + o);
-    const float4 mv = *reinterpret_cast<const float4 *>(mask + mask_index(i, chw, hw));
-    const float4 yv = *reinterpret_cast<const float4 *>(a.y + (a.y_n == 1 ? 0 : p) * chw + i);
+    const float4 mv = *reinterpret_cast<const float4 *>(mask + (int64_t)meas_row((unsigned)p, a.mask_div) * hw +
+                                                        mask_index(i, chw, hw));
+    const float4 yv = *reinterpret_cast<const float4 *>(a.y + (int64_t)meas_row((unsigned)p, a.y_div) * chw + i);
     const uchar4 in = *reinterpret_cast<const uchar4 *>(a.inside + o);
     float4 g;
     // A^T = multiply by mask again; then clamp gate; then d/d eps = -b
@@ -551,8 +599,9 @@ int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s)
 // (value, index) pairs are reduced with a total order -- NaN before everything, then the smaller value, then the
 // smaller index -- by wave shuffles and one LDS hop, so the result does not depend on the reduction shape.
 // (ArgMin / argmin_better: common.h, shared with the in-launch tail)
-__global__ __launch_bounds__(kThreads) void k_argmin(const float *__restrict__ v, int64_t n, int64_t *__restrict__ out,
-                                                     float *__restrict__ val_out)
+// (the block's body; `base` is added to the stored index: the segmented form stores global indices)
+__device__ __forceinline__ void argmin_block(const float *__restrict__ v, int64_t n, int64_t *__restrict__ out,
+                                             float *__restrict__ val_out, int64_t base)
 {
     __shared__ float s_val[kThreads / kWave];
     __shared__ int64_t s_idx[kThreads / kWave];
@@ -576,14 +625,34 @@ __global__ __launch_bounds__(kThreads) void k_argmin(const float *__restrict__ v
             const ArgMin c{s_val[w], s_idx[w]};
             if (argmin_better(c, best)) best = c;
         }
-        *out = best.i < 0 ? 0 : best.i;
+        *out = base + (best.i < 0 ? 0 : best.i);
         if (val_out) *val_out = best.v;
     }
+}
+
+__global__ __launch_bounds__(kThreads) void k_argmin(const float *__restrict__ v, int64_t n, int64_t *__restrict__ out,
+                                                     float *__restrict__ val_out)
+{
+    argmin_block(v, n, out, val_out, 0);
 }
 
 int argmin_f32(const float *v, int64_t n, int64_t *idx, float *val, hipStream_t s)
 {
     k_argmin<<<1, kThreads, 0, s>>>(v, n, idx, val);
+    return check_launch();
+}
+
+// one block per segment: block m runs k_argmin over v[m k .. (m + 1) k) and stores the global index
+__global__ __launch_bounds__(kThreads) void k_argmin_seg(const float *__restrict__ v, int64_t k, int64_t *__restrict__ out,
+                                                         float *__restrict__ val_out)
+{
+    const int64_t m = blockIdx.x;
+    argmin_block(v + m * k, k, out + m, val_out ? val_out + m : nullptr, m * k);
+}
+
+int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s)
+{
+    k_argmin_seg<<<(unsigned)segments, kThreads, 0, s>>>(v, k, idx, val);
     return check_launch();
 }
 
@@ -747,6 +816,49 @@ int select_champion(const float *table, int world, int64_t chw, float *dst, int6
     const int64_t chw4 = chw / 4;
     const dim3 grid((unsigned)((chw4 + kThreads - 1) / kThreads), (unsigned)((n_out + kRepl - 1) / kRepl));
     k_select_champion<<<grid, kThreads, 0, s>>>(table, world, chw4, dst, n_out, win_rank, win_local);
+    return check_launch();
+}
+
+// dst[p] = src[ids[p / per]]: each segment's winner replicated over its own particles (k_replicate per segment)
+__global__ __launch_bounds__(kThreads) void k_replicate_seg(const float *__restrict__ src, const int64_t *__restrict__ ids,
+                                                            float *__restrict__ dst, int64_t n_out, unsigned per,
+                                                            int64_t n_src, int64_t chw4)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= chw4) return;
+    const int64_t p0 = (int64_t)blockIdx.y * kRepl;
+    float4 *d4 = reinterpret_cast<float4 *>(dst) + p0 * chw4 + i;
+    const float q = __builtin_nanf("");
+#pragma unroll
+    for (int k = 0; k < kRepl; ++k) {
+        if (p0 + k >= n_out) break;
+        const int64_t sidx = ids[(unsigned)(p0 + k) / per];
+        d4[(int64_t)k * chw4] = (sidx < 0 || sidx >= n_src) ? make_float4(q, q, q, q)
+                                                             : (reinterpret_cast<const float4 *>(src) + sidx * chw4)[i];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_replicate_seg_scalar(const float *__restrict__ src,
+                                                                   const int64_t *__restrict__ ids, float *__restrict__ dst,
+                                                                   unsigned per, int64_t n_src, int64_t chw)
+{
+    const int64_t p = blockIdx.y;
+    const int64_t sidx = ids[(unsigned)p / per];
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= chw) return;
+    dst[p * chw + i] = (sidx < 0 || sidx >= n_src) ? __builtin_nanf("") : src[sidx * chw + i];
+}
+
+int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t per, int64_t n_src,
+                      int64_t chw, hipStream_t s)
+{
+    if (n_out == 0 || chw == 0) return DPSX_OK;
+    if (chw % 4 == 0 && aligned16(src) && aligned16(dst)) {
+        const dim3 grid((unsigned)((chw / 4 + kThreads - 1) / kThreads), (unsigned)((n_out + kRepl - 1) / kRepl));
+        k_replicate_seg<<<grid, kThreads, 0, s>>>(src, ids, dst, n_out, (unsigned)per, n_src, chw / 4);
+    } else {
+        k_replicate_seg_scalar<<<grid_for(chw, n_out), kThreads, 0, s>>>(src, ids, dst, (unsigned)per, n_src, chw);
+    }
     return check_launch();
 }
 

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(PT) void k_phase_pre(const float *__restrict__ x, f
 template <int MODE>
 __global__ __launch_bounds__(PT) void k_phase_post(float2 *__restrict__ z, float *__restrict__ amp,
                                                    float2 *__restrict__ spec, const float *__restrict__ yu,
-                                                   int y_n, int c, float *__restrict__ partials, int s)
+                                                   unsigned y_div, int c, float *__restrict__ partials, int s)
 {
     __shared__ float scratch[PT / kWave];
     const int64_t plane = blockIdx.y;
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(PT) void k_phase_post(float2 *__restrict__ z, float
             if (spec) spec[plane * ss + cidx] = zz;
         } else {
             const int n = (int)(plane / c), ch = (int)(plane % c);
-            const int64_t yo = ((int64_t)(y_n == 1 ? 0 : n) * c + ch) * ss + cidx;
+            const int64_t yo = ((int64_t)meas_row((unsigned)n, y_div) * c + ch) * ss + cidx;
             float g;
             if (MODE == 1) {
                 g = yu[yo] - mag;
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(PT) void k_phase_pre_real(const float *__restrict__
 // z: [planes][s][s/2 + 1] from the R2C transform.  For k = (ky, kx <= s/2) and its mirror m = (-ky, -kx):
 // r(k) = y[shift k] - |z[k]|/s, r(m) = y[shift m] - |z[k]|/s; sums of squares over the FULL spectrum (the mirror
 // counts here unless it lies in the half itself, kx in {0, s/2}); z[k] <- (r(k) + r(m)) / 2 * z[k] / |z[k]|.
-__global__ __launch_bounds__(PT) void k_phase_post_half(float2 *__restrict__ z, const float *__restrict__ y, int y_n,
+__global__ __launch_bounds__(PT) void k_phase_post_half(float2 *__restrict__ z, const float *__restrict__ y, unsigned y_div,
                                                         int c, float *__restrict__ partials, int s)
 {
     __shared__ float scratch[PT / kWave];
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(PT) void k_phase_post_half(float2 *__restrict__ z, 
     const int64_t hh = (int64_t)s * hs, ss = (int64_t)s * s;
     const float inv = 1.0f / (float)s;
     const int n = (int)(plane / c), ch = (int)(plane % c);
-    const float *yp = y + ((int64_t)(y_n == 1 ? 0 : n) * c + ch) * ss;
+    const float *yp = y + ((int64_t)meas_row((unsigned)n, y_div) * c + ch) * ss;
     float acc = 0.0f;
     const int base = blockIdx.x * kChunk;
     for (int t = threadIdx.x; t < kChunk; t += PT) {
@@ -420,13 +420,13 @@ int phase_step_fwd(dpsx_op *op, const StepFwdArgs &f, float *resid_c, hipStream_
         const unsigned tiles = (prfft::HS + prfft::CT - 1) / prfft::CT;
         if (phase_v1()) {
             const size_t lds = (size_t)(prfft::N + prfft::N * prfft::CT) * sizeof(float2);
-            prfft::k_pr_cols<<<dim3(tiles, (unsigned)planes), prfft::BT, lds, s>>>(hbuf, f.y, (int)f.y_n, (int)c, f.partials, tw);
+            prfft::k_pr_cols<<<dim3(tiles, (unsigned)planes), prfft::BT, lds, s>>>(hbuf, f.y, f.y_div, (int)c, f.partials, tw);
             return check_launch();
         }
         const size_t lds = (size_t)prfft::B2LDS * sizeof(float2);
         const unsigned nyq_blocks = (unsigned)((planes + prfft::CT - 1) / prfft::CT);
         const unsigned grid = nyq_blocks + (unsigned)planes * (prfft::HS / prfft::CT);
-        prfft::k_pr_cols2<<<grid, prfft::B2T, lds, s>>>(hbuf, f.y, (int)f.y_n, (int)c, f.partials, tw, (int)planes,
+        prfft::k_pr_cols2<<<grid, prfft::B2T, lds, s>>>(hbuf, f.y, f.y_div, (int)c, f.partials, tw, (int)planes,
                                                         (int)nyq_blocks);
         return check_launch();
     }
@@ -442,14 +442,13 @@ int phase_step_fwd(dpsx_op *op, const StepFwdArgs &f, float *resid_c, hipStream_
     }
     if (rc != DPSX_OK) return rc;
     const float *y = f.y;
-    const int64_t y_n = f.y_n;
     float *partials = f.partials;
     hipfftHandle plan;
     if ((rc = get_plan(op, planes, &plan, 1)) != DPSX_OK) return rc;
     if (hipfftSetStream(plan, s) != HIPFFT_SUCCESS) return DPSX_ELAUNCH;
     if (hipfftExecR2C(plan, real, reinterpret_cast<hipfftComplex *>(half)) != HIPFFT_SUCCESS) return DPSX_ELAUNCH;
     const unsigned chunks = (unsigned)((sz * (sz / 2 + 1) + kChunk - 1) / kChunk);
-    k_phase_post_half<<<dim3(chunks, (unsigned)planes), PT, 0, s>>>(half, y, (int)y_n, (int)c, partials, sz);
+    k_phase_post_half<<<dim3(chunks, (unsigned)planes), PT, 0, s>>>(half, y, f.y_div, (int)c, partials, sz);
     return check_launch();
 }
 

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256) void k_pr_rows_fwd(const float *__restrict__ x
 // ---- pass B: one (plane, 16-column tile) per block
 constexpr int BT = 512, TPC = BT / CT;      // threads of pass B, threads per column
 
-__global__ __launch_bounds__(BT) void k_pr_cols(float2 *__restrict__ half, const float *__restrict__ y, int y_n, int c,
+__global__ __launch_bounds__(BT) void k_pr_cols(float2 *__restrict__ half, const float *__restrict__ y, unsigned y_div, int c,
                                                  float *__restrict__ partials, const float2 *__restrict__ tw_g)
 {
     extern __shared__ __align__(16) float2 s_dyn[];
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(BT) void k_pr_cols(float2 *__restrict__ half, const
     fft_fwd<CT>(s_d + cl, s_tw, g, TPC);
     // pointwise on digit-reversed positions
     const int n = (int)(plane / c), ch = (int)(plane % c);
-    const float *yp = y + ((int64_t)(y_n == 1 ? 0 : n) * c + ch) * N * N;
+    const float *yp = y + ((int64_t)dpsx::meas_row((unsigned)n, y_div) * c + ch) * N * N;
     const float inv = 1.0f / (float)N;
     float acc = 0.0f;
     if (colok) {
@@ -415,7 +415,7 @@ __device__ __forceinline__ int b2_idx2(int be, int bo, int k) { return ((k & 1) 
 // work wasted); instead the first ceil(planes / 16) workgroups of the grid each take the Nyquist column of SIXTEEN planes
 // (lane cl <-> plane 16 b + cl), and the other 12 x planes workgroups a 16-column tile of one plane: 2,316 workgroups, three
 // generations.  Per-lane plane: the base pointers are per-lane values in both forms.
-__global__ __launch_bounds__(B2T, 3) void k_pr_cols2(float2 *__restrict__ half, const float *__restrict__ y, int y_n, int c,
+__global__ __launch_bounds__(B2T, 3) void k_pr_cols2(float2 *__restrict__ half, const float *__restrict__ y, unsigned y_div, int c,
                                                       float *__restrict__ partials, const float2 *__restrict__ tw_g,
                                                       int planes, int nyq_blocks)
 {
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(B2T, 3) void k_pr_cols2(float2 *__restrict__ half, 
         for (int q = 0; q < 16; ++q) st(s_d + b2_idx1(j, q, cl), x[q]);
     }
     const int n = (int)(plane / c), ch = (int)(plane % c);
-    const float *yp = y + ((int64_t)(y_n == 1 ? 0 : n) * c + ch) * N * N;       // (per lane in a Nyquist workgroup)
+    const float *yp = y + ((int64_t)dpsx::meas_row((unsigned)n, y_div) * c + ch) * N * N;       // (per lane in a Nyquist workgroup)
     // the measurement values of this lane's 24 frequencies and of their mirrors (an L2-resident table: 1.8 MB for a broadcast
     // measurement): issued ahead of the barrier, so that their latency runs under the wait and the forward DFT24
     float y1[24], y2[24];

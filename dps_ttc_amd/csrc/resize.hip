@@ -66,7 +66,7 @@ struct ResizeArgs {
     float *x0_hat, *sample;
     uint8_t *inside_w;
     const float *y;
-    int y_n;
+    unsigned y_div;       // row_div(y_n, n): particle q reads measurement row meas_row(q, y_div)
     float *partials;
     const float *norm_in, *norm_partials;
     int norm_parts;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(RT) void k_resize_fwd(ResizeArgs a, ResizeDev d)
             acc = fmaf(s_wh[k * d.tp + pl], s_tmp[s_ih[k * d.tp + pl] * d.out_w + o], acc);
         const int64_t oo = (int64_t)p * d.out_w + o;
         if constexpr (RESID) {
-            const float yv = a.y[((int64_t)(a.y_n == 1 ? 0 : n) * a.c + ch) * ohw + oo];
+            const float yv = a.y[((int64_t)meas_row((unsigned)n, a.y_div) * a.c + ch) * ohw + oo];
             const float r = yv - acc;
             if (a.out) a.out[(int64_t)plane * ohw + oo] = r;
             if constexpr (POST) return fmaf(r, r, run);
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(RT, 3) void k_resize_fwd_rows(ResizeArgs a, ResizeD
             acc = fmaf(s_wh[k * d.tp + pl], s_tmp[s_ih[k * d.tp + pl] * d.out_w + o], acc);
         const unsigned oo = (unsigned)(p * d.out_w + o);
         if constexpr (RESID) {
-            const float yv = a.y[((int64_t)(a.y_n == 1 ? 0 : n) * a.c + ch) * ohw + oo];
+            const float yv = a.y[((int64_t)meas_row((unsigned)n, a.y_div) * a.c + ch) * ohw + oo];
             const float r = yv - acc;
             if (a.out) a.out[(int64_t)plane * ohw + oo] = r;
             if constexpr (POST) return fmaf(r, r, run);
@@ -979,7 +979,7 @@ int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     if (f.n == 0) return DPSX_OK;
     ResizeArgs a{};
     a.x_t = f.x_t; a.model_out = f.model_out; a.noise = f.noise; a.x0_hat = f.x0_hat; a.sample = f.sample;
-    a.inside_w = f.inside; a.y = f.y; a.y_n = (int)f.y_n; a.out = f.resid; a.partials = f.partials;
+    a.inside_w = f.inside; a.y = f.y; a.y_div = f.y_div; a.out = f.resid; a.partials = f.partials;
     a.c = (int)f.c; a.planes = (int)(f.n * f.c); a.k = f.k;
     a.tail = f.tail;
     a.tail.blocks_per_particle = (int)resize_fwd_blocks_per_particle(op, f.c, f.n * f.c);
@@ -1004,7 +1004,7 @@ int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n,
 {
     if (n == 0) return DPSX_OK;
     ResizeArgs a{};
-    a.x = x; a.y = y; a.y_n = (int)y_n; a.out = nullptr; a.partials = partials; a.c = (int)c;
+    a.x = x; a.y = y; a.y_div = row_div(y_n, n); a.out = nullptr; a.partials = partials; a.c = (int)c;
     a.planes = (int)(n * c);
     a.l1 = l1;
     a.tail = tail;

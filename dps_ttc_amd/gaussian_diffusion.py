@@ -292,15 +292,42 @@ class GaussianDiffusion:
         x_next = kernels.step_update(buf, g_unet, coefs)
         return x_next, buf.norm
 
-    def _particle_group_set(self, method, cond_kw, x):
-        """the sampler's kernels.ParticleGroups for this operator / batch shape (built once, reused across trajectories)"""
+    def _particle_group_set(self, method, cond_kw, x, images=None):
+        """the sampler's kernels.ParticleGroups for this operator / batch shape (built once, reused across trajectories);
+        images=M: a multi-image batch, the groups hold whole images"""
         n, c, h, w = x.shape
         op, mask = method.operator, cond_kw.get('mask', None)
         key = (id(op), None if mask is None else (mask.data_ptr(), mask._version), (n, c, h, w), str(x.device),
-               int(self.particle_groups))
+               int(self.particle_groups), images)
         if self._pgroups is None or self._pgroups[0] != key:
-            self._pgroups = (key, kernels.ParticleGroups(op, n, c, h, w, x.device, self.particle_groups, mask=mask, like=x))
+            self._pgroups = (key, kernels.ParticleGroups(op, n, c, h, w, x.device, self.particle_groups, mask=mask, like=x,
+                                                         images=images))
         return self._pgroups[1]
+
+    @staticmethod
+    def _measurement_images(measurement, n):
+        """M when `measurement` holds one row per image of a multi-image batch (1 < M < N, particles [m K, (m + 1) K)
+        belong to image m), None for one broadcast measurement or one per particle"""
+        y_n = measurement.shape[0] if torch.is_tensor(measurement) and measurement.dim() > 0 else 1
+        if y_n in (1, n):
+            return None
+        if y_n < 1 or n % y_n:
+            raise ValueError(f"a measurement of {y_n} rows does not split {n} particles into whole images")
+        return y_n
+
+    def _check_multi_image(self, plan, method, projecting, images, n):
+        """a multi-image batch runs the fused ps / ps_anneal / ps_semantic-without-embedder step only"""
+        name = type(method).__name__ if method is not None else "this conditioning function"
+        if plan is None or projecting:
+            raise NotImplementedError(
+                f"multi-image batch ({images} measurements for {n} particles): {name} runs the per-op path, which takes "
+                "one measurement or one per particle; only the fused ps / ps_anneal / ps_semantic (no embedder) step "
+                "and DiffStateGrad off support one measurement per image")
+        last = self.num_timesteps - 1
+        if "semantic" in plan[0].fused_spec(beta_scale=self.betas[last], t=last / self.num_timesteps, **plan[1]):
+            raise NotImplementedError(
+                f"multi-image batch ({images} images): semantic guidance has one target for all particles; per-image "
+                "targets are not supported (set sem_guid_scale = 0 or run one image per call)")
 
     def dps_step_grouped(self, model, img, idx, measurement, method, cond_kw, pg, noise, loop_kw=None, want_x0=False):
         """dps_step over kernels.ParticleGroups: every group's whole step -- model call, K1, [semantic term], K2, model VJP,
@@ -355,9 +382,12 @@ class GaussianDiffusion:
         # itself, so it takes the per-op path; every other step keeps the fused launches
         period, project = kwargs.get('period', 20), kwargs.get('project', False)
         # particle groups on streams (sampler.particle_groups > 1): only where every step is a fused step
+        images = self._measurement_images(measurement, img.shape[0])
+        if images is not None:
+            self._check_multi_image(plan, method, project and returns_gradient, images, img.shape[0])
         pg = None
         if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
-            pg = self._particle_group_set(plan[0], plan[1], img)
+            pg = self._particle_group_set(plan[0], plan[1], img, images=images)
         for idx in steps:
             projecting = project and returns_gradient and period != 0 and idx % period == 0
             if plan is not None and not projecting:
@@ -545,7 +575,7 @@ class SearchDDPM(DDPM):
     #: noise draws, costs and winner indices are the same); False keeps N copies as the reference does.
     single_state = True
 
-    def search_step(self, model, img, idx, measurement, handle, noise=None):
+    def search_step(self, model, img, idx, measurement, handle, noise=None, segments=None):
         with torch.no_grad():
             model_out = self._call_model(model, img, idx)
         if noise is None:
@@ -553,21 +583,23 @@ class SearchDDPM(DDPM):
         # S1 -> scoring launch -> costs + select -> the winner's replication: one library call, nothing leaves the device
         local = self.global_select is None
         x_next, sample, costs, best, _ = handle.search_step(img, model_out, noise, measurement, self.step_coefs[idx],
-                                                            replicate=local)
+                                                            replicate=local, segments=segments)
         self.last_best = best
         if not local:
             return self.global_select(costs, sample), costs
         return x_next, costs
 
-    def search_step_one(self, model, state, n, idx, measurement, handle, noise=None):
-        """One step from the single state particle `state` [1,C,H,W] -> (winner [1,C,H,W], costs [n])."""
+    def search_step_one(self, model, state, n, idx, measurement, handle, noise=None, segments=None):
+        """One step from the single state particle `state` [1,C,H,W] -> (winner [1,C,H,W], costs [n]).
+        segments=M: one state per image, [M,C,H,W] -> (winners [M,C,H,W], costs [n])."""
         with torch.no_grad():
             model_out = self._call_model(model, state, idx)
         if noise is None:
             noise = self._randn(state, shape=(n,) + tuple(state.shape[1:]))
         local = self.global_select is None
         winner, sample, costs, best, _ = handle.search_step_one(state, model_out, noise, measurement,
-                                                                self.step_coefs[idx], want_winner=local)
+                                                                self.step_coefs[idx], want_winner=local,
+                                                                segments=segments)
         self.last_best = best
         if not local:
             winner = self.global_select(costs, sample, n_out=1)
@@ -583,18 +615,34 @@ class SearchDDPM(DDPM):
         handle = operator.hip_handle_for(mask) if operator.name == 'inpainting' else operator.hip_handle(img)
         self.best_paths, self.best_costs = [], []
         n = img.shape[0]
-        state = None                      # the single state particle, once a select has made all particles equal
+        # n_images=M: M images x n / M particles (image-major), measurement [1 or M, ...]: every select is per image
+        # (last_best: [M] global particle indices) and the state is one particle per image
+        segments = kwargs.get('n_images', None)
+        if segments is not None:
+            segments = int(segments)
+            y_n = measurement.shape[0]
+            if segments < 1 or n % segments or y_n not in (1, segments):
+                raise ValueError(f"n_images={segments}: {n} particles and a measurement of {y_n} rows do not form "
+                                 f"{segments} images")
+            if segments > 1 and self.global_select is not None:
+                raise NotImplementedError("n_images > 1 with a global (multi-rank) select is not supported: the champion "
+                                          "exchange picks one winner for all particles")
+        elif self._measurement_images(measurement, n) is not None:
+            raise ValueError(f"a measurement of {measurement.shape[0]} rows for {n} particles: pass n_images= for a "
+                             "multi-image batch")
+        per = n // (segments or 1)
+        state = None                      # the single state particle(s), once a select has made all particles equal
         for idx in range(self.num_timesteps - 1, -1, -1):
             if state is None:
-                img, costs = self.search_step(model, img, idx, measurement, handle)
-                if self.single_state and n > 1:
-                    state = img[:1]
+                img, costs = self.search_step(model, img, idx, measurement, handle, segments=segments)
+                if self.single_state and per > 1:
+                    state = img[::per] if segments is not None else img[:1]
             else:
-                state, costs = self.search_step_one(model, state, n, idx, measurement, handle)
+                state, costs = self.search_step_one(model, state, n, idx, measurement, handle, segments=segments)
             if kwargs.get('trace', False):
                 self.best_costs.append(costs)
         if state is not None:             # the reference returns N copies of the final winner
-            return state.repeat(n, 1, 1, 1)
+            return state.repeat_interleave(per, dim=0) if segments is not None else state.repeat(n, 1, 1, 1)
         return img.clone()
 
     @torch.no_grad()
@@ -608,6 +656,9 @@ class SearchDDPM(DDPM):
         if potential_type not in ('mean', 'min', 'diff', 'curr'):
             raise NotImplementedError
         n = denoised_candidates.shape[0]
+        if (kwargs.get('n_images', None) or 1) > 1 or self._measurement_images(measurement, n) is not None:
+            raise NotImplementedError("resample_update over a multi-image batch is not supported: the multinomial draw "
+                                      "would mix particles of different images (it needs a per-image RNG stream policy)")
         if resample and prev_costs is not None:
             pot = torch.exp(-rs_temp * prev_costs / steps_done) if potential_type == 'mean' \
                 else torch.exp(-rs_temp * prev_costs)
@@ -643,6 +694,9 @@ class TTC_DDIM(DDIM):
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
         kernels.require_cuda(img, "x_start")
+        if (kwargs.get('n_images', None) or 1) > 1 or self._measurement_images(measurement, img.shape[0]) is not None:
+            raise NotImplementedError("ttc_ddim over a multi-image batch is not supported: its resampling would mix "
+                                      "particles of different images (it needs a per-image RNG stream policy)")
         resample_every_steps, resample_scale = 10, 100
         distance = None
         self.last_resample_ids = None

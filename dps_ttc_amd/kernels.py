@@ -115,13 +115,21 @@ class OpHandle:
 
     @classmethod
     def mask(cls, mask, device):
+        """mask [1,1,H,W] (broadcast over the particles) or [M,1,H,W], one per image of a multi-image batch: particle p
+        of N uses mask p / (N / M)"""
         m = f32c(mask.to(device), "mask")
         hh, ww = m.shape[-2:]
-        if m.numel() != hh * ww:
-            raise ValueError("mask must be [1,1,H,W]")
+        mask_n = m.shape[0] if m.dim() == 4 else 1
+        if m.numel() != mask_n * hh * ww:
+            raise ValueError("mask must be [1,1,H,W] or [M,1,H,W]")
         h = c_void_p()
-        check(lib().dpsx_op_create_mask(ptr(m), hh, ww, byref(h)), "dpsx_op_create_mask")
-        return cls(h, device, keep=(m,))
+        if mask_n == 1:
+            check(lib().dpsx_op_create_mask(ptr(m), hh, ww, byref(h)), "dpsx_op_create_mask")
+        else:
+            check(lib().dpsx_op_create_mask_n(ptr(m), mask_n, hh, ww, byref(h)), "dpsx_op_create_mask_n")
+        obj = cls(h, device, keep=(m,))
+        obj.mask_n = mask_n
+        return obj
 
     @classmethod
     def identity(cls, device):
@@ -209,10 +217,13 @@ class OpHandle:
                                           n, c, h, w, ptr(ws), ws.numel(), stream_of(x)), "dpsx_score_argmin_f32")
         return costs, best, val
 
-    def search_step(self, x_t, model_out, noise, y, coefs, replicate=True):
+    def search_step(self, x_t, model_out, noise, y, coefs, replicate=True, segments=None):
         """One search_ddpm step (gaussian_diffusion.py:618-633): S1, costs of the proposals, select and -- with
         replicate=True -- the winner copied over all particles.  -> (x_next or None, sample, costs, best, costs[best]);
-        one library call, nothing leaves the device."""
+        one library call, nothing leaves the device.
+        segments=M: a multi-image batch of M images x N / M particles (image-major), y [1 or M, ...]: the select runs per
+        image, best / costs[best] are [M] (global particle indices) and each image's winner is replicated over its own
+        particles."""
         x_t, model_out, y = _nchw(f32c(x_t, "x_t")), f32c(model_out, "model_out"), f32c(y, "measurement")
         noise = None if noise is None else f32c(noise, "noise")
         n, c, h, w = x_t.shape
@@ -223,29 +234,50 @@ class OpHandle:
         sample = torch.empty_like(x_t)
         x_next = torch.empty_like(x_t) if replicate else None
         costs = torch.empty(n, dtype=torch.float32, device=x_t.device)
+        ws = self.workspace(n, c, h, w, x_t.device)
+        if segments is not None:
+            best = torch.empty(int(segments), dtype=torch.int64, device=x_t.device)
+            val = torch.empty(int(segments), dtype=torch.float32, device=x_t.device)
+            check(lib().dpsx_search_step_seg_f32(self._h, ptr(x_t), ptr(model_out), ptr(noise), ptr(y), y.shape[0],
+                                                 ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(x_next), int(segments),
+                                                 n, c, h, w, byref(coefs), ptr(ws), ws.numel(), stream_of(x_t)),
+                  "dpsx_search_step_seg_f32")
+            return x_next, sample, costs, best, val
         best = torch.empty((), dtype=torch.int64, device=x_t.device)
         val = torch.empty(1, dtype=torch.float32, device=x_t.device)
-        ws = self.workspace(n, c, h, w, x_t.device)
         check(lib().dpsx_search_step_f32(self._h, ptr(x_t), ptr(model_out), ptr(noise), ptr(y), y.shape[0], ptr(sample),
                                          ptr(costs), ptr(best), ptr(val), ptr(x_next), n, c, h, w, byref(coefs), ptr(ws),
                                          ws.numel(), stream_of(x_t)), "dpsx_search_step_f32")
         return x_next, sample, costs, best, val
 
-    def search_step_one(self, x_one, model_out_one, noise, y, coefs, want_winner=True):
+    def search_step_one(self, x_one, model_out_one, noise, y, coefs, want_winner=True, segments=None):
         """The same step from ONE state particle (after a select all particles are copies of the winner): x_one
         [1,C,H,W], model_out_one [1,2C,H,W], noise [N,C,H,W] -> (winner [1,C,H,W] or None, sample [N,...], costs,
-        best, costs[best]).  Bit-identical to search_step on N copies of the state; one model evaluation per step."""
+        best, costs[best]).  Bit-identical to search_step on N copies of the state; one model evaluation per step.
+        segments=M: M images, one state each (x_one [M,C,H,W], model_out_one [M,2C,H,W]); proposal p reads state p / (N / M),
+        the select runs per image and winner / best / costs[best] are [M, ...] (best: global particle indices)."""
         x_one, model_out_one, y = _nchw(f32c(x_one, "x_t")), f32c(model_out_one, "model_out"), f32c(y, "measurement")
         noise = _nchw(f32c(noise, "noise"))
         n, c, h, w = noise.shape
         if n == 0:
             raise ValueError("best-of-N over an empty particle set")
-        if x_one.shape != (1, c, h, w) or model_out_one.shape[0] != 1 or model_out_one[0].numel() != 2 * c * h * w:
-            raise ValueError(f"one state particle expected: x {tuple(x_one.shape)}, model_out {tuple(model_out_one.shape)}, "
-                             f"noise {tuple(noise.shape)}")
+        states = 1 if segments is None else int(segments)
+        if x_one.shape != (states, c, h, w) or model_out_one.shape[0] != states or \
+                model_out_one[0].numel() != 2 * c * h * w:
+            raise ValueError(f"{states} state particle(s) expected: x {tuple(x_one.shape)}, "
+                             f"model_out {tuple(model_out_one.shape)}, noise {tuple(noise.shape)}")
         sample = torch.empty_like(noise)
         winner = torch.empty_like(x_one) if want_winner else None
         costs = torch.empty(n, dtype=torch.float32, device=noise.device)
+        if segments is not None:
+            best = torch.empty(states, dtype=torch.int64, device=noise.device)
+            val = torch.empty(states, dtype=torch.float32, device=noise.device)
+            ws = self.workspace(n, c, h, w, noise.device)
+            check(lib().dpsx_search_step_one_seg_f32(self._h, ptr(x_one), ptr(model_out_one), ptr(noise), ptr(y),
+                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(winner),
+                                                     states, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
+                                                     stream_of(noise)), "dpsx_search_step_one_seg_f32")
+            return winner, sample, costs, best, val
         best = torch.empty((), dtype=torch.int64, device=noise.device)
         val = torch.empty(1, dtype=torch.float32, device=noise.device)
         ws = self.workspace(n, c, h, w, noise.device)
@@ -311,7 +343,7 @@ def residual_norm(y, ax, want_residual=True):
     n = ax.shape[0]
     m = ax[0].numel() if n else 0
     y_n = y.shape[0]
-    if y_n not in (1, n) or (n and y[0].numel() != m):
+    if (y_n not in (1, n) and (y_n < 1 or n % y_n)) or (n and y[0].numel() != m):
         raise ValueError(f"measurement {tuple(y.shape)} does not broadcast against {tuple(ax.shape)}")
     r = torch.empty_like(ax) if want_residual else None
     norm = torch.empty(n, dtype=torch.float32, device=ax.device)
@@ -364,6 +396,21 @@ def argmin(v, want_value=False):
     out = torch.empty((), dtype=torch.int64, device=v.device)
     val = torch.empty(1, dtype=torch.float32, device=v.device) if want_value else None
     check(lib().dpsx_argmin_f32(ptr(v), v.numel(), ptr(out), ptr(val), stream_of(v)), "dpsx_argmin_f32")
+    return (out, val) if want_value else out
+
+
+def argmin_seg(v, segments, want_value=False):
+    """v [segments * K] (or [segments, K]) -> [segments] int64 global indices m * K + argmin(v[m]) (torch.argmin order
+    within each segment: first minimum, NaN counts as the minimum), on the device in one launch -- the per-image best-of-N
+    of a multi-image batch.  want_value: also the [segments] minima."""
+    v = f32c(v.reshape(-1), "scores")
+    segments = int(segments)
+    if segments < 1 or v.numel() == 0 or v.numel() % segments:
+        raise ValueError(f"{v.numel()} scores do not split into {segments} non-empty segments")
+    out = torch.empty(segments, dtype=torch.int64, device=v.device)
+    val = torch.empty(segments, dtype=torch.float32, device=v.device) if want_value else None
+    check(lib().dpsx_argmin_seg_f32(ptr(v), segments, v.numel() // segments, ptr(out), ptr(val), stream_of(v)),
+          "dpsx_argmin_seg_f32")
     return (out, val) if want_value else out
 
 
@@ -539,20 +586,34 @@ class ParticleGroups:
     All groups' sample / gate / norm / g_model_out / x_next are contiguous particle slices of ONE full-batch StepBuffers
     (`self.full`): `self.full.norm` is the [N] distance vector and `self.x_next()` the [N, C, H, W] state, no copy."""
 
-    def __init__(self, operator, n, c, h, w, device, groups, mask=None, like=None, record_streams=True):
+    def __init__(self, operator, n, c, h, w, device, groups, mask=None, like=None, record_streams=True, images=None):
         """record_streams=False: the caller keeps every tensor it hands to the launches alive until the groups are joined
         (bench.py's device-resident rings), so the per-launch `record_stream` calls (about 1 us of host time each) are
-        skipped."""
+        skipped.
+        images=M (> 1): a multi-image batch of M images x N / M particles: the groups hold whole images (groups <= M) and
+        each group reads its own images' rows of a [M, ...] measurement (`y_rows`) and of a [M, 1, H, W] mask."""
         device = torch.device(device)
         self.record_streams = bool(record_streams)
-        groups = max(1, min(int(groups), max(n, 1)))
+        self.images = int(images) if images is not None and int(images) > 1 else None
+        if self.images is None:
+            groups = max(1, min(int(groups), max(n, 1)))
+            self.sizes = [n // groups + (1 if j < n % groups else 0) for j in range(groups)]   # may differ by one particle
+            self.rows = None
+        else:
+            M = self.images
+            if n % M:
+                raise ValueError(f"{n} particles do not split into {M} images")
+            groups = max(1, min(int(groups), M))
+            per_img = [M // groups + (1 if j < M % groups else 0) for j in range(groups)]
+            first = [sum(per_img[:j]) for j in range(groups)]
+            self.rows = [slice(f, f + k) for f, k in zip(first, per_img)]          # each group's images
+            self.sizes = [k * (n // M) for k in per_img]
         self.n, self.shape = n, (n, c, h, w)
-        self.sizes = [n // groups + (1 if j < n % groups else 0) for j in range(groups)]   # may differ by one particle
         self.starts = [sum(self.sizes[:j]) for j in range(groups)]
         self.slices = [slice(s, s + m) for s, m in zip(self.starts, self.sizes)]
         self.full = StepBuffers(None, n, c, h, w, device)
         probe = like if like is not None else self.full.sample
-        self.handles = [operator.new_hip_handle(probe, mask=mask) for _ in range(groups)]
+        self.handles = [operator.new_hip_handle(probe, mask=self._group_mask(j, mask)) for j in range(groups)]
         self.bufs = [StepBuffers(hd, m, c, h, w, device, parent=self.full, offset=s)
                      for hd, m, s in zip(self.handles, self.sizes, self.starts)]
         self.streams = [torch.cuda.Stream(device=device) for _ in range(groups)]
@@ -560,6 +621,21 @@ class ParticleGroups:
 
     def __len__(self):
         return len(self.bufs)
+
+    def _group_mask(self, j, mask):
+        if mask is None or self.images is None or mask.shape[0] == 1:
+            return mask
+        if mask.shape[0] != self.images:
+            raise ValueError(f"{mask.shape[0]} masks for {self.images} images")
+        return mask[self.rows[j]]
+
+    def y_rows(self, j, y):
+        """group j's measurement: y itself (one broadcast row, or a single-image batch), else its images' rows"""
+        if self.images is None or y.shape[0] == 1:
+            return y
+        if y.shape[0] != self.images:
+            raise ValueError(f"measurement of {y.shape[0]} rows for {self.images} images")
+        return y[self.rows[j]]
 
     # -- ordering against the caller's stream
     def fork(self, stream=None):
@@ -593,11 +669,11 @@ class ParticleGroups:
     # -- the three launches of group j, on its stream
     def step_fwd(self, j, x_t, model_out, noise, y, coefs, want_x0=True):
         step_fwd(self.handles[j], self.bufs[j], self._slice(j, x_t), self._slice(j, model_out), self._slice(j, noise),
-                 y, coefs, want_x0=want_x0, stream=self.streams[j])
+                 self.y_rows(j, y), coefs, want_x0=want_x0, stream=self.streams[j])
 
     def step_bwd(self, j, y, scale, power, coefs, g_x0_extra=None):
-        step_bwd(self.handles[j], self.bufs[j], y, scale, power, coefs, g_x0_extra=self._slice(j, g_x0_extra),
-                 stream=self.streams[j])
+        step_bwd(self.handles[j], self.bufs[j], self.y_rows(j, y), scale, power, coefs,
+                 g_x0_extra=self._slice(j, g_x0_extra), stream=self.streams[j])
 
     def step_update(self, j, g_unet, coefs):
         return step_update(self.bufs[j], self._slice(j, g_unet), coefs, stream=self.streams[j])

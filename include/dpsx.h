@@ -16,7 +16,10 @@
  *     stream -- kernels.ParticleGroups does exactly that).  Calls that take no op are
  *     re-entrant;
  *   - return value: DPSX_OK or a negative DPSX_E* code; nothing throws/exits;
- *   - `n` = particles, `c` = channels, `h`,`w` = image size, chw = c*h*w.
+ *   - `n` = particles, `c` = channels, `h`,`w` = image size, chw = c*h*w;
+ *   - a measurement `y` is [y_n, ...] with y_n dividing n: particle p reads row p / (n / y_n).  y_n = 1
+ *     broadcasts one measurement, y_n = n gives one per particle, and y_n = M serves a multi-image batch of
+ *     M images x n / M particles in image-major order (particles [m K, (m + 1) K) belong to image m).
  */
 #ifndef DPSX_H
 #define DPSX_H
@@ -103,6 +106,10 @@ int dpsx_op_create_resize(int64_t in_h, int64_t in_w,
 /* InpaintingOperator (measurements.py:151-168): mask_dev is a DEVICE pointer to
  * h*w fp32 ([1,1,h,w], broadcast over n and c); borrowed, must outlive the op. */
 int dpsx_op_create_mask(const float *mask_dev, int64_t h, int64_t w, dpsx_op **out);
+/* The same with one mask per image (sample_condition_batched_data.py:131-190 draws a mask per image):
+ * mask_dev is [mask_n, h, w] and particle p of n uses mask p / (n / mask_n).  Calls with an n that mask_n
+ * does not divide return DPSX_EINVAL. */
+int dpsx_op_create_mask_n(const float *mask_dev, int64_t mask_n, int64_t h, int64_t w, dpsx_op **out);
 
 /* DenoiseOperator (measurements.py:57-73): identity. */
 int dpsx_op_create_identity(dpsx_op **out);
@@ -131,7 +138,7 @@ int dpsx_op_adjoint_f32(dpsx_op *op, const float *u, const float *x, float *g,
                         void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- residual norm (condition_methods.py:37-39, 179-181; gaussian_diffusion.py:627-630)
- * r = y - ax (y has y_n in {1, n} particles); norm[p] = ||r_p||_2.  Deterministic
+ * r = y - ax (y has y_n rows, y_n dividing n); norm[p] = ||r_p||_2.  Deterministic
  * two-pass reduction (no float atomics).  r may be NULL. */
 int dpsx_residual_norm_f32(const float *y, int64_t y_n, const float *ax, float *r, float *norm,
                            int64_t n, int64_t m, void *workspace, int64_t workspace_bytes, void *stream);
@@ -225,6 +232,24 @@ int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_o
                              int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
                              void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Multi-image forms of the two steps above: the n particles are `segments` images of n / segments particles each
+ * (image-major), y_n is 1 or `segments`, and the select runs per image: best_idx_dev / best_val_dev are [segments] and
+ * receive each image's winner as a global particle index (m * K + local), torch.argmin order within the image.
+ *   _seg:     x_next[p] = sample[best[p / K]] (each image's winner replicated over its own particles);
+ *   _one_seg: x_t [segments, c, h, w] and model_out [segments, 2c, h, w] hold one state per image (proposal p reads
+ *             state p / K) and x_next [segments, c, h, w] receives each image's winner once.
+ * With segments = 1 they equal dpsx_search_step_f32 / dpsx_search_step_one_f32 bit for bit. */
+int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                             const float *y, int64_t y_n, float *sample, float *costs,
+                             int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments,
+                             int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                                 const float *y, int64_t y_n, float *sample, float *costs,
+                                 int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments,
+                                 int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
+
 /* SearchDDPM.resample_update's cost update (gaussian_diffusion.py:556-585):
  *   curr[p] = ||y - A(x_p)||_1^2 / (c*h*w)                                         (:557-563)
  *   net[p]  = curr + prev (MEAN) | min(curr, prev) (MIN, NaN propagates as torch.min) | curr - prev (DIFF) | curr (CURR)
@@ -238,6 +263,10 @@ int dpsx_resample_cost_f32(dpsx_op *op, const float *x, const float *y, int64_t 
 /* torch.argmin semantics: first minimum wins, NaN counts as the minimum (gaussian_diffusion.py:631).
  * val_out_dev (optional, may be NULL) receives v[argmin] -- `costs[best_path]` of :632 without a host index. */
 int dpsx_argmin_f32(const float *v, int64_t n, int64_t *idx_out_dev, float *val_out_dev, void *stream);
+/* The same per segment: v is [segments, k]; idx_out_dev[m] = m * k + the torch.argmin of v[m] (a global index),
+ * val_out_dev[m] (nullable) its value -- the per-image best-of-N of a multi-image batch (best_of_n_simple.py:32-40). */
+int dpsx_argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx_out_dev, float *val_out_dev,
+                        void *stream);
 /* dst[p] = src[ids[p]]   (ids: device int64 [n_out]; an id outside [0, n_src) fills dst[p] with NaN) */
 int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst,
                     int64_t n_out, int64_t n_src, int64_t chw, void *stream);

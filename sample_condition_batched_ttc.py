@@ -13,6 +13,9 @@ measurement distance (best_of_n_simple.py semantics, on device).
 
 Differences from the reference script, all fixes of things that crash there: `--l1` exists,
 the sampler returns a tensor for this call signature, LPIPS is logged only if torchmetrics is installed.
+`--images_per_batch M` runs up to M reference images per sampler call, `batch_size` particles each, with one
+measurement (and, for inpainting, one mask) per image: M x batch_size particles in one launch sequence, the select of
+`search_ddpm` and the best-of-N per image.  One rank only; not with `ttc_ddim` or `--embedder`.
 With `torchrun --nproc-per-node G` (the reference shards by hand: run0.sh:12 / run1.sh:13 start one process per GPU
 with its own --path_start_idx) the particle groups are sharded contiguously over the ranks and the best-of-N pick is
 global: RCCL all-gather of the distances, winner broadcast from its owner.  `sampler: search_ddpm` then selects over
@@ -100,13 +103,42 @@ def parse_args(argv=None):
     p.add_argument('--particle_groups', type=int, default=1,
                    help='run the batch_size particles of a fused DPS loop as this many independent sub-batches, each on its '
                         'own HIP stream with its own operator handle (kernels.ParticleGroups; results per particle unchanged)')
+    p.add_argument('--images_per_batch', type=int, default=1,
+                   help='run up to this many reference images per sampler call, batch_size particles each, with one '
+                        'measurement (and inpainting mask) per image; selects and best-of-N stay per image')
     return p.parse_args(argv)
+
+
+def image_batches(picks, m):
+    """the picked reference images in pick order as batches of up to m images (the last one may be smaller)"""
+    m = max(1, int(m))
+    return [picks[i:i + m] for i in range(0, len(picks), m)]
+
+
+def check_images_per_batch(args, sampler_name, world):
+    """--images_per_batch > 1: reject what this mode does not support, before any GPU work (one-line message)"""
+    m = args.images_per_batch
+    if m < 1:
+        raise SystemExit(f"--images_per_batch must be at least 1 (got {m})")
+    if m == 1:
+        return
+    if world > 1:
+        raise SystemExit("--images_per_batch > 1 runs on one rank only: sharding a multi-image batch over "
+                         f"WORLD_SIZE={world} ranks is not supported")
+    if sampler_name == 'ttc_ddim':
+        raise SystemExit("--images_per_batch > 1 is not supported with sampler ttc_ddim: its resampling would mix the "
+                         "particles of different images")
+    if args.embedder is not None:
+        raise SystemExit("--images_per_batch > 1 is not supported with --embedder: semantic guidance has one target "
+                         "for all particles")
 
 
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    if args.images_per_batch != 1:
+        check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1)
@@ -190,6 +222,11 @@ def main(argv=None):
     mask_gen = mask_generator(**measure_config['mask_opt']) if op_name == 'inpainting' else None
     if op_name == 'motion_blur' and rank == 0:
         imsave(os.path.join(out_path, f'kernel_{str(args.kernel_idx).zfill(5)}.png'), clear_color(operator.get_kernel()))
+    if args.images_per_batch > 1:
+        for batch in image_batches(picks, args.images_per_batch):
+            run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn,
+                            mask_gen, groups, diffusion_config['sampler'], out_path)
+        return
 
     # particle groups shard contiguously over the ranks: the rank-major order of the gathered scores is the path order
     g_lo, g_hi = dd.shard_range(groups, rank, world)
@@ -263,6 +300,74 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+
+
+def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn, mask_gen,
+                    groups, sampler_name, out_path):
+    """--images_per_batch: the B = len(batch) images of `batch` as one multi-image batch per particle group --
+    B x batch_size particles, image-major (particles [b K, (b + 1) K) belong to image b), y [B, ...] -- and the
+    per-image best-of-N (one argmin per image over its n_paths distances, on the device)."""
+    from dps_ttc_amd import kernels
+    B, K = len(batch), args.batch_size
+    fnames = [str(i).zfill(5) for i in batch]
+    logger.info(f"Inference for images {', '.join(fnames)} ({B} x {K} particles per call)")
+    refs = torch.stack([dataset[min(i, len(dataset) - 1)] for i in batch]).to(device)
+    C, H, W = refs.shape[1:]
+    masks, ys = [], []
+    with torch.no_grad():
+        for b in range(B):             # per image in pick order: its mask, then its noisy measurement
+            fkw = {}
+            if op_name == 'inpainting':
+                masks.append(mask_gen(refs[b:b + 1])[:, 0, :, :].unsqueeze(dim=0).contiguous())
+                fkw = {'mask': masks[-1]}
+            ys.append(noiser(operator.forward(refs[b:b + 1], **fkw)))
+    y = torch.cat(ys).contiguous()
+    fkw, this_sample_fn = {}, sample_fn
+    if op_name == 'inpainting':
+        mask = torch.cat(masks).contiguous()                     # [B, 1, H, W]: particle p uses mask p // K
+        fkw = {'mask': mask}
+        this_sample_fn = partial(sample_fn, measurement_cond_fn=partial(cond_method.conditioning, mask=mask, l1=args.l1),
+                                 mask=mask)
+    for b, fname in enumerate(fnames):
+        os.makedirs(os.path.join(out_path, 'recon_paths', fname), exist_ok=True)
+        os.makedirs(os.path.join(out_path, 'recon_paths_y', fname), exist_ok=True)
+        imsave(os.path.join(out_path, 'input', fname + '.png'), clear_color(y[b:b + 1]))
+        imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(refs[b:b + 1]))
+
+    distances, finals = [], []
+    for g in range(groups):
+        x_start = torch.randn((B * K, C, H, W), device=device).requires_grad_()
+        sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
+        with torch.no_grad():
+            y_space = operator.forward(sample, **fkw)
+            handle = operator.hip_handle_for(fkw['mask']) if op_name == 'inpainting' else operator.hip_handle(sample)
+            dist_g = handle.score(sample, y)                          # ||y_{p // K} - A(x_p)||_2 per particle
+        distances.append(dist_g)
+        finals.append(sample)
+        for b, fname in enumerate(fnames):
+            for i in range(K):
+                p, path_idx = b * K + i, args.path_start_idx + g * K + i
+                psnr = compute_psnr(refs[b:b + 1], sample[p].unsqueeze(0))
+                logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {float(psnr):.4f} / "
+                            f"distance: {float(dist_g[p]):.4f}")
+                imsave(os.path.join(out_path, 'recon_paths', fname, f'path#{path_idx + 1}.png'),
+                       clear_color(sample[p].unsqueeze(0)))
+                imsave(os.path.join(out_path, 'recon_paths_y', fname, f'path#{path_idx + 1}_y_space.png'),
+                       clear_color(y_space[p].unsqueeze(0)))
+    # best-of-N per image: the [groups, B, K] distances in image-major path order, one segmented argmin, one gather
+    n_paths = groups * K
+    d_img = torch.stack(distances).reshape(groups, B, K).transpose(0, 1).reshape(B * n_paths).contiguous()
+    best = kernels.argmin_seg(d_img, B)                                   # [B]: b * n_paths + path
+    path = best - torch.arange(B, device=best.device) * n_paths
+    src = (path // K) * (B * K) + torch.arange(B, device=best.device) * K + path % K    # index into the groups' concat
+    winners = kernels.gather(torch.cat(finals).detach(), src, validate=False)
+    d_host, path_host = d_img.reshape(B, n_paths).cpu().numpy(), path.cpu().numpy()
+    for b, fname in enumerate(fnames):
+        k = int(path_host[b])
+        logger.info(f"Image {fname}: best-of-{n_paths} = path#{args.path_start_idx + k + 1} | PSNR: "
+                    f"{float(compute_psnr(refs[b:b + 1], winners[b:b + 1])):.4f} | distance: {float(d_host[b, k]):.4f}")
+        imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winners[b:b + 1]))
+        np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), d_host[b])
 
 
 if __name__ == '__main__':

@@ -1,0 +1,368 @@
+"""GPU suite: multi-image batches -- M images x K particles (image-major) with one measurement (and inpainting mask) per
+image run as ONE launch sequence of N = M K particles.  Every result is compared bit for bit (torch.equal) with the same
+particles run image by image with y[m:m+1] / mask[m:m+1]: the single-image launches are what the rest of the suite pins
+against the oracle and the golden fixtures."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from standin import StandInModel, synthetic_motion_kernel
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def K():
+    from dps_ttc_amd import kernels
+    return kernels
+
+
+def _sampler(name, respacing="20"):
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    return create_sampler(sampler=name, steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                          model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                          rescale_timesteps=True, timestep_respacing=respacing)
+
+
+def _operator(name, hw, M, seed=0):
+    """-> (operator, per-image masks [M,1,H,W] or None)"""
+    from dps_ttc_amd.measurements import get_operator
+    if name == "gauss":
+        return get_operator("gaussian_blur", kernel_size=61, intensity=3.0, device=DEV), None
+    if name == "motion":
+        op = get_operator("motion_blur", kernel_size=61, intensity=0.5, device=DEV)
+        op._set_weights(synthetic_motion_kernel(61, 3))
+        return op, None
+    if name in ("sr4", "sr8"):
+        return get_operator("super_resolution", in_shape=(1, 3, hw, hw), scale_factor=int(name[2:]), device=DEV), None
+    if name == "inpaint":
+        masks = (np.random.RandomState(seed).rand(M, 1, hw, hw) < 0.5).astype(np.float32)
+        return get_operator("inpainting", device=DEV), torch.from_numpy(masks).to(DEV)
+    if name == "phase":
+        return get_operator("phase_retrieval", oversample=2.0, device=DEV), None
+    raise KeyError(name)
+
+
+def _handle(op, masks, x):
+    return op.hip_handle_for(masks) if masks is not None else op.hip_handle(x)
+
+
+def _measurements(op, masks, M, hw, gen):
+    ys = []
+    for m in range(M):
+        fkw = {} if masks is None else {"mask": masks[m:m + 1]}
+        ys.append(op.forward(torch.rand(1, 3, hw, hw, device=DEV, generator=gen) * 2 - 1, **fkw).detach())
+    return torch.cat(ys).contiguous()
+
+
+# ----------------------------------------------------------------- the fused step
+@pytest.mark.parametrize("name,hw", [("gauss", 64), ("motion", 64), ("sr4", 64), ("sr8", 64), ("inpaint", 64),
+                                     ("phase", 64), ("phase", 256)])
+@pytest.mark.parametrize("k", [4, 5])
+def test_fused_step_multi_image_equals_per_image(K, name, hw, k):
+    M = 3
+    n = M * k
+    gen = torch.Generator(device=DEV).manual_seed(hw + k)
+    mk = lambda *shape: torch.randn(*shape, device=DEV, generator=gen)
+    op, masks = _operator(name, hw, M)
+    x, mo, z, gu = mk(n, 3, hw, hw), mk(n, 6, hw, hw) * 0.4, mk(n, 3, hw, hw), mk(n, 3, hw, hw) * 1e-2
+    y = _measurements(op, masks, M, hw, gen)
+    ck = _sampler("ddpm", "").step_coefs[400]
+
+    def run(sl, yy, mm):
+        xs, ms, zs, gs = (t[sl].contiguous() for t in (x, mo, z, gu))
+        handle = _handle(op, mm, xs)
+        buf = K.StepBuffers(handle, xs.shape[0], 3, hw, hw, DEV)
+        K.step_fwd(handle, buf, xs, ms, zs, yy, ck)
+        K.step_bwd(handle, buf, yy, 0.3, 1, ck)
+        out = K.step_update(buf, gs, ck)
+        return out.clone(), buf.norm.clone(), buf.sample.clone(), buf.inside.clone(), buf.x0_hat.clone()
+
+    full = run(slice(0, n), y, masks)          # first: the phase operator's plans are sized by the largest batch
+    assert bool(torch.isfinite(full[0]).all()) and bool((full[1] > 0).all())
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        part = run(sl, y[m:m + 1], None if masks is None else masks[m:m + 1])
+        for a, b, what in zip(full, part, ("x_prev", "norm", "sample", "gate", "x0_hat")):
+            assert torch.equal(a[sl], b), f"{name} {hw} K={k}: {what} of image {m}"
+    # the images really differ: a broadcast of row 0 would not reproduce image 1
+    assert not torch.equal(full[1][k:2 * k], run(slice(k, 2 * k), y[:1], None if masks is None else masks[:1])[1])
+
+
+def test_mask_n_must_divide_the_batch(K):
+    from dps_ttc_amd._lib import DpsxError
+    op, masks = _operator("inpaint", 64, 3)
+    h = K.OpHandle.mask(masks, DEV)
+    assert h.mask_n == 3
+    with pytest.raises(DpsxError):
+        h.forward(torch.rand(4, 3, 64, 64, device=DEV))
+    x = torch.rand(6, 3, 64, 64, device=DEV)
+    ax = h.forward(x)
+    assert torch.equal(ax, x * masks.repeat_interleave(2, dim=0))
+
+
+# ----------------------------------------------------------------- per-op paths
+@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint", "phase"])
+def test_per_op_paths_multi_image(K, name):
+    M, k, hw = 3, 4, 64
+    n = M * k
+    gen = torch.Generator(device=DEV).manual_seed(5)
+    op, masks = _operator(name, hw, M)
+    x = torch.rand(n, 3, hw, hw, device=DEV, generator=gen) * 2 - 1
+    y = _measurements(op, masks, M, hw, gen)
+    hfull = _handle(op, masks, x)
+    ax = hfull.forward(x)
+    r, norm = K.residual_norm(y, ax)
+    costs = hfull.score(x, y)
+    c2, best, val = hfull.score_argmin(x, y)
+    costs_img, norm_img, r_img, ax_img = [], [], [], []
+    prev = torch.rand(n, device=DEV, generator=gen)
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        hm = _handle(op, None if masks is None else masks[m:m + 1], x[sl])
+        ax_m = hm.forward(x[sl])
+        ax_img.append(ax_m)
+        r_m, n_m = K.residual_norm(y[m:m + 1], ax_m)
+        r_img.append(r_m)
+        norm_img.append(n_m)
+        costs_img.append(hm.score(x[sl].contiguous(), y[m:m + 1]))
+    assert torch.equal(ax, torch.cat(ax_img)) and torch.equal(r, torch.cat(r_img))
+    assert torch.equal(norm, torch.cat(norm_img)) and torch.equal(costs, torch.cat(costs_img))
+    assert torch.equal(c2, costs) and int(best) == int(torch.argmin(costs)) and float(val) == float(costs[int(best)])
+    curr, net = hfull.resample_cost(x, y, prev, "min")
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        hm = _handle(op, None if masks is None else masks[m:m + 1], x[sl])
+        cm_, nm_ = hm.resample_cost(x[sl].contiguous(), y[m:m + 1], prev[sl].contiguous(), "min")
+        assert torch.equal(curr[sl], cm_) and torch.equal(net[sl], nm_)
+
+
+# ----------------------------------------------------------------- segmented search steps
+@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint"])
+def test_search_steps_segmented(K, name):
+    M, k, hw = 3, 4, 64
+    n = M * k
+    gen = torch.Generator(device=DEV).manual_seed(9)
+    mk = lambda *shape: torch.randn(*shape, device=DEV, generator=gen)
+    op, masks = _operator(name, hw, M)
+    x, mo, z = mk(n, 3, hw, hw), mk(n, 6, hw, hw) * 0.4, mk(n, 3, hw, hw)
+    x1, mo1 = mk(M, 3, hw, hw), mk(M, 6, hw, hw) * 0.4
+    y = _measurements(op, masks, M, hw, gen)
+    ck = _sampler("ddpm", "").step_coefs[400]
+    hfull = _handle(op, masks, x)
+    xn, smp, costs, best, val = hfull.search_step(x, mo, z, y, ck, segments=M)
+    w1, smp1, costs1, best1, val1 = hfull.search_step_one(x1, mo1, z, y, ck, segments=M)
+    assert best.shape == (M,) and w1.shape == (M, 3, hw, hw)
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        hm = _handle(op, None if masks is None else masks[m:m + 1], x[sl])
+        xn_m, smp_m, c_m, b_m, v_m = hm.search_step(x[sl].contiguous(), mo[sl].contiguous(), z[sl].contiguous(),
+                                                     y[m:m + 1], ck)
+        assert torch.equal(costs[sl], c_m) and torch.equal(smp[sl], smp_m)
+        assert int(best[m]) - m * k == int(b_m) and float(val[m]) == float(v_m)
+        assert torch.equal(xn[sl], xn_m)
+        w_m, s1_m, c1_m, b1_m, v1_m = hm.search_step_one(x1[m:m + 1].contiguous(), mo1[m:m + 1].contiguous(),
+                                                         z[sl].contiguous(), y[m:m + 1], ck)
+        assert torch.equal(costs1[sl], c1_m) and torch.equal(smp1[sl], s1_m)
+        assert int(best1[m]) - m * k == int(b1_m) and float(val1[m]) == float(v1_m)
+        assert torch.equal(w1[m:m + 1], w_m)
+
+
+def test_search_steps_one_segment_equal_the_unsegmented_steps(K):
+    n, hw = 8, 64
+    gen = torch.Generator(device=DEV).manual_seed(13)
+    mk = lambda *shape: torch.randn(*shape, device=DEV, generator=gen)
+    op, _ = _operator("gauss", hw, 1)
+    x, mo, z = mk(n, 3, hw, hw), mk(n, 6, hw, hw) * 0.4, mk(n, 3, hw, hw)
+    y = _measurements(op, None, 1, hw, gen)
+    ck = _sampler("ddpm", "").step_coefs[300]
+    h = op.hip_handle(x)
+    a = h.search_step(x, mo, z, y, ck)
+    b = h.search_step(x, mo, z, y, ck, segments=1)
+    for u, v in zip(a, b):
+        assert torch.equal(u.reshape(-1), v.reshape(-1))
+    a = h.search_step_one(x[:1], mo[:1], z, y, ck)
+    b = h.search_step_one(x[:1], mo[:1], z, y, ck, segments=1)
+    for u, v in zip(a, b):
+        assert torch.equal(u.reshape(-1), v.reshape(-1))
+
+
+def test_argmin_seg_tie_and_nan_rules(K):
+    nan = float("nan")
+    v = torch.tensor([3.0, 1.0, 1.0, 2.0,      # tie: the first minimum wins
+                      5.0, nan, 0.0, nan,      # NaN counts as the minimum, the first NaN wins
+                      7.0, 7.0, 7.0, 7.0,      # all equal
+                      -1.0, 4.0, 4.0, -2.0], device=DEV)
+    idx, val = K.argmin_seg(v, 4, want_value=True)
+    ref = [m * 4 + int(torch.argmin(v[m * 4:(m + 1) * 4])) for m in range(4)]
+    assert idx.tolist() == ref == [1, 5, 8, 15]
+    assert val[0] == 1.0 and torch.isnan(val[1]) and val[2] == 7.0 and val[3] == -2.0
+    big = torch.randn(5 * 1000, device=DEV, generator=torch.Generator(device=DEV).manual_seed(3))
+    assert K.argmin_seg(big, 5).tolist() == [m * 1000 + int(torch.argmin(big[m * 1000:(m + 1) * 1000])) for m in range(5)]
+
+
+# ----------------------------------------------------------------- loops
+def _noise_bank(steps, n, hw, seed=21):
+    return torch.randn(steps, n, 3, hw, hw, device=DEV, generator=torch.Generator(device=DEV).manual_seed(seed))
+
+
+def _patch_randn(smp, bank, offset):
+    """the sampler's noise: row `offset + p` of the bank's next step for particle p (single-state draws too)"""
+    it = {"k": 0}
+
+    def rnd(like, stride=None, shape=None):
+        cnt = (tuple(shape) if shape is not None else tuple(like.shape))[0]
+        z = bank[it["k"], offset:offset + cnt].contiguous()
+        it["k"] += 1
+        return z
+    smp._randn = rnd
+
+
+@pytest.mark.parametrize("power", [1, 2])
+def test_ddpm_fused_loop_multi_image(K, power):
+    from functools import partial
+    from dps_ttc_amd.condition_methods import get_conditioning_method
+    from dps_ttc_amd.measurements import get_noise
+    M, k, hw = 3, 2, 64
+    gen = torch.Generator(device=DEV).manual_seed(17)
+    op, _ = _operator("gauss", hw, M)
+    cm = get_conditioning_method("ps", op, get_noise("gaussian", sigma=0.05), scale=0.5)
+    fn = partial(cm.conditioning, norm_exp=power)
+    y = _measurements(op, None, M, hw, gen)
+    x0 = torch.randn(M * k, 3, hw, hw, device=DEV, generator=gen)
+    bank = _noise_bank(20, M * k, hw)
+    model = StandInModel().to(DEV)
+    outs = []
+    for groups in (1, 2):
+        smp = _sampler("ddpm")
+        smp.particle_groups = groups
+        _patch_randn(smp, bank, 0)
+        img, d, _ = smp.p_sample_loop(model=model, x_start=x0.clone(), measurement=y, measurement_cond_fn=fn,
+                                      record=False, save_root=None)
+        torch.cuda.synchronize()
+        outs.append((img, d))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        smp = _sampler("ddpm")
+        _patch_randn(smp, bank, m * k)
+        img, d, _ = smp.p_sample_loop(model=model, x_start=x0[sl].clone(), measurement=y[m:m + 1],
+                                      measurement_cond_fn=fn, record=False, save_root=None)
+        assert torch.equal(outs[0][0][sl], img) and torch.equal(outs[0][1][sl], d)
+
+
+@pytest.mark.parametrize("single", [True, False])
+def test_search_ddpm_loop_multi_image(K, single):
+    M, k, hw = 3, 2, 64
+    gen = torch.Generator(device=DEV).manual_seed(19)
+    op, _ = _operator("sr4", hw, M)
+    y = _measurements(op, None, M, hw, gen)
+    x0 = torch.randn(M * k, 3, hw, hw, device=DEV, generator=gen)
+    bank = _noise_bank(20, M * k, hw, seed=23)
+    model = StandInModel().to(DEV)
+
+    def run(x, yy, offset, n_images):
+        smp = _sampler("search_ddpm")
+        smp.single_state = single
+        _patch_randn(smp, bank, offset)
+        bests = []
+        for name in ("search_step", "search_step_one"):
+            orig = getattr(smp, name)
+
+            def spy(*a, _orig=orig, **kw):
+                r = _orig(*a, **kw)
+                bests.append(smp.last_best.clone())
+                return r
+            setattr(smp, name, spy)
+        kw = {} if n_images is None else {"n_images": n_images}
+        img = smp.p_sample_loop(model=model, x_start=x.clone(), measurement=yy, measurement_cond_fn=None, record=False,
+                                save_root=None, operator=op, **kw)
+        return img, torch.stack([b.reshape(-1) for b in bests])
+
+    img, best = run(x0, y, 0, M)
+    assert best.shape == (20, M)
+    for m in range(M):
+        sl = slice(m * k, (m + 1) * k)
+        img_m, best_m = run(x0[sl], y[m:m + 1], m * k, None)
+        assert torch.equal(img[sl], img_m), m
+        assert torch.equal(best[:, m] - m * k, best_m[:, 0]), m
+
+
+def test_unsupported_combinations_raise(K):
+    from dps_ttc_amd.condition_methods import get_conditioning_method
+    from dps_ttc_amd.measurements import get_noise
+    M, k, hw = 2, 2, 64
+    op, _ = _operator("gauss", hw, M)
+    y = torch.rand(M, 3, hw, hw, device=DEV)
+    x0 = torch.randn(M * k, 3, hw, hw, device=DEV)
+    model = StandInModel().to(DEV)
+    noiser = get_noise("gaussian", sigma=0.05)
+    for method in ("mcg", "ps+"):
+        kw = {"scale": 0.5} if method == "mcg" else {"scale": 0.5, "num_sampling": 2}
+        cm = get_conditioning_method(method, op, noiser, **kw)
+        with pytest.raises(NotImplementedError, match="multi-image"):
+            _sampler("ddpm", "3").p_sample_loop(model=model, x_start=x0.clone(), measurement=y,
+                                                measurement_cond_fn=cm.conditioning, record=False, save_root=None)
+    with pytest.raises(NotImplementedError, match="ttc_ddim"):
+        cm = get_conditioning_method("ps", op, noiser, scale=0.5)
+        _sampler("ttc_ddim", "3").p_sample_loop(model=model, x_start=x0.clone(), measurement=y,
+                                                measurement_cond_fn=cm.conditioning, record=False, save_root=None)
+    smp = _sampler("search_ddpm", "3")
+    smp.global_select = lambda *a, **kw: None
+    with pytest.raises(NotImplementedError, match="global"):
+        smp.p_sample_loop(model=model, x_start=x0.clone(), measurement=y, measurement_cond_fn=None, record=False,
+                          save_root=None, operator=op, n_images=M)
+    with pytest.raises(NotImplementedError, match="resample_update"):
+        _sampler("search_ddpm", "3").resample_update(x0, x0, op, y)
+
+
+# ----------------------------------------------------------------- driver
+def _setup(tmp_path, task, sampler):
+    from PIL import Image
+    data = tmp_path / "data"
+    data.mkdir()
+    rng = np.random.RandomState(0)
+    for i in range(2):
+        img = np.kron(rng.rand(8, 8, 3), np.ones((32, 32, 1)))
+        Image.fromarray((img * 255).astype(np.uint8)).save(data / f"{i:05d}.png")
+    cfg = yaml.load(open(os.path.join(ROOT, "configs", task)), Loader=yaml.FullLoader)
+    cfg["data"]["root"] = str(data)
+    tpath = tmp_path / "task.yaml"
+    yaml.dump(cfg, open(tpath, "w"))
+    diff = yaml.load(open(os.path.join(ROOT, "configs", "diffusion_config.yaml")), Loader=yaml.FullLoader)
+    diff["sampler"] = sampler
+    dpath = tmp_path / "diffusion.yaml"
+    yaml.dump(diff, open(dpath, "w"))
+    return str(tpath), str(dpath)
+
+
+@pytest.mark.parametrize("task,sampler", [("gaussian_deblur_config.yaml", "ddpm"),
+                                          ("super_resolution_config.yaml", "search_ddpm")])
+def test_driver_images_per_batch(tmp_path, task, sampler):
+    sys.path.insert(0, ROOT)
+    import sample_condition_batched_ttc as drv
+    tpath, dpath = _setup(tmp_path, task, sampler)
+    out = tmp_path / "results"
+    drv.main(["--model_config", os.path.join(ROOT, "configs", "model_config.yaml"), "--diffusion_config", dpath,
+              "--task_config", tpath, "--save_dir", str(out), "--n_paths", "2", "--batch_size", "2",
+              "--ref_image_idxs", "0,1", "--images_per_batch", "2", "--timestep_respacing", "3", "--seed", "0",
+              "--gpu", "0"])
+    (sub,) = os.listdir(out)
+    root = out / sub
+    for fname in ("00000", "00001"):
+        assert (root / "input" / f"{fname}.png").exists() and (root / "label" / f"{fname}.png").exists()
+        for k in (1, 2):
+            assert (root / "recon_paths" / fname / f"path#{k}.png").exists()
+            assert (root / "recon_paths_y" / fname / f"path#{k}_y_space.png").exists()
+        assert (root / "best_of_n" / f"{fname}.png").exists()
+        d = np.load(root / f"{fname}_pathwise_distances.npy")
+        assert d.shape == (2,) and np.isfinite(d).all() and (d > 0).all()
+        best = int(np.argmin(d))
+        a = open(root / "best_of_n" / f"{fname}.png", "rb").read()
+        assert a == open(root / "recon_paths" / fname / f"path#{best + 1}.png", "rb").read()

@@ -2,9 +2,13 @@
 """Kernel micro-bench: time each launch of the fused DPS step (and the plain operator calls) in isolation.
 
     python tools/kbench.py [--operator gaussian_blur] [--particles 64] [--reps 30] [--only fwd,bwd,upd,op,adj]
+    python tools/kbench.py --operator super_resolution --particles 16 --images 4     (multi-image batches)
 
 Prints one line per launch: avg / min microseconds and achieved GB/s against the algorithmic bytes
 (SURVEY.md 8d).  Used under rocprofv3 for the per-kernel profiles in profiles/.
+--images M: the step's three launches (fwd, bwd, upd) for a multi-image batch of M images x --particles K with one
+measurement (and inpainting mask) per image, as ONE sequence of N = M K particles, against M sequential K-particle
+sequences with y[m] (and mask[m]) in the same process: us per step and particle-steps per second of both.
 """
 import argparse
 import os
@@ -26,7 +30,10 @@ def main():
     ap.add_argument("--sigma", type=float, default=3.0, help="gaussian_blur only: another radius bucket")
     ap.add_argument("--norm-in-fwd", action="store_true", help="K1 finishes the norm itself (last block of a particle)")
     ap.add_argument("--no-x0", action="store_true", help="K1 does not write x0_hat out (blur / resize; the `ps` loop's setting)")
+    ap.add_argument("--images", type=int, default=None, help="time the multi-image step of M images x --particles")
     args = ap.parse_args()
+    if args.images is not None:
+        return multi_image(args)
     from dps_ttc_amd import kernels
     from dps_ttc_amd.gaussian_diffusion import create_sampler
     dev = torch.device("cuda", 0)
@@ -85,6 +92,75 @@ def main():
         else:
             print(f"{name:6s} avg {ts.mean():8.1f} us  min {ts.min():8.1f} us   "
                   f"{bytes_pp * n / ts.mean() / 1e3:8.1f} GB/s algorithmic ({bytes_pp / P:.2f} P/particle{label})", flush=True)
+
+
+def multi_image(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    M, k = max(1, args.images), args.particles
+    n = M * k
+    op, fkw = bench.build_operator(args.operator, dev, sigma=args.sigma)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    x_t, ring, truth, _ = bench.synth_inputs(n, 2, dev, 1234)
+    # M different images (shifted copies of the synthetic truth) and, for inpainting, M different masks
+    masks = torch.cat([fkw["mask"].roll(13 * m, dims=-1) for m in range(M)]).contiguous() if "mask" in fkw else None
+    ys = []
+    for m in range(M):
+        kw = {} if masks is None else {"mask": masks[m:m + 1]}
+        ys.append(op.forward(truth.to(dev).roll(7 * m, dims=-1), **kw).detach())
+    y = torch.cat(ys).contiguous()
+    ck = smp.step_coefs[500]
+    want_x0 = not args.no_x0
+
+    def new_handle(mask_rows, x):
+        return kernels.OpHandle.mask(mask_rows, dev) if mask_rows is not None else op.new_hip_handle(x)
+
+    # one sequence of N = M K particles
+    h_all = new_handle(masks, x_t)
+    buf_all = kernels.StepBuffers(h_all, n, 3, 256, 256, dev)
+    # M sequences of K particles: own handle and buffers per image (particle slices of the same inputs)
+    hs = [new_handle(None if masks is None else masks[m:m + 1], x_t[:k]) for m in range(M)]
+    bufs = [kernels.StepBuffers(hs[m], k, 3, 256, 256, dev) for m in range(M)]
+    sl = [slice(m * k, (m + 1) * k) for m in range(M)]
+    xs = [x_t[s].contiguous() for s in sl]
+    rs = [[{key: r[key][s].contiguous() for key in ("model_out", "noise", "g_unet")} for s in sl] for r in ring]
+
+    def one(i):
+        r = ring[i % 2]
+        kernels.step_fwd(h_all, buf_all, x_t, r["model_out"], r["noise"], y, ck, want_x0=want_x0)
+        kernels.step_bwd(h_all, buf_all, y, 0.3, 1, ck)
+        kernels.step_update(buf_all, r["g_unet"], ck)
+
+    def seq(i):
+        for m in range(M):
+            r = rs[i % 2][m]
+            kernels.step_fwd(hs[m], bufs[m], xs[m], r["model_out"], r["noise"], y[m:m + 1], ck, want_x0=want_x0)
+            kernels.step_bwd(hs[m], bufs[m], y[m:m + 1], 0.3, 1, ck)
+            kernels.step_update(bufs[m], r["g_unet"], ck)
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    res = {}
+    for rep in range(3):                           # alternated: both forms see the same box state
+        for name, fn in (("one", one), ("seq", seq)):
+            res.setdefault(name, []).append(timed(fn))
+    for name, label in (("one", f"one sequence of N = {n}"), ("seq", f"{M} sequences of K = {k}")):
+        ts = np.concatenate(res[name])
+        print(f"images {args.operator} M={M} K={k} {label:28s} avg {ts.mean():8.1f} us/step  min {ts.min():8.1f}  "
+              f"{n / ts.mean():8.3f} M particle-steps/s (x0_hat store {'off' if args.no_x0 else 'on'})", flush=True)
 
 
 if __name__ == "__main__":
