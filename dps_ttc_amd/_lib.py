@@ -83,6 +83,8 @@ SIGNATURES = {
     "dpsx_argmin_seg_f32": (c_int, [_f, _i64, _i64, _p, _f, _p]),
     "dpsx_gather_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
     "dpsx_replicate_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
+    "dpsx_resample_draw_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _p, _p, _p]),
+    "dpsx_resample_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _f, _f, _f, _p, _p, _i64, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

@@ -906,6 +906,40 @@ int dpsx_replicate_f32(const float *src, const int64_t *idx_dev, float *dst, int
     return gather_f32(src, idx_dev, dst, n_out, n_src, chw, true, (hipStream_t)stream);
 }
 
+// shared argument checks of the two resampling entry points
+static int resample_args(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const int64_t *ids)
+{
+    if (!d || !u || !ids || segments < 1 || k < 1 || !(inv_scale >= 0.0f) || inv_scale > 3.402823466e38f)
+        return DPSX_EINVAL;
+    if (k > kResampleMaxK || segments > (1 << 24)) return DPSX_EUNSUPPORTED;       // the CDF of a segment lives in 8 k bytes of LDS
+    return DPSX_OK;
+}
+
+int dpsx_resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                               int64_t *ids_out, int32_t *q_out, void *stream)
+{
+    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
+    if (rc != DPSX_OK) return rc;
+    return resample_draw_seg_f32(d, u, segments, k, inv_scale, ids_out, q_out, (hipStream_t)stream);
+}
+
+int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                          const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
+                          int64_t n, int64_t chw, void *stream)
+{
+    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
+    if (rc != DPSX_OK) return rc;
+    if (!src || !dst || !d_out || n != segments * k || chw < 1) return DPSX_EINVAL;
+    // the gather reads whole particles of src while other blocks write dst: no overlap of the two ranges, and the
+    // distances are read by every block while one of them writes d_out
+    const char *sb = reinterpret_cast<const char *>(src), *db = reinterpret_cast<const char *>(dst);
+    const int64_t bytes = n * chw * (int64_t)sizeof(float);
+    if (sb < db + bytes && db < sb + bytes) return DPSX_EINVAL;
+    if (d_out < d + n && d < d_out + n) return DPSX_EINVAL;
+    if (n > 65535) return DPSX_EUNSUPPORTED;                              // one grid row per destination particle
+    return resample_seg_f32(d, u, segments, k, inv_scale, src, dst, d_out, ids_out, q_out, chw, (hipStream_t)stream);
+}
+
 int dpsx_pack_champion_f32(const float *particles, const float *costs, const int64_t *best_idx_dev,
                            const float *best_val_dev, float *out, int64_t n, int64_t chw, void *stream)
 {

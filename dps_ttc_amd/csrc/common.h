@@ -533,6 +533,14 @@ int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s);
 int argmin_f32(const float *v, int64_t n, int64_t *idx, float *val, hipStream_t s);
 int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw,
                bool replicate, hipStream_t s);
+// the per-segment resampling draw (include/dpsx.h): d, u [segments * k]; ids [segments * k] global particle indices,
+// q_out (nullable) the integer weights.  resample_seg_f32: the draw + dst[p] = src[ids[p]] + d_out[p] = d[ids[p]] in one
+// launch (chw >= 1, src and dst do not alias; the caller checked k <= 4096 and the grid limits)
+constexpr int kResampleMaxK = 4096;           // 8 B of LDS per particle of a segment: 32 KB
+int resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, int64_t *ids,
+                          int32_t *q_out, hipStream_t s);
+int resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
+                     float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, hipStream_t s);
 int pack_champion(const float *particles, const float *costs, const int64_t *best, const float *val, float *out, int64_t n,
                   int64_t chw, hipStream_t s);
 int select_champion(const float *table, int world, int64_t chw, float *dst, int64_t n_out, int64_t *win_rank,

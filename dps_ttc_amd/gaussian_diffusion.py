@@ -147,6 +147,10 @@ class GaussianDiffusion:
         self.rng_parity = False
         #: strides of the reference run's measurement tensor (only read when rng_parity is set)
         self.parity_measurement_stride = None
+        #: the resampling draw of ttc_ddim / resample_update: "multinomial" (torch.multinomial over all N weights, the
+        #: reference's draw) or "device" (kernels.resample: a pure function of the distances and one torch.rand per slot,
+        #: computed per image on the device and fused with the particle gather -- the draw multi-image batches need)
+        self.resample_draw = "multinomial"
         self.progress = False
         self.last_measurement_distance = None
         self.last_semantic_distance = None
@@ -174,6 +178,18 @@ class GaussianDiffusion:
                 torch.empty_strided(tuple(like.shape), tuple(stride), dtype=torch.float32)
             return torch.randn_like(proxy).contiguous().to(like.device)
         return torch.randn_like(like, dtype=torch.float32)
+
+    def _rand(self, n, like):
+        """n uniforms in [0, 1) on like's device (fp32: multiples of 2^-24) -- the device resampling draw's input"""
+        if self.rng_parity:
+            return torch.rand(int(n), dtype=torch.float32).to(like.device)
+        return torch.rand(int(n), dtype=torch.float32, device=like.device)
+
+    @staticmethod
+    def _check_resample_draw(value):
+        if value not in ("multinomial", "device"):
+            raise ValueError(f"resample_draw must be 'multinomial' or 'device' (got {value!r})")
+        return value
 
     # -- q ------------------------------------------------------------------
     def q_sample(self, x_start, t):
@@ -656,10 +672,29 @@ class SearchDDPM(DDPM):
         if potential_type not in ('mean', 'min', 'diff', 'curr'):
             raise NotImplementedError
         n = denoised_candidates.shape[0]
-        if (kwargs.get('n_images', None) or 1) > 1 or self._measurement_images(measurement, n) is not None:
+        draw = self._check_resample_draw(kwargs.get('resample_draw', None) or self.resample_draw)
+        images = self._measurement_images(measurement, n)
+        n_images = int(kwargs.get('n_images', None) or 1)
+        if images is not None and n_images > 1 and images != n_images:
+            raise ValueError(f"n_images={n_images} with a measurement of {images} rows")
+        segments = images or n_images
+        if segments > 1 and draw != "device":
             raise NotImplementedError("resample_update over a multi-image batch is not supported: the multinomial draw "
-                                      "would mix particles of different images (it needs a per-image RNG stream policy)")
-        if resample and prev_costs is not None:
+                                      "would mix particles of different images (it needs a per-image RNG stream policy; "
+                                      "resample_draw='device' draws per image)")
+        if segments < 1 or n % segments:
+            raise ValueError(f"{n} particles do not split into {segments} images")
+        if draw == "device":
+            if resample and prev_costs is not None:
+                # one uniform per slot whatever the weights turn out to be (a flat segment keeps its particles: the
+                # draw's identity rule), so the stream position does not depend on data and nothing is read back
+                inv = rs_temp / steps_done if potential_type == 'mean' else rs_temp
+                ids = kernels.resample_draw(prev_costs, self._rand(n, prev_costs), segments, inv)
+                self.last_resample_ids = ids
+                candidates = kernels.gather(candidates, ids, validate=False)      # ids inside [0, n) by construction
+                denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
+                prev_costs = kernels.gather(prev_costs.reshape(n, 1), ids, validate=False).reshape(n)
+        elif resample and prev_costs is not None:
             pot = torch.exp(-rs_temp * prev_costs / steps_done) if potential_type == 'mean' \
                 else torch.exp(-rs_temp * prev_costs)
             if pot.max() != pot.min():                                                     # :545
@@ -683,26 +718,53 @@ class TTC_DDIM(DDIM):
     Multi-GPU (SURVEY.md 8e iii): with `global_resample` set (the driver does when WORLD_SIZE > 1) the weights of
     all ranks' particles are all-gathered, every rank draws the same ids from `resample_generator` (a host
     generator seeded identically on all ranks) and fetches its slots of the resampled set -- the same particle
-    set one process holding all particles would produce from that generator."""
+    set one process holding all particles would produce from that generator.
+
+    `resample_draw = "device"`: the draw is the library's own (include/dpsx.h "resampling draw": integer weights
+    normalised by the best particle, an exact integer CDF, one torch.rand per slot) and runs with both gathers in ONE
+    launch (kernels.resample).  It is defined per image, so a measurement with one row per image (or `n_images = M`)
+    is accepted in that mode: image m's particles are resampled among themselves, and fed the same uniforms they are
+    what a single-image run draws, bit for bit.  The default stays torch.multinomial over all N weights, and
+    `global_resample` (several ranks) keeps its own multinomial draw whatever this option says."""
 
     global_resample = False
     resample_generator = None
     #: how the drawn particles travel between ranks: "selected" (one all-to-all of the drawn ones, each once per
     #: destination), "all" (all-gather of every state, no host read of device ids) or "auto" (distributed.resample_particles)
     resample_fetch = "auto"
+    _resample_segments = 1
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
         kernels.require_cuda(img, "x_start")
-        if (kwargs.get('n_images', None) or 1) > 1 or self._measurement_images(measurement, img.shape[0]) is not None:
-            raise NotImplementedError("ttc_ddim over a multi-image batch is not supported: its resampling would mix "
-                                      "particles of different images (it needs a per-image RNG stream policy)")
+        draw = self._check_resample_draw(self.resample_draw)
+        n = img.shape[0]
+        images = self._measurement_images(measurement, n)
+        n_images = int(kwargs.get('n_images', None) or 1)
+        if images is not None and n_images > 1 and images != n_images:
+            raise ValueError(f"n_images={n_images} with a measurement of {images} rows")
+        segments = images or n_images
+        if segments < 1 or n % segments:
+            raise ValueError(f"{n} particles do not split into {segments} images")
         resample_every_steps, resample_scale = 10, 100
         distance = None
         self.last_resample_ids = None
         # 'ps'-type methods run the three fused launches with the DDIM variant of S1; the rest (e.g. 'mcg', the
         # method whose two return values fit the reference loop's unpacking at :672) go through the per-op path
         plan = self._fusion_plan(measurement_cond_fn, img)
+        if segments > 1:
+            if draw != "device":
+                raise NotImplementedError("ttc_ddim over a multi-image batch is not supported: its resampling would mix "
+                                          "particles of different images (it needs a per-image RNG stream policy: "
+                                          "resample_draw = 'device' draws per image)")
+            if self.global_resample:
+                raise NotImplementedError("ttc_ddim over a multi-image batch with global (multi-rank) resampling is not "
+                                          "supported: the exchange draws over all ranks' particles as one set")
+            try:
+                self._check_multi_image(plan, self._unwrap_cond_fn(measurement_cond_fn)[0], False, segments, n)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"ttc_ddim: {e}") from None
+        self._resample_segments = segments      # the images of this trajectory's particle set (_resample draws per image)
         for idx in range(self.num_timesteps - 1, -1, -1):
             if plan is not None:
                 noise = self._randn(img)
@@ -732,6 +794,13 @@ class TTC_DDIM(DDIM):
             img, distance, ids = dd.global_resample(img, distance, resample_scale, self.resample_generator,
                                                      fetch=self.resample_fetch)
             self.last_resample_ids = ids if ids is not None else self.last_resample_ids
+            return img, distance
+        if self.resample_draw == "device":
+            # one launch: per-image draw + both gathers.  img / distance are views of the persistent step buffers on the
+            # fused route (the launch's src / d), the results are fresh tensors
+            img, distance, ids = kernels.resample(img, distance, self._rand(n, distance),
+                                                  self._resample_segments, 1.0 / resample_scale)
+            self.last_resample_ids = ids
             return img, distance
         if n <= 1:
             return img, distance

@@ -442,6 +442,49 @@ def replicate(src, idx_dev, n_out=None):
     return dst
 
 
+def _resample_args(d, u, segments):
+    d, u = f32c(d.reshape(-1), "distances"), f32c(u.reshape(-1), "uniforms")
+    segments = int(segments)
+    n = d.numel()
+    if segments < 1 or n == 0 or n % segments:
+        raise ValueError(f"{n} distances do not split into {segments} non-empty segments")
+    if u.numel() != n:
+        raise ValueError(f"the draw takes one uniform per particle ({u.numel()} for {n})")
+    if u.device != d.device:
+        raise ValueError("distances and uniforms live on different devices")
+    return d, u, segments, n
+
+
+def resample_draw(d, u, segments, inv_scale, want_weights=False):
+    """The resampling draw of include/dpsx.h per segment of K = N / segments particles: d [N] distances, u [N] uniforms in
+    [0, 1) (one per output slot, e.g. torch.rand) -> ids [N] int64 global particle indices, each inside its own segment;
+    a pure function of (d, u), one launch, nothing read back.  want_weights: also the integer weights q [N] int32."""
+    d, u, segments, n = _resample_args(d, u, segments)
+    ids = torch.empty(n, dtype=torch.int64, device=d.device)
+    q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
+    check(lib().dpsx_resample_draw_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
+                                           stream_of(d)), "dpsx_resample_draw_seg_f32")
+    return (ids, q) if want_weights else ids
+
+
+def resample(src, d, u, segments, inv_scale, want_weights=False):
+    """resample_draw fused with the gathers, ONE launch: -> (src[ids], d[ids], ids[, q]) for src [N, ...] fp32.
+    The results are fresh tensors (the launch does not work in place)."""
+    src = f32c(src, "particles")
+    d, u, segments, n = _resample_args(d, u, segments)
+    if src.dim() < 1 or src.shape[0] != n or src.device != d.device:
+        raise ValueError(f"{n} distances for particles of shape {tuple(src.shape)} on {src.device}")
+    if src[0].numel() == 0:
+        raise ValueError("empty particles")
+    dst, d_out = torch.empty_like(src), torch.empty_like(d)
+    ids = torch.empty(n, dtype=torch.int64, device=d.device)
+    q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
+    check(lib().dpsx_resample_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
+                                      ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), stream_of(src)),
+          "dpsx_resample_seg_f32")
+    return (dst, d_out, ids, q) if want_weights else (dst, d_out, ids)
+
+
 def pack_champion(particles, costs=None, best=None, best_val=None, out=None):
     """This rank's record for the champion exchange (distributed._exchange_champions): [C*H*W floats of particles[best] |
     cost, (float)best, 0, 0] in ONE launch.  best=None: the torch.argmin-order select over `costs` runs inside the launch."""

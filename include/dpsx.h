@@ -274,6 +274,28 @@ int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst,
 int dpsx_replicate_f32(const float *src, const int64_t *idx_dev, float *dst,
                        int64_t n_out, int64_t n_src, int64_t chw, void *stream);
 
+/* ---- resampling draw: a pure function of (distances, uniforms), per segment of k particles (one image of a multi-image
+ * batch; segments = 1: the whole set).  d, u: [segments * k] fp32, u[j] in [0, 1) is the caller's uniform of output slot j
+ * (the library owns no RNG state); inv_scale finite and >= 0.  For each segment:
+ *   1. a NaN / infinite distance gets weight 0; d_min = the minimum over the finite ones
+ *   2. w_i = expf(-(d_i - d_min) * inv_scale)                       (fp32; the best particle has weight 1)
+ *   3. q_i = (uint32) rintf(w_i * 2^24)                             (integer weights in [0, 2^24])
+ *   4. all q_i equal (k = 1 and "no finite distance" included): the segment's ids are the identity
+ *   5. else cdf_i = q_0 + ... + q_i in 64-bit integers, total = cdf_{k-1},
+ *      ui = clamp((uint32)(u * 2^24), 0, 2^24 - 1) (NaN counts as 0), target = (total * ui) >> 24,
+ *      slot j takes the smallest i with cdf_i > target.
+ * Ids are global particle indices (segment * k + i), always inside their own segment; a particle with q_i = 0 is never
+ * drawn.  The sums are integer sums, so the ids do not depend on how the launch splits the work: a segmented call and
+ * one call per segment fed u[m k .. (m + 1) k) agree bit for bit.  k <= 4096 (DPSX_EUNSUPPORTED above).
+ *   draw:     ids_out [n] int64, q_out [n] int32 (nullable: the integer weights).
+ *   resample: the same draw fused with the gathers, one launch: dst[p] = src[ids[p]] ([n, chw] fp32), d_out[p] = d[ids[p]].
+ *             n = segments * k <= 65535; src / dst and d / d_out must not overlap (DPSX_EINVAL). */
+int dpsx_resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                               int64_t *ids_out, int32_t *q_out, void *stream);
+int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                          const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
+                          int64_t n, int64_t chw, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

@@ -15,7 +15,8 @@ Differences from the reference script, all fixes of things that crash there (SUR
 the sampler returns a tensor for this call signature, LPIPS is logged only if torchmetrics is installed.
 `--images_per_batch M` runs up to M reference images per sampler call, `batch_size` particles each, with one
 measurement (and, for inpainting, one mask) per image: M x batch_size particles in one launch sequence, the select of
-`search_ddpm` and the best-of-N per image.  One rank only; not with `ttc_ddim` or `--embedder`.
+`search_ddpm` and the best-of-N per image.  One rank only; not with `--embedder`; `ttc_ddim` needs
+`--resample_draw device` (its per-image resampling draw).
 With `torchrun --nproc-per-node G` (the reference shards by hand: run0.sh:12 / run1.sh:13 start one process per GPU
 with its own --path_start_idx) the particle groups are sharded contiguously over the ranks and the best-of-N pick is
 global: RCCL all-gather of the distances, winner broadcast from its owner.  `sampler: search_ddpm` then selects over
@@ -106,6 +107,10 @@ def parse_args(argv=None):
     p.add_argument('--images_per_batch', type=int, default=1,
                    help='run up to this many reference images per sampler call, batch_size particles each, with one '
                         'measurement (and inpainting mask) per image; selects and best-of-N stay per image')
+    p.add_argument('--resample_draw', type=str, default='multinomial', choices=('multinomial', 'device'),
+                   help='the resampling draw of ttc_ddim: torch.multinomial over all particles (default, the '
+                        "reference's draw) or the library's per-image draw fused with the particle gather "
+                        '(one launch; required for --images_per_batch > 1 with ttc_ddim)')
     return p.parse_args(argv)
 
 
@@ -125,9 +130,9 @@ def check_images_per_batch(args, sampler_name, world):
     if world > 1:
         raise SystemExit("--images_per_batch > 1 runs on one rank only: sharding a multi-image batch over "
                          f"WORLD_SIZE={world} ranks is not supported")
-    if sampler_name == 'ttc_ddim':
+    if sampler_name == 'ttc_ddim' and args.resample_draw != 'device':
         raise SystemExit("--images_per_batch > 1 is not supported with sampler ttc_ddim: its resampling would mix the "
-                         "particles of different images")
+                         "particles of different images (--resample_draw device draws per image)")
     if args.embedder is not None:
         raise SystemExit("--images_per_batch > 1 is not supported with --embedder: semantic guidance has one target "
                          "for all particles")
@@ -187,6 +192,7 @@ def main(argv=None):
 
     sampler = create_sampler(**diffusion_config)
     sampler.particle_groups = max(1, args.particle_groups)
+    sampler.resample_draw = args.resample_draw
     groups = args.n_paths // args.batch_size
     if world > 1 and diffusion_config['sampler'] in ('search_ddpm', 'ttc_ddim'):
         # these loops exchange particles at every select / resample point: every rank runs the same number of groups
@@ -338,6 +344,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
     for g in range(groups):
         x_start = torch.randn((B * K, C, H, W), device=device).requires_grad_()
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
+        if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances)
+            sample = sample[0]
         with torch.no_grad():
             y_space = operator.forward(sample, **fkw)
             handle = operator.hip_handle_for(fkw['mask']) if op_name == 'inpainting' else operator.hip_handle(sample)

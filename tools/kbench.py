@@ -6,9 +6,14 @@
 
 Prints one line per launch: avg / min microseconds and achieved GB/s against the algorithmic bytes
 (SURVEY.md 8d).  Used under rocprofv3 for the per-kernel profiles in profiles/.
+    python tools/kbench.py --resample [--images M]                                    (the resampling step, 256^2)
 --images M: the step's three launches (fwd, bwd, upd) for a multi-image batch of M images x --particles K with one
 measurement (and inpainting mask) per image, as ONE sequence of N = M K particles, against M sequential K-particle
 sequences with y[m] (and mask[m]) in the same process: us per step and particle-steps per second of both.
+--resample: the resampling step of ttc_ddim on [N, 3, 256, 256] particles, three forms alternated in one process:
+(a) torch.multinomial + its [N]-sized glue + two gathers (resample_draw = "multinomial", the non-parity branch),
+(b) kernels.resample_draw + two gathers, (c) the fused kernels.resample; single image at K = 16 / 64 / 512 and
+M (default 4) images x K = 16, there also against M single-image calls of each form.
 """
 import argparse
 import os
@@ -31,7 +36,10 @@ def main():
     ap.add_argument("--norm-in-fwd", action="store_true", help="K1 finishes the norm itself (last block of a particle)")
     ap.add_argument("--no-x0", action="store_true", help="K1 does not write x0_hat out (blur / resize; the `ps` loop's setting)")
     ap.add_argument("--images", type=int, default=None, help="time the multi-image step of M images x --particles")
+    ap.add_argument("--resample", action="store_true", help="time the resampling step (multinomial / draw + gathers / fused)")
     args = ap.parse_args()
+    if args.resample:
+        return resample_step(args)
     if args.images is not None:
         return multi_image(args)
     from dps_ttc_amd import kernels
@@ -161,6 +169,70 @@ def multi_image(args):
         ts = np.concatenate(res[name])
         print(f"images {args.operator} M={M} K={k} {label:28s} avg {ts.mean():8.1f} us/step  min {ts.min():8.1f}  "
               f"{n / ts.mean():8.3f} M particle-steps/s (x0_hat store {'off' if args.no_x0 else 'on'})", flush=True)
+
+
+def resample_step(args):
+    from dps_ttc_amd import kernels
+    dev = torch.device("cuda", 0)
+    M4 = max(1, args.images or 4)
+    scale = 100.0
+    gen = torch.Generator(device=dev).manual_seed(1234)
+
+    def multinomial(img, distance, u, segments):      # TTC_DDIM._resample, resample_draw = "multinomial", no rng_parity
+        n = len(distance)
+        weights = torch.exp(-distance / scale)
+        flat = weights.max() == weights.min()
+        drawn = torch.multinomial(torch.where(flat, torch.ones_like(weights), weights), n, replacement=True)
+        ids = torch.where(flat, torch.arange(n, device=img.device), drawn)
+        return kernels.gather(img, ids, validate=False), kernels.gather(distance.reshape(n, 1), ids, validate=False).reshape(n)
+
+    def draw_gather(img, distance, u, segments):
+        n = len(distance)
+        ids = kernels.resample_draw(distance, u, segments, 1.0 / scale)
+        return kernels.gather(img, ids, validate=False), kernels.gather(distance.reshape(n, 1), ids, validate=False).reshape(n)
+
+    def fused(img, distance, u, segments):
+        return kernels.resample(img, distance, u, segments, 1.0 / scale)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for a, b in evs:
+            a.record()
+            fn()
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for M, k in ((1, 16), (1, 64), (1, 512), (M4, 16)):
+        n = M * k
+        img = torch.randn(n, 3, 256, 256, device=dev, generator=gen)
+        distance = 50.0 + 30.0 * torch.randn(n, device=dev, generator=gen)
+        u = torch.rand(n, device=dev, generator=gen)
+        sl = [slice(m * k, (m + 1) * k) for m in range(M)]
+        parts = [(img[s], distance[s], u[s]) for s in sl]           # contiguous views: no copy in the timed region
+        forms = []
+        if M == 1:
+            forms.append(("a multinomial + 2 gathers", lambda: multinomial(img, distance, u, 1)))
+        forms += [("b draw + 2 gathers", lambda: draw_gather(img, distance, u, M)),
+                  ("c fused", lambda: fused(img, distance, u, M))]
+        if M > 1:
+            forms += [(f"a multinomial + 2 gathers, {M} calls", lambda: [multinomial(*p, 1) for p in parts]),
+                      (f"b draw + 2 gathers, {M} calls", lambda: [draw_gather(*p, 1) for p in parts]),
+                      (f"c fused, {M} calls", lambda: [fused(*p, 1) for p in parts])]
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        moved = 2.0 * n * (img[0].numel() + 1) * 4      # particles and distances, read once and written once
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            print(f"resample 256^2 M={M} K={k:3d} {name:36s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs})  "
+                  f"{moved / ts.mean() / 1e6:6.2f} TB/s = {moved / ts.mean() / 1e6 / 8.0:.2f} of 8 TB/s", flush=True)
+        del img, parts
 
 
 if __name__ == "__main__":
