@@ -545,7 +545,9 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
     case OP_TAPS: rc = blur_step_fwd(op, a, s); break;
     case OP_RESIZE: rc = resize_step_fwd(op, a, s); break;
     case OP_MASK:
-        // shapes that are not a multiple of 4: the host composes the step from the op-level calls
+        // shapes that are not a multiple of 4 have no fused form: the Python front end asks first (OpHandle.fuses_step in
+        // kernels.py mirrors mask_fused_ok) and GaussianDiffusion._fusion_plan then runs the step per op under autograd --
+        // S1, dpsx_op_forward_f32, dpsx_residual_norm_f32 and their VJPs; a caller that launches anyway gets the refusal
         if (!mask_fused_ok(op, c, h, w, {x_t, model_out, noise, y, x0_hat, sample}) ||
             (reinterpret_cast<uintptr_t>(inside) & 3u) != 0)
             return DPSX_EUNSUPPORTED;

@@ -264,6 +264,10 @@ class GaussianDiffusion:
             handle = op.hip_handle(x_start)
         else:
             return None
+        # a shape the fused launches refuse (inpainting with H * W off the float4 grid): decided here, before the first
+        # step, so the loop -- and the particle groups, which exist only under a plan -- takes the per-op path
+        if not handle.fuses_step(*x_start.shape[1:]):
+            return None
         return method, kw, handle
 
     def _buffers(self, handle, x):

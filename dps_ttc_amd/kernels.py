@@ -157,6 +157,13 @@ class OpHandle:
             pass
 
     # -- geometry / scratch
+    def fuses_step(self, c, h, w):
+        """whether step_fwd / step_bwd take this handle at [N, c, h, w] (mirror of mask_fused_ok in csrc/api.hip for buffers
+        torch allocated): the inpainting step exists in its float4 form only, H * W a multiple of 4; every other operator
+        has a scalar form.  Where this is False the launches return DPSX_EUNSUPPORTED and the loops take the per-op path
+        (GaussianDiffusion._fusion_plan asks before the first step)."""
+        return self.kind != _lib.KIND_MASK or (int(h) * int(w)) % 4 == 0
+
     def out_hw(self, h, w):
         oh, ow = c_int64(), c_int64()
         check(lib().dpsx_op_out_shape(self._h, h, w, byref(oh), byref(ow)), "dpsx_op_out_shape")

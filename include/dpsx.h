@@ -162,7 +162,11 @@ int64_t dpsx_step_resid_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h
  * prologue from the partial sums left in `workspace` (see there).
  * x0_hat == NULL (blur and resize operators, phase retrieval at the hand-written 384-point geometry): pred_xstart is consumed inside the launch -- A(x0_hat), the clamp gate --
  * and not written out; the `ps` step reads it nowhere afterwards (posterior_mean_variance.py:96-129 returns it to
- * condition_methods.py:33-60, which uses it for the norm only).  The other operators read it back and require it. */
+ * condition_methods.py:33-60, which uses it for the norm only).  The other operators read it back and require it.
+ * DPSX_EUNSUPPORTED (here and from dpsx_step_bwd_f32, before anything is launched): an inpainting op whose H * W is not
+ * a multiple of 4, or whose buffers are not 16-byte aligned -- that step exists in its float4 form only.  The caller runs
+ * such a step from the per-op calls instead (dpsx_posterior_fwd_f32, dpsx_op_forward_f32, dpsx_residual_norm_f32 and
+ * their VJPs); the Python front end decides this from the shape before its loop starts (OpHandle.fuses_step). */
 int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
                       const float *y, int64_t y_n,
                       float *x0_hat, float *sample, uint8_t *inside, void *resid, float *norm,

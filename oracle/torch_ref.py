@@ -8,6 +8,7 @@ launches per step, in its order, with autograd doing the backward half --
     A       ReflectionPad2d + depthwise Conv2d     util/img_utils.py:275-283        (gaussian_blur, motion_blur)
             x[fov] * w, sum(0) per axis            util/resizer.py:59-72            (super_resolution)
             x * mask                               measurements.py:160              (inpainting)
+            x                                      measurements.py:60-62            (noise: the denoising task)
             pad, ifftshift, fft2(ortho), fftshift, abs   measurements.py:186-189, util/fastmri_utils.py:67-89
     norm    linalg.norm(y - A x0_hat) per particle, autograd.grad    condition_methods.py:179-185
     update  sample - grad                          gaussian_diffusion.py:255
@@ -50,6 +51,8 @@ class TorchOperator:
             return x
         if self.name == "inpainting":
             return x * self.mask
+        if self.name == "noise":
+            return x
         if self.name == "phase_retrieval":
             p = F.pad(x, (self.fpad,) * 4)
             z = torch.fft.fftshift(torch.fft.fftn(torch.fft.ifftshift(p.to(torch.complex64), dim=(-2, -1)), dim=(-2, -1),

@@ -114,6 +114,12 @@ def _inputs(g, tag):
     return x.numpy(), u.numpy()
 
 
+def _pair(hw):
+    """hw: a side or an (h, w) pair -> (h, w, an int to seed with)"""
+    h, w = (hw, hw) if isinstance(hw, int) else hw
+    return h, w, h + w if h != w else h
+
+
 def make_product_op(name, g=None, hw=64, **extra):
     from dps_ttc_amd.measurements import get_operator
     if name == "gauss":
@@ -128,6 +134,8 @@ def make_product_op(name, g=None, hw=64, **extra):
         return get_operator("inpainting", device=DEV), {"mask": dev(extra["mask"])}
     if name == "phase":
         return get_operator("phase_retrieval", oversample=2.0, device=DEV), {}
+    if name == "denoise":
+        return get_operator("noise", device=DEV), {}
     raise KeyError(name)
 
 
@@ -142,6 +150,8 @@ def make_oracle_op(oracle, name, hw=64, **extra):
         return oracle.make_operator("inpainting", mask=extra["mask"])
     if name == "phase":
         return oracle.make_operator("phase_retrieval", oversample=2.0)
+    if name == "denoise":
+        return oracle.make_operator("noise")
     raise KeyError(name)
 
 
@@ -347,28 +357,30 @@ def test_residual_norm_and_vjp(K, oracle):
 
 # ----------------------------------------------------------------- fused DPS step vs oracle
 def _fused_case(K, oracle, name, n, hw, t, scale, power, seed, kernel=None, mask=None, finalize=False, ddim_eta=None,
-                extra=False, per_particle_y=False):
+                extra=False, per_particle_y=False, chw=None):
+    """chw: (C, H, W) where the image is not 3 x hw x hw"""
+    ch, ih, iw = chw if chw is not None else (3, hw, hw)
     rng = np.random.RandomState(seed)
     sched = oracle.tables.schedule(1000)
     c, ck = coefs_of(K, oracle, t, sched) if ddim_eta is None else ddim_coefs_of(K, oracle, t, ddim_eta, sched)
     op, fkw = make_product_op(name, hw=hw, kernel=kernel, mask=mask)
     orc = make_oracle_op(oracle, name, hw=hw, kernel=kernel, mask=mask)
-    x_prev = rng.randn(n, 3, hw, hw).astype(np.float32)
-    target = 1.4 * np.tanh(rng.randn(n, 3, hw, hw))
+    x_prev = rng.randn(n, ch, ih, iw).astype(np.float32)
+    target = 1.4 * np.tanh(rng.randn(n, ch, ih, iw))
     eps = ((c["a"] * x_prev - target) / c["b"]).astype(np.float32)
     mo = np.concatenate([eps, rng.uniform(-1, 1, eps.shape).astype(np.float32)], axis=1)
-    noise = rng.randn(n, 3, hw, hw).astype(np.float32)
-    truth = rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32)
+    noise = rng.randn(n, ch, ih, iw).astype(np.float32)
+    truth = rng.uniform(-1, 1, (1, ch, ih, iw)).astype(np.float32)
     y = orc.forward(truth)
     if per_particle_y:          # one measurement per particle ([N, ...] instead of the broadcast [1, ...])
         y = np.repeat(y, n, axis=0)
     y = (y + 0.05 * rng.randn(*y.shape)).astype(np.float32)
-    g_unet = (1e-2 * rng.randn(n, 3, hw, hw)).astype(np.float32)
-    g_extra = (0.05 * rng.randn(n, 3, hw, hw)).astype(np.float32) if extra else None
+    g_unet = (1e-2 * rng.randn(n, ch, ih, iw)).astype(np.float32)
+    g_extra = (0.05 * rng.randn(n, ch, ih, iw)).astype(np.float32) if extra else None
     ref = oracle.dps_step(orc, x_prev, mo, noise, y, c, scale=scale, power=power, g_unet_fn=lambda g: g_unet,
                           g_x0_extra=g_extra)
     handle = op.hip_handle_for(fkw["mask"]) if name == "inpaint" else op.hip_handle(dev(x_prev))
-    buf = K.StepBuffers(handle, n, 3, hw, hw, DEV)
+    buf = K.StepBuffers(handle, n, ch, ih, iw, DEV)
     K.step_fwd(handle, buf, dev(x_prev), dev(mo), dev(noise), dev(y), ck, finalize_norm=finalize)
     if finalize:        # norms already final after K1 (the stand-alone finalisation kernel)
         assert rel_l2(host(buf.norm), ref["norm"]) < TOL
@@ -379,12 +391,12 @@ def _fused_case(K, oracle, name, n, hw, t, scale, power, seed, kernel=None, mask
     assert rel_l2(host(buf.sample), ref["sample"]) < 1e-6
     assert rel_l2(host(buf.norm), ref["norm"]) < TOL
     assert rel_l2(host(buf.g_model_out), ref["g_model_out"]) < TOL
-    assert np.all(host(buf.g_model_out)[:, 3:] == 0)
+    assert np.all(host(buf.g_model_out)[:, ch:] == 0)
     assert rel_l2(host(x_next) - ref["sample"], ref["x_next"] - ref["sample"]) < TOL      # the update itself
     assert rel_l2(host(x_next), ref["x_next"]) < 1e-6
     if name == "inpaint":      # gradient support = mask AND clamp gate, bit-exact pattern
-        pat = (host(buf.g_model_out)[:, :3] != 0)
-        expect = (ref["g_model_out"][:, :3] != 0)
+        pat = (host(buf.g_model_out)[:, :ch] != 0)
+        expect = (ref["g_model_out"][:, :ch] != 0)
         np.testing.assert_array_equal(pat, expect)
 
 
@@ -472,7 +484,8 @@ def test_phase_spectral_step_full_size(K, oracle, t, power, extra):
     _fused_case(K, oracle, "phase", 1, 256, t, 0.6, power, seed=41 + t, extra=extra, finalize=True)
 
 
-@pytest.mark.parametrize("name,hw", [("gauss", 128), ("motion", 64), ("sr4", 64), ("inpaint", 64), ("phase", 32), ("phase", 256)])
+@pytest.mark.parametrize("name,hw", [("gauss", 128), ("motion", 64), ("sr4", 64), ("inpaint", 64), ("phase", 32), ("phase", 256),
+                                     ("denoise", 17)])
 def test_fused_step_per_particle_measurement(K, golden, name, hw):
     """y given once ([1, ...], broadcast) or per particle ([N, ...]): the same launches, bit-identical results"""
     g = golden("operators")
@@ -498,7 +511,7 @@ def test_fused_step_per_particle_measurement(K, golden, name, hw):
     assert float(out[0][1].abs().max()) > 0
 
 
-@pytest.mark.parametrize("name,hw", [("gauss", 128), ("sr4", 64), ("inpaint", 64), ("motion", 64)])
+@pytest.mark.parametrize("name,hw", [("gauss", 128), ("sr4", 64), ("inpaint", 64), ("motion", 64), ("denoise", 64)])
 def test_fused_step_is_graph_capturable(K, golden, name, hw):
     """The three launches allocate nothing and never synchronise: captured once in a HIP graph on a
     side stream and replayed on new inputs, they give the eager results bit for bit."""
@@ -929,17 +942,19 @@ def test_resample_update_golden(K, golden, tag, oname):
 
 @pytest.mark.parametrize("name,hw,n", [("gauss", 256, 5), ("motion", 256, 3), ("sr4", 256, 5), ("sr8", 256, 3),
                                        ("inpaint", 256, 4), ("phase", 256, 2), ("gauss", 46, 3), ("sr4", 36, 3),
-                                       ("inpaint", 30, 3)])
+                                       ("inpaint", 30, 3), ("denoise", 17, 3), ("phase", 34, 2), ("phase", 36, 2),
+                                       ("inpaint", 63, 3), ("inpaint", (62, 63), 3)])
 def test_resample_cost_vs_oracle(K, oracle, name, hw, n):
     """curr = ||y - A x||_1^2 / CHW and the four combines for every operator (full size and ragged), against the oracle;
     NaN in either cost propagates through 'min' as torch.min does"""
+    ih, iw, hw = _pair(hw)
     rng = np.random.RandomState(hw + n)
     kernel = synthetic_motion_kernel(61, 5)
-    mask = (np.random.RandomState(3).rand(1, 1, hw, hw) < 0.5).astype(np.float32)
+    mask = (np.random.RandomState(3).rand(1, 1, ih, iw) < 0.5).astype(np.float32)
     op, fkw = make_product_op(name, hw=hw, kernel=kernel, mask=mask)
     orc = make_oracle_op(oracle, name, hw=hw, kernel=kernel, mask=mask)
-    x = rng.uniform(-1, 1, (n, 3, hw, hw)).astype(np.float32)
-    y = orc.forward(rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32))
+    x = rng.uniform(-1, 1, (n, 3, ih, iw)).astype(np.float32)
+    y = orc.forward(rng.uniform(-1, 1, (1, 3, ih, iw)).astype(np.float32))
     y = (y + 0.05 * rng.randn(*y.shape)).astype(np.float32)
     handle = op.hip_handle_for(fkw["mask"]) if name == "inpaint" else op.hip_handle(dev(x))
     prev = (rng.rand(n) * 50).astype(np.float32)
@@ -959,14 +974,16 @@ def test_resample_cost_vs_oracle(K, oracle, name, hw, n):
 
 
 @pytest.mark.parametrize("name,hw,n", [("gauss", 256, 64), ("motion", 128, 9), ("sr4", 256, 64), ("inpaint", 256, 33),
-                                       ("phase", 256, 3), ("gauss", 46, 7), ("sr4", 64, 300)])
+                                       ("phase", 256, 3), ("gauss", 46, 7), ("sr4", 64, 300), ("denoise", 17, 7),
+                                       ("phase", 34, 2), ("phase", 36, 2), ("inpaint", 63, 3), ("inpaint", (62, 63), 3)])
 def test_score_argmin_fused(K, name, hw, n):
     """dpsx_score_argmin_f32: the scoring launch's own tail finishes the norms and the select -- same costs bit for bit
     as dpsx_score_f32, same index as torch.argmin (first minimum; NaN wins), repeatable (counters reset themselves)"""
+    ih, iw, hw = _pair(hw)
     gen = torch.Generator(device=DEV).manual_seed(n)
-    mask = (np.random.RandomState(3).rand(1, 1, hw, hw) < 0.5).astype(np.float32)
+    mask = (np.random.RandomState(3).rand(1, 1, ih, iw) < 0.5).astype(np.float32)
     op, fkw = make_product_op(name, hw=hw, kernel=synthetic_motion_kernel(61, 5), mask=mask)
-    x = torch.randn(n, 3, hw, hw, device=DEV, generator=gen)
+    x = torch.randn(n, 3, ih, iw, device=DEV, generator=gen)
     x[n // 2] = x[1]                                         # an exact tie: the first one must win
     handle = op.hip_handle_for(fkw["mask"]) if name == "inpaint" else op.hip_handle(x)
     y = op.forward(x[1:2] * 0.9, **fkw).detach().contiguous()
@@ -981,7 +998,8 @@ def test_score_argmin_fused(K, name, hw, n):
     assert int(best) == n - 1 and bool(torch.isnan(val).all())
 
 
-@pytest.mark.parametrize("name,hw", [("gauss", 256), ("motion", 128), ("sr4", 256), ("inpaint", 256), ("gauss", 46)])
+@pytest.mark.parametrize("name,hw", [("gauss", 256), ("motion", 128), ("sr4", 256), ("inpaint", 256), ("gauss", 46),
+                                     ("denoise", 17)])
 def test_step_fwd_norm_modes_bit_identical(K, name, hw):
     """K1 finishing the norm itself (last block of each particle) == the stand-alone finalisation kernel of r01 ==
     K2's prologue finalisation: the same bits, and repeatable over launches (self-resetting counters)"""
@@ -1012,7 +1030,8 @@ def test_step_fwd_norm_modes_bit_identical(K, name, hw):
     assert rel_l2(host(outs[0][0]), host(r.norm(dim=1))) < TOL
 
 
-@pytest.mark.parametrize("name,hw,n", [("gauss", 256, 64), ("sr4", 256, 64), ("inpaint", 256, 64), ("motion", 128, 16)])
+@pytest.mark.parametrize("name,hw,n", [("gauss", 256, 64), ("sr4", 256, 64), ("inpaint", 256, 64), ("motion", 128, 16),
+                                       ("denoise", 64, 8)])
 def test_in_launch_reduction_sees_fresh_partials(K, name, hw, n):
     """the tail of a launch re-reads partial sums other XCDs wrote a moment ago, in buffers earlier launches filled with
     other values: every launch of a sequence with CHANGING inputs must reproduce the norms of the materialised residual
@@ -1091,20 +1110,22 @@ def test_taps_regular_multi_tile(K, oracle, kind, seed, hw):
 
 
 @pytest.mark.parametrize("name,hw,n", [("gauss", 256, 9), ("gauss", 64, 5), ("gauss", 128, 3), ("gauss", 46, 4), ("sr4", 256, 5),
-                                       ("inpaint", 64, 4), ("motion", 128, 3), ("phase", 32, 2)])
+                                       ("inpaint", 64, 4), ("motion", 128, 3), ("phase", 32, 2), ("denoise", 64, 5),
+                                       ("denoise", 17, 4), ("inpaint", 63, 3), ("inpaint", (62, 63), 3)])
 @pytest.mark.parametrize("t", [700, 0])
 def test_search_step_fused_equals_separate(K, oracle, name, hw, n, t):
     """dpsx_search_step_f32 (S1, scoring launch, one launch for costs + select + replication) ==
     dpsx_posterior_fwd_f32 + dpsx_score_argmin_f32 + dpsx_replicate_f32, bit for bit: sample, costs, winner, x_next"""
+    ih, iw, hw = _pair(hw)
     rng = np.random.RandomState(hw + n + t)
-    mask = (np.random.RandomState(3).rand(1, 1, hw, hw) < 0.5).astype(np.float32)
+    mask = (np.random.RandomState(3).rand(1, 1, ih, iw) < 0.5).astype(np.float32)
     op, fkw = make_product_op(name, hw=hw, kernel=synthetic_motion_kernel(61, 5), mask=mask)
     _, ck = coefs_of(K, oracle, t)
-    x = dev(rng.randn(n, 3, hw, hw).astype(np.float32))
-    mo = dev(rng.randn(n, 6, hw, hw).astype(np.float32) * 0.5)
-    z = dev(rng.randn(n, 3, hw, hw).astype(np.float32))
+    x = dev(rng.randn(n, 3, ih, iw).astype(np.float32))
+    mo = dev(rng.randn(n, 6, ih, iw).astype(np.float32) * 0.5)
+    z = dev(rng.randn(n, 3, ih, iw).astype(np.float32))
     handle = op.hip_handle_for(fkw["mask"]) if name == "inpaint" else op.hip_handle(x)
-    y = op.forward(dev(rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32)), **fkw).detach().contiguous()
+    y = op.forward(dev(rng.uniform(-1, 1, (1, 3, ih, iw)).astype(np.float32)), **fkw).detach().contiguous()
     for yy in (y, y.expand(n, *y.shape[1:]).contiguous()):
         _, ref_sample = K.posterior_fwd(x, mo, z, ck, want_x0=False)
         ref_costs, ref_best, ref_val = handle.score_argmin(ref_sample, yy)
@@ -1118,7 +1139,8 @@ def test_search_step_fused_equals_separate(K, oracle, name, hw, n, t):
                 assert x_next is None
 
 
-@pytest.mark.parametrize("name,hw,n", [("gauss", 256, 9), ("gauss", 64, 5), ("sr4", 256, 5), ("inpaint", 64, 4), ("motion", 128, 3)])
+@pytest.mark.parametrize("name,hw,n", [("gauss", 256, 9), ("gauss", 64, 5), ("sr4", 256, 5), ("inpaint", 64, 4), ("motion", 128, 3),
+                                       ("denoise", 17, 4)])
 @pytest.mark.parametrize("t", [700, 0])
 def test_search_step_one_state_equals_replicated(K, oracle, name, hw, n, t):
     """dpsx_search_step_one_f32 (one state particle feeds all N proposals, the winner is copied out once) ==
@@ -1167,3 +1189,241 @@ def test_fused_step_without_x0_store(K, oracle, name):
     for a, b in zip(outs[0][:5], outs[1][:5]):
         assert torch.equal(a, b)
     assert bool((outs[1][5] == 123.0).all()) and not bool((outs[0][5] == 123.0).all())
+
+
+# ----------------------------------------------------------------- the denoising operator (get_operator("noise"), OP_IDENT)
+@pytest.mark.parametrize("shape", [(2, 3, 64, 64), (3, 3, 17, 13), (1, 1, 5, 3)])
+def test_identity_handle_copies_bit_exact(K, shape):
+    """OpHandle.identity: A and A^T are device-to-device copies, out_hw is the identity; its scoring launch always uses
+    64 partial slots per particle, more than the 15 elements of the smallest shape here (empty chunks sum to zero)"""
+    gen = torch.Generator(device=DEV).manual_seed(shape[-1])
+    h = K.OpHandle.identity(DEV)
+    assert h.kind == K._lib.KIND_IDENT and h.out_hw(*shape[-2:]) == tuple(shape[-2:]) and h.fuses_step(*shape[1:])
+    x, u = torch.randn(*shape, device=DEV, generator=gen), torch.randn(*shape, device=DEV, generator=gen)
+    y, g = h.forward(x), h.adjoint(u, in_hw=shape[-2:])
+    assert y.data_ptr() != x.data_ptr() and torch.equal(y, x)
+    assert g.data_ptr() != u.data_ptr() and torch.equal(g, u)
+    meas = torch.randn(1, *shape[1:], device=DEV, generator=gen)
+    ref = torch.linalg.norm((meas - x).reshape(shape[0], -1).double(), dim=-1).cpu().numpy()
+    assert rel_l2(host(h.score(x, meas)), ref) < TOL
+    costs, best, val = h.score_argmin(x, meas)
+    assert torch.equal(costs, h.score(x, meas)) and int(best) == int(torch.argmin(costs)) and float(val) == float(costs[int(best)])
+    op, _ = make_product_op("denoise")
+    xt = x.clone().requires_grad_()
+    (adj,) = torch.autograd.grad((op.forward(xt) * u).sum(), xt)
+    assert torch.equal(adj, u) and op.hip_handle(x).kind == K._lib.KIND_IDENT
+
+
+@pytest.mark.parametrize("hw", [64, 17])          # 17: 867 floats per particle, the scalar kernels
+@pytest.mark.parametrize("t", [900, 400, 0])
+@pytest.mark.parametrize("power", [1, 2])
+def test_denoise_fused_step_vs_oracle(K, oracle, hw, t, power):
+    """S1 + residual_partials, [finalize_norm] + clamp_scale_to_eps against the oracle, both norm-finalisation modes"""
+    for finalize in (False, True):
+        _fused_case(K, oracle, "denoise", 3, hw, t, 0.7, power, seed=hw + t + power, finalize=finalize)
+
+
+@pytest.mark.parametrize("hw", [64, 17])
+@pytest.mark.parametrize("t,eta", [(900, 0.0), (400, 0.7), (0, 0.0)])
+def test_denoise_fused_step_ddim_vs_oracle(K, oracle, hw, t, eta):
+    _fused_case(K, oracle, "denoise", 3, hw, t, 0.7, 1, seed=hw + t + 1, ddim_eta=eta)
+
+
+@pytest.mark.parametrize("hw", [64, 17])
+def test_denoise_fused_step_extra_cotangent_and_per_particle_y(K, oracle, hw):
+    _fused_case(K, oracle, "denoise", 3, hw, 600, 0.7, 1, seed=hw + 3, extra=True)
+    _fused_case(K, oracle, "denoise", 2, hw, 0, 0.4, 2, seed=hw + 4, extra=True, finalize=True)
+    _fused_case(K, oracle, "denoise", 3, hw, 300, 0.4, 1, seed=hw + 5, per_particle_y=True)
+    _fused_case(K, oracle, "denoise", 2, hw, 700, 0.4, 2, seed=hw + 6, per_particle_y=True, extra=True, finalize=True)
+
+
+@pytest.mark.parametrize("chw", [(3, 160, 160), (1, 5, 3)])
+def test_denoise_fused_step_partial_slot_counts(K, oracle, chw):
+    """the identity launches write and re-sum 64 partial slots per particle whatever the size, while the workspace holds
+    max(ceil(CHW / 1024), 64): 3 x 160 x 160 is where the first count (75) exceeds 64; 1 x 5 x 3 has fewer elements (15)
+    than slots"""
+    for finalize in (False, True):
+        _fused_case(K, oracle, "denoise", 2, chw[1], 500, 0.5, 1, seed=chw[1], finalize=finalize, chw=chw)
+        _fused_case(K, oracle, "denoise", 2, chw[1], 0, 0.5, 2, seed=chw[1] + 1, finalize=finalize, chw=chw, extra=True)
+
+
+def test_denoise_loop_fused_matches_per_op(K, golden):
+    """`ps` on the denoising task, as test_ttc_ddim_fused_matches_per_op: _fusion_plan takes the identity handle (three
+    fused launches per step), a foreign callable takes the per-op autograd path; two HIP routes to the same 20-step loop,
+    within the loop gate.  (ttc_ddim: the loop whose unpacking fits what `ps` returns on the per-op route.)"""
+    from dps_ttc_amd.condition_methods import get_conditioning_method
+    from dps_ttc_amd.measurements import get_noise
+    g = golden("loop")
+    op, _ = make_product_op("denoise")
+    cm = get_conditioning_method("ps", op, get_noise("gaussian", sigma=0.05), scale=0.5)
+    x_start = dev(g["gauss.r20.x_start"])
+    gen = torch.Generator(device=DEV).manual_seed(2)
+    y = (x_start[:1].tanh() + 0.05 * torch.randn(1, *x_start.shape[1:], device=DEV, generator=gen)).contiguous()
+    res = []
+    for fused in (True, False):
+        smp = _sampler("ttc_ddim", "20")
+        cond = cm.conditioning if fused else (lambda **kw: cm.conditioning(**kw))
+        plan = smp._fusion_plan(cond, x_start)
+        assert (plan is not None) == fused and (not fused or plan[2].kind == K._lib.KIND_IDENT)
+        torch.manual_seed(5)
+        img, dist = smp.p_sample_loop(model=StandInModel().to(DEV), x_start=x_start.clone().requires_grad_(),
+                                      measurement=y, measurement_cond_fn=cond, record=False, save_root=None)
+        res.append((host(img), host(dist), smp.last_resample_ids.cpu().numpy()))
+    assert np.isfinite(res[0][0]).all() and np.all(res[0][1] > 0)
+    np.testing.assert_array_equal(res[0][2], res[1][2])
+    assert rel_l2(res[0][0], res[1][0]) < 1e-4 and rel_l2(res[0][1], res[1][1]) < 1e-4
+
+
+# ----------------------------------------------------------------- shapes off the float4 grid
+@pytest.mark.parametrize("side", [34, 36])
+def test_phase_off_vector_grid_forward_adjoint(K, oracle, side):
+    """sides 34 and 36 with pad 64 (padded 162 / 164): h % 4 or (h + 2 pad) / 2 % 4 is non-zero, so nothing takes a
+    float4 form -- A and its autograd adjoint against the oracle's direct DFT"""
+    rng = np.random.RandomState(side)
+    op, _ = make_product_op("phase")
+    orc = make_oracle_op(oracle, "phase")
+    x = rng.uniform(-1, 1, (2, 3, side, side)).astype(np.float32)
+    u = rng.randn(2, 3, side + 128, side + 128).astype(np.float32)
+    xt = dev(x).requires_grad_()
+    y = op.forward(xt)
+    (adj,) = torch.autograd.grad((y * dev(u)).sum(), xt)
+    assert tuple(y.shape) == (2, 3, side + 128, side + 128)
+    assert rel_l2(host(y), orc.forward(x)) < TOL, "forward"
+    assert rel_l2(host(adj), orc.adjoint(u, (side, side))) < TOL, "adjoint"
+
+
+@pytest.mark.parametrize("side", [34, 36])
+@pytest.mark.parametrize("t", [900, 0])
+@pytest.mark.parametrize("power", [1, 2])
+def test_phase_off_vector_grid_fused_step_vs_oracle(K, oracle, side, t, power):
+    """the scalar staging kernel of phase_step_fwd and the un-fused backward (C2R, crop, clamp_scale_to_eps): both
+    norm-finalisation modes, with and without the extra cotangent"""
+    for finalize in (False, True):
+        for extra in (False, True):
+            _fused_case(K, oracle, "phase", 2, side, t, 0.6, power, seed=side + t + power, finalize=finalize, extra=extra)
+
+
+def test_phase_odd_padded_size_is_refused(K):
+    with pytest.raises(K._lib.DpsxError) as e:
+        K.OpHandle.phase(33, 64, 6, DEV)            # 33 + 2 x 64 = 161: no Hermitian half of an odd transform
+    assert e.value.code == K._lib.EINVAL
+
+
+@pytest.mark.parametrize("hw", [(63, 63), (62, 63)])         # H W = 1 and 2 (mod 4)
+def test_inpainting_off_grid_per_op_and_refusal(K, oracle, hw):
+    """H W not a multiple of 4: A and A^T (scalar k_mask_mul) stay bit-exact; the fused step has no such form, and the
+    library says so (DPSX_EUNSUPPORTED) before it launches anything -- OpHandle.fuses_step is the question to ask first"""
+    rng = np.random.RandomState(hw[0])
+    n = 3
+    mask = (np.random.RandomState(7).rand(1, 1, *hw) < 0.5).astype(np.float32)
+    op, fkw = make_product_op("inpaint", mask=mask)
+    orc = make_oracle_op(oracle, "inpaint", mask=mask)
+    x, u = rng.randn(n, 3, *hw).astype(np.float32), rng.randn(n, 3, *hw).astype(np.float32)
+    xt = dev(x).requires_grad_()
+    y = op.forward(xt, **fkw)
+    (adj,) = torch.autograd.grad((y * dev(u)).sum(), xt)
+    np.testing.assert_array_equal(host(y), orc.forward(x))
+    np.testing.assert_array_equal(host(adj), orc.adjoint(u, hw))
+    handle = op.hip_handle_for(fkw["mask"])
+    assert not handle.fuses_step(3, *hw) and handle.fuses_step(3, 64, 64)
+    _, ck = coefs_of(K, oracle, 500)
+    buf = K.StepBuffers(handle, n, 3, *hw, DEV)
+    mo, z = dev(rng.randn(n, 6, *hw).astype(np.float32)), dev(rng.randn(n, 3, *hw).astype(np.float32))
+    with pytest.raises(K._lib.DpsxError) as e:
+        K.step_fwd(handle, buf, dev(x), mo, z, y.detach().contiguous()[:1], ck)
+    assert e.value.code == K._lib.EUNSUPPORTED
+    with pytest.raises(K._lib.DpsxError) as e:
+        K.step_bwd(handle, buf, y.detach().contiguous()[:1], 0.5, 1, ck)
+    assert e.value.code == K._lib.EUNSUPPORTED
+
+
+def test_inpainting_off_grid_loop_takes_the_per_op_path(K):
+    """`ps` on a 63 x 63 mask: _fusion_plan answers None from the shape, before the first step, and the loop runs per op.
+    Base loop: sampler.particle_groups = 2 changes nothing (no plan, no groups: same bits); a multi-image batch, which
+    only the fused step serves, is refused up front.  ttc_ddim (whose per-op unpacking fits a foreign `ps` callable): the
+    bound method and the foreign callable now take the same route, bit for bit."""
+    import functools
+    from dps_ttc_amd.condition_methods import get_conditioning_method
+    from dps_ttc_amd.measurements import get_noise
+    hw, n = 63, 3
+    gen = torch.Generator(device=DEV).manual_seed(63)
+    mask = dev((np.random.RandomState(7).rand(1, 1, hw, hw) < 0.5).astype(np.float32))
+    op, _ = make_product_op("inpaint", mask=host(mask))
+    cm = get_conditioning_method("ps", op, get_noise("gaussian", sigma=0.05), scale=0.5)
+    bound = functools.partial(cm.conditioning, mask=mask)
+    x_start = torch.randn(n, 3, hw, hw, device=DEV, generator=gen)
+    y = op.forward(torch.rand(1, 3, hw, hw, device=DEV, generator=gen) * 2 - 1, mask=mask).detach().contiguous()
+    model = StandInModel().to(DEV)
+    res = []
+    for groups in (1, 2):
+        smp = _sampler("ddpm", "20")
+        smp.particle_groups = groups
+        assert smp._fusion_plan(bound, x_start) is None
+        torch.manual_seed(7)
+        img, dist, _ = smp.p_sample_loop(model=model, x_start=x_start.clone().requires_grad_(), measurement=y,
+                                         measurement_cond_fn=bound, record=False, save_root=None)
+        assert smp._pgroups is None and smp._bufs is None
+        res.append((img, dist))
+        with pytest.raises(NotImplementedError, match="multi-image"):
+            smp.p_sample_loop(model=model, x_start=torch.cat([x_start, x_start[:1]]).requires_grad_(),
+                              measurement=torch.cat([y, y]), measurement_cond_fn=bound, record=False, save_root=None)
+    assert bool(torch.isfinite(res[0][0]).all()) and bool((res[0][1] > 0).all())
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    res = []
+    for cond in (bound, lambda **kw: cm.conditioning(**kw, mask=mask)):
+        smp = _sampler("ttc_ddim", "20")
+        assert smp._fusion_plan(cond, x_start) is None
+        torch.manual_seed(7)
+        img, dist = smp.p_sample_loop(model=model, x_start=x_start.clone().requires_grad_(), measurement=y,
+                                      measurement_cond_fn=cond, record=False, save_root=None)
+        assert smp._bufs is None
+        res.append((img, dist, smp.last_resample_ids))
+    assert bool(torch.isfinite(res[0][0]).all()) and bool((res[0][1] > 0).all())
+    assert all(torch.equal(u, v) for u, v in zip(res[0], res[1]))
+    # the same mask family on the float4 grid keeps its plan
+    mask64 = dev((np.random.RandomState(7).rand(1, 1, 64, 64) < 0.5).astype(np.float32))
+    assert _sampler("ddpm", "20")._fusion_plan(functools.partial(cm.conditioning, mask=mask64),
+                                               torch.zeros(n, 3, 64, 64, device=DEV)) is not None
+
+
+@pytest.mark.parametrize("name,hw", [("gauss", 47), ("motion", 47), ("denoise", 47), ("phase", 34)])
+def test_particle_groups_on_unaligned_slices_match_one_chain(K, oracle, name, hw):
+    """kernels.ParticleGroups hands group j a slice of one full-batch buffer set: with C H W = 3 x 47 x 47 = 6627 floats the
+    second group's sample / x0_hat / g_model_out / x_next start 8 or 12 bytes past a 16-byte boundary and its clamp gate at
+    an odd byte: the scalar kernels on slices.  (A slice is unaligned only where C H W is no multiple of 4, where the size
+    test alone already picks the scalar kernel, so this does not show that a launcher also tests its pointers.)  34 x 34
+    phase retrieval is the scalar staging + un-fused backward on slices.  Per-particle results equal one chain bit for bit."""
+    n, steps = 3, 3
+    gen = torch.Generator(device=DEV).manual_seed(hw)
+    mk = lambda *shape: torch.randn(*shape, device=DEV, generator=gen)
+    op, fkw = make_product_op(name, hw=hw, kernel=synthetic_motion_kernel(61, 5))
+    x_t = mk(n, 3, hw, hw)
+    ring = [dict(model_out=mk(n, 6, hw, hw) * 0.4, noise=mk(n, 3, hw, hw), g_unet=mk(n, 3, hw, hw) * 1e-2)
+            for _ in range(steps)]
+    y = op.forward(torch.rand(1, 3, hw, hw, device=DEV, generator=gen) * 2 - 1, **fkw).detach().contiguous()
+    cks = [coefs_of(K, oracle, t)[1] for t in (900, 400, 0)]
+    handle = op.hip_handle(x_t)
+    buf = K.StepBuffers(handle, n, 3, hw, hw, DEV)
+    x = x_t
+    for s, ck in zip(ring, cks):
+        K.step_fwd(handle, buf, x, s["model_out"], s["noise"], y, ck)
+        K.step_bwd(handle, buf, y, 0.3, 1, ck)
+        x = K.step_update(buf, s["g_unet"], ck)
+    ref, ref_norm, ref_x0 = x.clone(), buf.norm.clone(), buf.x0_hat.clone()
+    assert bool(torch.isfinite(ref).all()) and bool((ref_norm > 0).all())
+    for groups in (2, 3):
+        pg = K.ParticleGroups(op, n, 3, hw, hw, torch.device(DEV), groups, like=x_t)
+        assert sum(pg.sizes) == n and len(pg) == groups
+        if (3 * hw * hw) % 4:
+            assert any(b.sample.data_ptr() % 16 for b in pg.bufs) and any(b.inside.data_ptr() % 4 for b in pg.bufs)
+        pg.fork()
+        xs = [x_t[sl] for sl in pg.slices]
+        for s, ck in zip(ring, cks):
+            for j in range(len(pg)):
+                pg.step_fwd(j, xs[j], s["model_out"], s["noise"], y, ck)
+                pg.step_bwd(j, y, 0.3, 1, ck)
+                xs[j] = pg.step_update(j, s["g_unet"], ck)
+        pg.join()
+        torch.cuda.synchronize()
+        assert torch.equal(pg.x_next(), ref), groups
+        assert torch.equal(pg.full.norm, ref_norm) and torch.equal(pg.full.x0_hat, ref_x0), groups

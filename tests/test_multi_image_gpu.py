@@ -46,6 +46,8 @@ def _operator(name, hw, M, seed=0):
         return get_operator("inpainting", device=DEV), torch.from_numpy(masks).to(DEV)
     if name == "phase":
         return get_operator("phase_retrieval", oversample=2.0, device=DEV), None
+    if name == "denoise":
+        return get_operator("noise", device=DEV), None
     raise KeyError(name)
 
 
@@ -63,7 +65,7 @@ def _measurements(op, masks, M, hw, gen):
 
 # ----------------------------------------------------------------- the fused step
 @pytest.mark.parametrize("name,hw", [("gauss", 64), ("motion", 64), ("sr4", 64), ("sr8", 64), ("inpaint", 64),
-                                     ("phase", 64), ("phase", 256)])
+                                     ("phase", 64), ("phase", 256), ("denoise", 17)])
 @pytest.mark.parametrize("k", [4, 5])
 def test_fused_step_multi_image_equals_per_image(K, name, hw, k):
     M = 3
@@ -108,7 +110,7 @@ def test_mask_n_must_divide_the_batch(K):
 
 
 # ----------------------------------------------------------------- per-op paths
-@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint", "phase"])
+@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint", "phase", "denoise"])
 def test_per_op_paths_multi_image(K, name):
     M, k, hw = 3, 4, 64
     n = M * k
@@ -144,7 +146,7 @@ def test_per_op_paths_multi_image(K, name):
 
 
 # ----------------------------------------------------------------- segmented search steps
-@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint"])
+@pytest.mark.parametrize("name", ["gauss", "sr4", "inpaint", "denoise"])
 def test_search_steps_segmented(K, name):
     M, k, hw = 3, 4, 64
     n = M * k

@@ -268,7 +268,7 @@ def test_resample_update_golden(oracle, golden, tag, opname, cfg):
     assert list(g["gauss.flat.ids"]) == list(range(6))
 
 
-@pytest.mark.parametrize("name", ["gaussian_blur", "super_resolution", "inpainting", "phase_retrieval"])
+@pytest.mark.parametrize("name", ["gaussian_blur", "super_resolution", "inpainting", "phase_retrieval", "noise"])
 def test_torch_ops_reference_agrees_with_the_port(oracle, name):
     """oracle/torch_ref.py (the reference's ATen ops, bench.py's second CPU baseline) against the C port on one `ps` step"""
     from oracle import torch_ref
@@ -282,10 +282,10 @@ def test_torch_ops_reference_agrees_with_the_port(oracle, name):
     gu = (1e-2 * rng.randn(n, 3, hw, hw)).astype(np.float32)
     mask = (rng.rand(1, 1, hw, hw) < 0.5).astype(np.float32)
     cfg = {"gaussian_blur": dict(kernel_size=61, intensity=3.0), "super_resolution": dict(in_shape=(1, 3, hw, hw), scale_factor=4),
-           "inpainting": dict(mask=mask), "phase_retrieval": dict(oversample=2.0)}[name]
+           "inpainting": dict(mask=mask), "phase_retrieval": dict(oversample=2.0), "noise": {}}[name]
     orc = oracle.make_operator(name, **cfg)
     tkw = {"gaussian_blur": dict(kernel=orc.kw.get("kernel")), "super_resolution": dict(tables=orc.kw.get("tables")),
-           "inpainting": dict(mask=mask), "phase_retrieval": dict(pad=64)}[name]
+           "inpainting": dict(mask=mask), "phase_retrieval": dict(pad=64), "noise": {}}[name]
     y = orc.forward(rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32))
     y = (y + 0.05 * rng.randn(*y.shape)).astype(np.float32)
     ref = oracle.dps_step(orc, x, mo, z, y, c, scale=0.3, power=1, g_unet_fn=lambda g: gu)
