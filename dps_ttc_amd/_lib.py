@@ -5,7 +5,7 @@ point.  If the shared object is missing or a call fails, this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPSX_LIB: development aid to A/B an experimental build of the same library (tools/abl.sh)
@@ -22,6 +22,12 @@ class Coefs(ctypes.Structure):
     """struct dpsx_coefs"""
     _fields_ = [("a", c_float), ("b", c_float), ("c1", c_float), ("c2", c_float),
                 ("min_log", c_float), ("max_log", c_float), ("add_noise", c_int32)]
+
+
+class RngRec(ctypes.Structure):
+    """struct dpsx_rng"""
+    _fields_ = [("seed", c_uint64), ("step", c_uint32), ("tag", c_uint32), ("particle_base", c_int64),
+                ("per_image", c_int64)]
 
 
 class DpsxError(RuntimeError):
@@ -85,6 +91,15 @@ SIGNATURES = {
     "dpsx_replicate_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
     "dpsx_resample_draw_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _p, _p, _p]),
     "dpsx_resample_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _f, _f, _f, _p, _p, _i64, _i64, _p]),
+    "dpsx_randn_f32": (c_int, [_f, _p, _i64, _i64, POINTER(RngRec), _p]),
+    "dpsx_posterior_fwd_rng_f32": (c_int, [_f, _f, POINTER(RngRec), _f, _f, _p, _i64, _i64, POINTER(Coefs), _p]),
+    "dpsx_step_draws_in_kernel": (c_int, [c_void_p, _i64, _i64, _i64]),
+    "dpsx_step_fwd_rng_f32": (c_int, [c_void_p, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _p, _f,
+                                      _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_search_step_seg_rng_f32": (c_int, [c_void_p, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _f, _f, _i64,
+                                             _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_search_step_one_seg_rng_f32": (c_int, [c_void_p, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _f, _f, _i64,
+                                                 _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

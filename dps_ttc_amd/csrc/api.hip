@@ -63,6 +63,44 @@ int dpsx_posterior_bwd_f32(const float *g_x0, const float *g_sample, const float
                          (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ counter-based normals
+// dpsx_rng -> the launch record; every particle id of the n rows must fit 32 bits
+static int to_rngk(const dpsx_rng *r, int64_t n, RngK &o)
+{
+    if (!r || r->particle_base < 0 || r->per_image < 0) return DPSX_EINVAL;
+    const int64_t rows = std::max<int64_t>(n, 1);
+    const int64_t per = (r->per_image > 0 && r->per_image < rows) ? r->per_image : 0;   // per >= n: p % per == p
+    if (r->particle_base + (per ? per : rows) - 1 > 0xffffffffll) return DPSX_EINVAL;
+    o = RngK{(uint32_t)(r->seed & 0xffffffffu), (uint32_t)(r->seed >> 32), r->step, r->tag,
+             (uint32_t)r->particle_base, (uint32_t)per};
+    return DPSX_OK;
+}
+
+int dpsx_randn_f32(float *out, uint32_t *bits_out, int64_t n, int64_t chw, const dpsx_rng *rng_host, void *stream)
+{
+    if (n < 0 || chw < 0 || n > 65535) return DPSX_EINVAL;
+    RngK r;
+    int rc = to_rngk(rng_host, n, r);
+    if (rc != DPSX_OK) return rc;
+    if (n == 0 || chw == 0) return DPSX_OK;
+    if (!out) return DPSX_EINVAL;
+    return randn_f32(out, bits_out, n, chw, r, (hipStream_t)stream);
+}
+
+int dpsx_posterior_fwd_rng_f32(const float *x_t, const float *model_out, const dpsx_rng *rng_host, float *x0_hat,
+                               float *sample, uint8_t *inside, int64_t n, int64_t chw,
+                               const dpsx_coefs *coefs_host, void *stream)
+{
+    if (!coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
+    RngK r;
+    int rc = to_rngk(rng_host, n, r);
+    if (rc != DPSX_OK) return rc;
+    if (n == 0 || chw == 0) return DPSX_OK;
+    if (!x_t || !model_out) return DPSX_EINVAL;
+    return posterior_fwd_rng(x_t, model_out, r, x0_hat, sample, inside, n, chw, to_coefs(coefs_host),
+                             (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------ operator objects
 // arrival counters of the in-launch reductions (common.h: Tail); zero between launches
 static int alloc_counters(dpsx_op *op)
@@ -500,13 +538,33 @@ static bool mask_fused_ok(const dpsx_op *op, int64_t c, int64_t h, int64_t w,
     return true;
 }
 
-int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
-                      int64_t y_n, float *x0_hat, float *sample, uint8_t *inside, void *resid, float *norm,
-                      int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host, void *workspace,
-                      int64_t workspace_bytes, void *stream)
+int dpsx_step_draws_in_kernel(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
+{
+    if (!op || c < 1 || h < 1 || w < 1) return 0;
+    switch (op->kind) {
+    case OP_IDENT: return 1;
+    case OP_MASK: return (h * w) % 4 == 0 && (c * h * w) % 4 == 0;
+    case OP_SEP:
+    case OP_TAPS: return blur_step_draws_in_kernel(op, h, w) ? 1 : 0;
+    case OP_RESIZE: return h == op->in_h && w == op->in_w && resize_step_draws_in_kernel(op) ? 1 : 0;
+    default: return 0;       // phase retrieval: fill + pointer form
+    }
+}
+
+// rng != NULL: the noise is drawn inside the launch (noise is then NULL).  Routes without an in-kernel draw decline
+// before anything is launched.
+static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const dpsx_rng *rng,
+                         const float *y, int64_t y_n, float *x0_hat, float *sample, uint8_t *inside, void *resid,
+                         float *norm, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                         void *workspace, int64_t workspace_bytes, void *stream)
 {
     int rc = check_geom(op, n, c, h, w);
     if (rc != DPSX_OK) return rc;
+    RngK rk{};
+    if (rng) {
+        if ((rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
+        if (!dpsx_step_draws_in_kernel(op, c, h, w)) return DPSX_EUNSUPPORTED;
+    }
     if (!x_t || !model_out || !y || !sample || !inside || !resid || !coefs_host) return DPSX_EINVAL;
     // x0_hat is an optional OUTPUT where the launch consumes it on the fly (blur, resize): the `ps` loop reads it nowhere
     // after this call (the backward half works from the clamp gate), so a caller that does not need the image saves its
@@ -515,7 +573,7 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
     if (!x0_hat && op && op->kind != OP_SEP && op->kind != OP_TAPS && op->kind != OP_RESIZE &&
         !(op->kind == OP_PHASE && phase_is_spectral(op)))
         return DPSX_EINVAL;
-    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
+    if ((coefs_host->add_noise & 1) && !noise && !rng) return DPSX_EINVAL;
     if (!rows_ok(y_n, n)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
     Ws ws;
@@ -527,6 +585,8 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
                   ws.partials, n, c, h, w, k};
     a.y_div = row_div(y_n, n);
     a.mask_div = row_div(op->mask_n, n);
+    a.use_rng = rng != nullptr;
+    a.rng = rk;
     int parts = (int)parts_per_particle(op, c, h, w);
     // norm != NULL: the launch itself finishes the per-particle reduction (each particle's last block re-sums its
     // partials in the order of k_finalize_norm -- bit-identical, no extra launch)
@@ -554,7 +614,8 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
         rc = mask_step_fwd(op, a, parts, s);
         break;
     case OP_IDENT:
-        rc = posterior_fwd(x_t, model_out, noise, x0_hat, sample, inside, n, chw, k, s);
+        rc = rng ? posterior_fwd_rng(x_t, model_out, rk, x0_hat, sample, inside, n, chw, k, s)
+                 : posterior_fwd(x_t, model_out, noise, x0_hat, sample, inside, n, chw, k, s);
         if (rc != DPSX_OK) return rc;
         parts = 64;
         rc = residual_partials(y, y_n, x0_hat, static_cast<float *>(resid), ws.partials, n, chw, parts, s, 0, a.tail);
@@ -573,6 +634,25 @@ int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, con
     }
     // norm == NULL: the partial sums stay in `workspace` and dpsx_step_bwd_f32 finalises them in its prologue
     return (norm && !tail_done) ? finalize_norm(ws.partials, parts, norm, n, s) : DPSX_OK;
+}
+
+int dpsx_step_fwd_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+                      int64_t y_n, float *x0_hat, float *sample, uint8_t *inside, void *resid, float *norm,
+                      int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host, void *workspace,
+                      int64_t workspace_bytes, void *stream)
+{
+    return step_fwd_impl(op, x_t, model_out, noise, nullptr, y, y_n, x0_hat, sample, inside, resid, norm, n, c, h, w,
+                         coefs_host, workspace, workspace_bytes, stream);
+}
+
+int dpsx_step_fwd_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                          const float *y, int64_t y_n, float *x0_hat, float *sample, uint8_t *inside, void *resid,
+                          float *norm, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                          void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!rng_host) return DPSX_EINVAL;
+    return step_fwd_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, x0_hat, sample, inside, resid, norm, n, c, h, w,
+                         coefs_host, workspace, workspace_bytes, stream);
 }
 
 int dpsx_step_bwd_f32(dpsx_op *op, const void *resid, const float *norm, float *norm_out, const uint8_t *inside,
@@ -788,7 +868,7 @@ int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_o
 
 // ------------------------------------------------------------------ multi-image search (segments of n / segments particles)
 // The argument checks of both segmented steps; y holds one row (broadcast) or one per segment.
-static int search_seg_args(const dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+static int search_seg_args(const dpsx_op *op, const float *x_t, const float *model_out, const void *noise, const float *y,
                            int64_t y_n, const float *sample, const float *costs, const int64_t *best_idx_dev,
                            const float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
                            const dpsx_coefs *coefs_host)
@@ -802,14 +882,17 @@ static int search_seg_args(const dpsx_op *op, const float *x_t, const float *mod
     return DPSX_OK;
 }
 
-int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+static int search_step_seg_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                                const dpsx_rng *rng, const float *y,
                              int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev, float *best_val_dev,
                              float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
                              const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    int rc = search_seg_args(op, x_t, model_out, noise, y, y_n, sample, costs, best_idx_dev, x_next, segments, n, c, h, w,
-                             coefs_host);
+    int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
+                             best_idx_dev, x_next, segments, n, c, h, w, coefs_host);
     if (rc != DPSX_OK) return rc;
+    RngK rk{};
+    if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
     // the launches of dpsx_search_step_f32; the select runs one block per segment and the replication copies each
     // segment's winner over that segment's particles
     Ws ws;
@@ -817,7 +900,8 @@ int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_o
     hipStream_t s = (hipStream_t)stream;
     const int64_t chw = c * h * w;
     const int parts = score_parts(op, c, h, w);
-    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s);
+    rc = rng ? posterior_fwd_rng(x_t, model_out, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s)
+             : posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s);
     if (rc != DPSX_OK) return rc;
     if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
     const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
@@ -826,22 +910,46 @@ int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_o
     return replicate_seg_f32(sample, best_idx_dev, x_next, n, n / segments, n, chw, s);
 }
 
-int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
+                             int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev, float *best_val_dev,
+                             float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
+                             const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return search_step_seg_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev,
+                                x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
+}
+
+int dpsx_search_step_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
                                  const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
                                  float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h,
                                  int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
                                  void *stream)
 {
-    int rc = search_seg_args(op, x_t, model_out, noise, y, y_n, sample, costs, best_idx_dev, x_next, segments, n, c, h, w,
-                             coefs_host);
+    if (!rng_host) return DPSX_EINVAL;
+    return search_step_seg_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev, best_val_dev,
+                                x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
+}
+
+static int search_step_one_seg_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                                    const dpsx_rng *rng,
+                                 const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
+                                 float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h,
+                                 int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
+                                 void *stream)
+{
+    int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
+                             best_idx_dev, x_next, segments, n, c, h, w, coefs_host);
     if (rc != DPSX_OK) return rc;
+    RngK rk{};
+    if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
     // one state per segment: proposal p reads state p / (n / segments); x_next receives each segment's winner once
     Ws ws;
     if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t chw = c * h * w;
     const int parts = score_parts(op, c, h, w);
-    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments);
+    rc = rng ? posterior_fwd_rng(x_t, model_out, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments)
+             : posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments);
     if (rc != DPSX_OK) return rc;
     if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
     const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
@@ -850,6 +958,28 @@ int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *mod
     rc = finalize_select_seg(tail, (int)segments, s);
     if (rc != DPSX_OK || !x_next) return rc;
     return gather_f32(sample, best_idx_dev, x_next, segments, n, chw, false, s);
+}
+
+int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                                 const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
+                                 float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h,
+                                 int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
+                                 void *stream)
+{
+    return search_step_one_seg_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev,
+                                    x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
+}
+
+int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                                     const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
+                                     float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c,
+                                     int64_t h, int64_t w, const dpsx_coefs *coefs_host, void *workspace,
+                                     int64_t workspace_bytes, void *stream)
+{
+    if (!rng_host) return DPSX_EINVAL;
+    return search_step_one_seg_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev,
+                                    best_val_dev, x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes,
+                                    stream);
 }
 
 int dpsx_score_f32(dpsx_op *op, const float *x, const float *y, int64_t y_n, float *costs, int64_t n, int64_t c,

@@ -16,6 +16,7 @@
 //            adjoint the clamp gate and the -b * coef scaling into g_model_out.
 // Blocks are numbered so that the tiles of one plane share blockIdx % 8, i.e.
 // one XCD and its L2 (halo re-reads then hit L2, not HBM).
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
@@ -63,6 +64,9 @@ struct BlurArgs {
     // scoring variants of the residual epilogue (plain input only): sums of |r| instead of r^2; in-launch finalisation
     int l1;
     Tail tail;
+    // in-kernel noise draw of the fused S1 prologue (RNG instantiations; `noise` is then unused).  Last, so that every
+    // other field keeps its kernel-argument offset
+    RngK rng;
 };
 
 __device__ __forceinline__ bool block_to_tile(const BlurArgs &a, int &plane, int &ty, int &tx)
@@ -299,7 +303,8 @@ __device__ __forceinline__ void taps_halo_unit(const TapGeom &g, const int RWu, 
 // -- before anything is consumed: one memory round trip per tile instead of one per 1024 units (round 1: 2-4 serialised
 // round trips per tile, with four co-resident blocks in lockstep).  Halo units beyond NHB x 256 (kernels whose path
 // reaches far on several sides) follow in rounds of four.
-template <bool POST, bool REFLECT, int NHB>
+// RNG (POST only): the noise unit is drawn from a.rng where S1 consumes it instead of loaded up front (common.h: rng_unit).
+template <bool POST, bool REFLECT, int NHB, bool RNG = false>
 __device__ __forceinline__ void load_region_taps_first(float *s_in, const int SW, const int RWu, const TapGeom g,
                                                        const int h0, const int w0, const BlurArgs &a, const int plane)
 {
@@ -349,7 +354,7 @@ __device__ __forceinline__ void load_region_taps_first(float *s_in, const int SW
             const int u = threadIdx.x + k * NT, row = u >> 4, cu = u & 15;
             const unsigned o = (unsigned)((h0 + row) * w + w0 + 4 * cu);
             vi[k] = ld_stream(noisy ? vv + o : g_zero_unit, true);
-            zi[k] = ld_stream(noisy ? zz + o : g_zero_unit, true);
+            if constexpr (!RNG) zi[k] = ld_stream(noisy ? zz + o : g_zero_unit, true);
         }
     }
     __builtin_amdgcn_sched_barrier(0);   // every load above issues before the first use below
@@ -360,7 +365,15 @@ __device__ __forceinline__ void load_region_taps_first(float *s_in, const int SW
         if constexpr (POST) {
             float4 x0, sm;
             uchar4 gate;
-            post_unit(xi[k], ei[k], vi[k], zi[k], a.k, x0, sm, gate);       // packed S1 (common.h)
+            float4 zk = make_float4(0, 0, 0, 0);
+            if constexpr (RNG) {     // the unit's index inside the particle: (channel plane, row, column) / 4
+                if (noisy)
+                    zk = rng_unit(a.rng, ((unsigned)ch * hw + (unsigned)((h0 + row) * w + w0 + 4 * cu)) >> 2,
+                                  rng_particle(a.rng, (unsigned)n));
+            } else {
+                zk = zi[k];
+            }
+            post_unit(xi[k], ei[k], vi[k], zk, a.k, x0, sm, gate);          // packed S1 (common.h)
             const int64_t o = (int64_t)plane * hw + (unsigned)((h0 + row) * w + w0 + 4 * cu);
             if (a.x0_hat) *reinterpret_cast<float4 *>(a.x0_hat + o) = x0;
             *reinterpret_cast<float4 *>(a.sample + o) = sm;
@@ -586,7 +599,8 @@ __device__ __forceinline__ void tap_all_runs(v2f (&acc)[PRW], const float *s_in,
 // latencies (LDS reads and scalar loads share one counter, so a run record's wait drains the window reads too).
 // NHB: halo units per lane the loads-first stage keeps in flight (2: a halo of at most 512 units -- the compact kernels, and
 // 16 fewer live registers, which is what keeps the fused forward's 24 loads free of a spill in their midst; else 4)
-template <bool POST, int MODE, bool VEC, int SWC, int NHB = 4>
+// RNG: K1 with the noise drawn in the kernel; launched for regular geometry only (blur_step_draws_in_kernel)
+template <bool POST, int MODE, bool VEC, int SWC, int NHB = 4, bool RNG = false>
 __global__ __launch_bounds__(NT, 4) void k_blur_taps(BlurArgs a, TapGeom g)
 {
     constexpr bool RESID = MODE == 1, REFLECT = MODE != 2;
@@ -599,7 +613,9 @@ __global__ __launch_bounds__(NT, 4) void k_blur_taps(BlurArgs a, TapGeom g)
     bool regular;
     if constexpr (REFLECT) regular = VEC && a.h % TH == 0 && a.w % TW == 0 && max(g.t, g.b) < a.h && max(g.l, g.r) < a.w;
     else regular = VEC && a.src_w % 4 == 0 && a.src_off % 4 == 0;   // the SOURCE decides whether a unit is wholly in or out
-    if constexpr (VEC) {
+    if constexpr (RNG) {
+        load_region_taps_first<POST, REFLECT, NHB, true>(s_in, SW, RW / 4, g, h0, w0, a, plane);
+    } else if constexpr (VEC) {
         if (regular) load_region_taps_first<POST, REFLECT, NHB>(s_in, SW, RW / 4, g, h0, w0, a, plane);
         else load_region<POST, REFLECT, VEC>(s_in, SW, RH, RW, h0 - g.t, w0 - g.l, h0, w0, a, plane);
     } else {
@@ -1249,25 +1265,25 @@ static int allow_lds(K kernel, size_t bytes, bool &done)
         return check_launch();                                            \
     } while (0)
 
-template <int R4, bool POST, bool RESID>
+template <int R4, bool POST, bool RESID, bool RNG = false>
 static int launch_sep_fwd(const BlurArgs &a, const SepTaps &t, hipStream_t s)
 {
     const size_t lds = sep_lds_bytes(4 * R4);
-    DPSX_LAUNCH((k_blur_sep_fwd<R4, POST, RESID>), grid_blocks(a), lds, s, a, t);
+    DPSX_LAUNCH((k_blur_sep_fwd<R4, POST, RESID, RNG>), grid_blocks(a), lds, s, a, t);
 }
 
-template <bool POST, bool RESID>
+template <bool POST, bool RESID, bool RNG = false>
 static int dispatch_sep_fwd(const dpsx_op *op, const BlurArgs &a, hipStream_t s)
 {
     switch (op->radius4 / 4) {
-    case 1: return launch_sep_fwd<1, POST, RESID>(a, op->sep, s);
-    case 2: return launch_sep_fwd<2, POST, RESID>(a, op->sep, s);
-    case 3: return launch_sep_fwd<3, POST, RESID>(a, op->sep, s);
-    case 4: return launch_sep_fwd<4, POST, RESID>(a, op->sep, s);
-    case 5: return launch_sep_fwd<5, POST, RESID>(a, op->sep, s);
-    case 6: return launch_sep_fwd<6, POST, RESID>(a, op->sep, s);
-    case 7: return launch_sep_fwd<7, POST, RESID>(a, op->sep, s);
-    case 8: return launch_sep_fwd<8, POST, RESID>(a, op->sep, s);
+    case 1: return launch_sep_fwd<1, POST, RESID, RNG>(a, op->sep, s);
+    case 2: return launch_sep_fwd<2, POST, RESID, RNG>(a, op->sep, s);
+    case 3: return launch_sep_fwd<3, POST, RESID, RNG>(a, op->sep, s);
+    case 4: return launch_sep_fwd<4, POST, RESID, RNG>(a, op->sep, s);
+    case 5: return launch_sep_fwd<5, POST, RESID, RNG>(a, op->sep, s);
+    case 6: return launch_sep_fwd<6, POST, RESID, RNG>(a, op->sep, s);
+    case 7: return launch_sep_fwd<7, POST, RESID, RNG>(a, op->sep, s);
+    case 8: return launch_sep_fwd<8, POST, RESID, RNG>(a, op->sep, s);
     }
     return DPSX_EUNSUPPORTED;
 }
@@ -1369,21 +1385,21 @@ static TapGeom make_geom(int t, int b, int l, int r)
     return g;
 }
 
-template <bool POST, int MODE, bool VEC, int SWC, int NHB>
+template <bool POST, int MODE, bool VEC, int SWC, int NHB, bool RNG = false>
 static int launch_taps_kn(const BlurArgs &a, const TapGeom &g, hipStream_t s)
 {
     const size_t lds = taps_lds(g, SWC);
-    DPSX_LAUNCH((k_blur_taps<POST, MODE, VEC, SWC, NHB>), grid_blocks(a), lds, s, a, g);
+    DPSX_LAUNCH((k_blur_taps<POST, MODE, VEC, SWC, NHB, RNG>), grid_blocks(a), lds, s, a, g);
 }
 
-template <bool POST, int MODE, bool VEC, int SWC>
+template <bool POST, int MODE, bool VEC, int SWC, bool RNG = false>
 static int launch_taps_k(const BlurArgs &a, const TapGeom &g, hipStream_t s)
 {
     if constexpr (VEC && POST) {
         const int halo_units = (g.t + g.b) * ((TW + g.l + g.r) / 4) + TH * ((g.l + g.r) / 4);
-        if (halo_units <= 2 * NT) return launch_taps_kn<POST, MODE, VEC, SWC, 2>(a, g, s);
+        if (halo_units <= 2 * NT) return launch_taps_kn<POST, MODE, VEC, SWC, 2, RNG>(a, g, s);
     }
-    return launch_taps_kn<POST, MODE, VEC, SWC, 4>(a, g, s);
+    return launch_taps_kn<POST, MODE, VEC, SWC, 4, RNG>(a, g, s);
 }
 
 template <bool POST, int MODE>
@@ -1400,6 +1416,15 @@ static int launch_taps_fwd(const dpsx_op *op, BlurArgs a, bool vec, hipStream_t 
     set_taps(op, a);
     const TapGeom g = make_geom(op->halo_t, op->halo_b, op->halo_l, op->halo_r);
     return launch_taps<POST, RESID ? 1 : 0>(a, g, vec, s);
+}
+
+// K1 of the tap list with the noise drawn in the kernel: 16-byte path on regular geometry only (the caller checked)
+static int launch_taps_fwd_rng(const dpsx_op *op, BlurArgs a, hipStream_t s)
+{
+    set_taps(op, a);
+    const TapGeom g = make_geom(op->halo_t, op->halo_b, op->halo_l, op->halo_r);
+    if (taps_swc(g, true) == kSwNarrow) return launch_taps_k<true, 1, true, kSwNarrow, true>(a, g, s);
+    return launch_taps_k<true, 1, true, kSwWide, true>(a, g, s);
 }
 
 int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h, int64_t w)
@@ -1521,6 +1546,16 @@ int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, in
                                      : launch_taps_adj<false>(op, a, vec, scratch, scratch_bytes, s);
 }
 
+// K1 with the noise drawn in the kernel exists on REGULAR geometry -- whole 64 x 64 tiles, the halo shorter than both
+// sides -- where the loads-first loaders run (load_region_reg, load_region_taps_first): the noise load is local to them.
+// The general loaders decline: the caller fills a noise buffer with the same function and runs the pointer launch.
+bool blur_step_draws_in_kernel(const dpsx_op *op, int64_t h, int64_t w)
+{
+    if (!geometry_ok(op, h, w) || h % TH != 0 || w % TW != 0) return false;
+    if (op->kind == OP_SEP) return op->radius4 < h && op->radius4 < w && op->radius4 / 4 >= 1 && op->radius4 / 4 <= 8;
+    return std::max(op->halo_t, op->halo_b) < h && std::max(op->halo_l, op->halo_r) < w;
+}
+
 int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
 {
     if (!geometry_ok(op, f.h, f.w)) return DPSX_EINVAL;
@@ -1535,6 +1570,11 @@ int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     a.tail.blocks_per_particle = a.c * a.tiles_x * a.tiles_y;
     const bool vec = vec_ok(f.h, f.w, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample, f.y, f.resid}) &&
                      (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
+    if (f.use_rng) {
+        if (!vec || !blur_step_draws_in_kernel(op, f.h, f.w)) return DPSX_EUNSUPPORTED;      // nothing launched
+        a.rng = f.rng;
+        return op->kind == OP_SEP ? dispatch_sep_fwd<true, true, true>(op, a, s) : launch_taps_fwd_rng(op, a, s);
+    }
     return op->kind == OP_SEP && vec ? dispatch_sep_fwd<true, true>(op, a, s) : launch_taps_fwd<true, true>(op, a, vec, s);
 }
 

@@ -287,7 +287,8 @@ __device__ __forceinline__ float4 load_unit_reg(const float *plane, int gy, int 
     else return make_float4(v.x, v.y, v.z, v.w);
 }
 
-template <int RR, bool POST, bool REFLECT>
+// RNG (POST only): the noise unit is drawn from a.rng where S1 consumes it instead of loaded up front (common.h: rng_unit)
+template <int RR, bool POST, bool REFLECT, bool RNG = false>
 __device__ __forceinline__ void load_region_reg(float *s, const int h0, const int w0, const BlurArgs &a,
                                                 const int plane)
 {
@@ -300,7 +301,7 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
         src = a.x_t + (int64_t)plane * hw;
         eps = a.model_out + ((int64_t)n * 2 * a.c + ch) * hw;
         vv = eps + (int64_t)a.c * hw;
-        zz = a.noise + (int64_t)plane * hw;
+        if constexpr (!RNG) zz = a.noise + (int64_t)plane * hw;
     } else {
         src = a.x + (int64_t)plane * hw;
     }
@@ -334,7 +335,7 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
                 const int u = threadIdx.x + k * NT, row = u >> 4, cu = u & 15;
                 const unsigned o = (unsigned)((h0 + row) * w + w0 + 4 * cu);
                 vi[k] = ld_stream(vv + o, true);
-                zi[k] = ld_stream(zz + o, true);
+                if constexpr (!RNG) zi[k] = ld_stream(zz + o, true);
             }
         } else {
 #pragma unroll
@@ -354,10 +355,18 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
             x0.y = post_x0(xi[k].y, ei[k].y, a.k, b1);
             x0.z = post_x0(xi[k].z, ei[k].z, a.k, b2);
             x0.w = post_x0(xi[k].w, ei[k].w, a.k, b3);
-            sm.x = post_sample(xi[k].x, x0.x, vi[k].x, zi[k].x, a.k);
-            sm.y = post_sample(xi[k].y, x0.y, vi[k].y, zi[k].y, a.k);
-            sm.z = post_sample(xi[k].z, x0.z, vi[k].z, zi[k].z, a.k);
-            sm.w = post_sample(xi[k].w, x0.w, vi[k].w, zi[k].w, a.k);
+            float4 zk = make_float4(0, 0, 0, 0);
+            if constexpr (RNG) {     // the unit's index inside the particle: (channel plane, row, column) / 4
+                if (a.k.add_noise & 1)
+                    zk = rng_unit(a.rng, ((unsigned)ch * hw + (unsigned)((h0 + row) * w + w0 + 4 * cu)) >> 2,
+                                  rng_particle(a.rng, (unsigned)n));
+            } else {
+                zk = zi[k];
+            }
+            sm.x = post_sample(xi[k].x, x0.x, vi[k].x, zk.x, a.k);
+            sm.y = post_sample(xi[k].y, x0.y, vi[k].y, zk.y, a.k);
+            sm.z = post_sample(xi[k].z, x0.z, vi[k].z, zk.z, a.k);
+            sm.w = post_sample(xi[k].w, x0.w, vi[k].w, zk.w, a.k);
             const int64_t o = (int64_t)plane * hw + (unsigned)((h0 + row) * w + w0 + 4 * cu);
             if (a.x0_hat) *reinterpret_cast<float4 *>(a.x0_hat + o) = x0;          // launch-uniform: optional output
             *reinterpret_cast<float4 *>(a.sample + o) = sm;
@@ -557,7 +566,8 @@ constexpr int sep_waves_per_simd(int r4, bool light = false)
 }
 constexpr int sep_adj_waves_per_simd(int r4) { return r4 <= 6 ? sep_waves_per_simd(r4) : 1; }
 
-template <int R4, bool POST, bool RESID>
+// RNG: K1 with the noise drawn in the kernel; launched for regular geometry only (blur.hip: blur_step_draws_in_kernel)
+template <int R4, bool POST, bool RESID, bool RNG = false>
 __global__ __launch_bounds__(NT, sep_waves_per_simd(R4, !POST && !RESID)) void k_blur_sep_fwd(BlurArgs a, SepTaps taps)
 {
     constexpr int RR = 4 * R4;
@@ -568,7 +578,8 @@ __global__ __launch_bounds__(NT, sep_waves_per_simd(R4, !POST && !RESID)) void k
     if (!block_to_tile(a, plane, ty, tx)) return;
     const int h0 = ty * TH, w0 = tx * TW;
     const bool regular = a.h % TH == 0 && a.w % TW == 0 && RR < a.h && RR < a.w && !ABL(128);
-    if (regular) load_region_reg<RR, POST, true>(s, h0, w0, a, plane);
+    if constexpr (RNG) load_region_reg<RR, POST, true, true>(s, h0, w0, a, plane);
+    else if (regular) load_region_reg<RR, POST, true>(s, h0, w0, a, plane);
     else if (!ABL(4)) load_region_fast<RR, POST, true>(s, h0, w0, a, plane);
     else for (int i = threadIdx.x; i < G::RH * G::SW; i += NT) s[i] = (float)i;
     const int slot = sep_slot(), cg = slot & 15, rg = slot >> 4;      // one hardware read group = one row group

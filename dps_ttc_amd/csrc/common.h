@@ -140,6 +140,59 @@ __device__ __forceinline__ void post_unit(const float4 &x, const float4 &e, cons
     sm = make_float4(s0.x, s0.y, s1.x, s1.y);
 }
 
+// -------------------------------------------------------------------- counter-based normals (include/dpsx.h: dpsx_rng)
+// Philox4x32-10 keyed on the seed; counter = (float4 unit inside the particle, particle id, step, tag); one call gives
+// the four normals of one unit.  The ONLY implementation: the stand-alone fill and every in-kernel draw call this
+// function, so a counter yields the same bits wherever it is evaluated (no contraction: -ffp-contract=off).
+struct RngK {                  // launch form of dpsx_rng (by-value kernel argument -> SGPRs)
+    uint32_t k0, k1, step, tag;
+    uint32_t base, per;        // particle id of batch row p: base + (per ? p % per : p)
+};
+
+__device__ __forceinline__ uint32_t rng_particle(const RngK &r, unsigned p) { return r.base + (r.per ? p % r.per : p); }
+
+__device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1;
+        c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+// Box-Muller on one word pair: u1 = ((ra >> 8) + 1) 2^-24 in (0, 1], u2 = (rb >> 8) 2^-24 in [0, 1) (both exact in fp32);
+// rad = sqrt(-2 ln u1) from v_log_f32 (log2; u1 >= 2^-24 is normal) and v_sqrt_f32; v_cos_f32 / v_sin_f32 take
+// revolutions, so u2 feeds them as it is.  |z| <= sqrt(48 ln 2) = 5.77; no infinity, no NaN.
+__device__ __forceinline__ void rng_pair(uint32_t ra, uint32_t rb, float &za, float &zb)
+{
+    const float u1 = __fmul_rn((float)((ra >> 8) + 1u), 0x1p-24f), u2 = __fmul_rn((float)(rb >> 8), 0x1p-24f);
+    const float rad = __builtin_amdgcn_sqrtf(__fmul_rn(__builtin_amdgcn_logf(u1), -1.3862943611198906f));   // -2 ln 2
+    za = __fmul_rn(rad, __builtin_amdgcn_cosf(u2));
+    zb = __fmul_rn(rad, __builtin_amdgcn_sinf(u2));
+}
+
+__device__ __forceinline__ float4 rng_unit(const RngK &r, uint32_t unit, uint32_t particle, uint4 *bits = nullptr)
+{
+    const uint4 w = philox4x32_10(unit, particle, r.step, r.tag, r.k0, r.k1);
+    if (bits) *bits = w;
+    float4 z;
+    rng_pair(w.x, w.y, z.x, z.y);
+    rng_pair(w.z, w.w, z.z, z.w);
+    return z;
+}
+
+// element e of a particle (scalar kernels): word e % 4 of unit e / 4
+__device__ __forceinline__ float rng_elem(const RngK &r, int64_t e, uint32_t particle)
+{
+    const float4 z = rng_unit(r, (uint32_t)(e >> 2), particle);
+    const int q = (int)(e & 3);
+    return q == 0 ? z.x : (q == 1 ? z.y : (q == 2 ? z.z : z.w));
+}
+
 // -------------------------------------------------------------------- reductions
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -448,6 +501,8 @@ struct StepFwdArgs {
     Coefs k;
     Tail tail{};      // per-particle finalisation inside the launch (tail.counters == nullptr: not requested / not supported)
     unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
+    bool use_rng = false;               // draw the noise in the kernel from `rng` (noise is then null)
+    RngK rng{};
 };
 
 struct StepBwdArgs {
@@ -473,6 +528,7 @@ int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, in
                  int64_t scratch_bytes, hipStream_t s);
 int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h, int64_t w);
 int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &a, hipStream_t s);
+bool blur_step_draws_in_kernel(const dpsx_op *op, int64_t h, int64_t w);   // blur_step_fwd takes StepFwdArgs::use_rng
 int blur_step_bwd(const dpsx_op *op, const StepBwdArgs &a, float *scratch, int64_t scratch_bytes, hipStream_t s);
 // l1: partials are sums of |r| instead of r^2;  tail: finish the reduction inside the launch (see Tail)
 int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials,
@@ -487,6 +543,7 @@ int64_t resize_parts_per_particle(const dpsx_op *op, int64_t c);
 int resize_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, hipStream_t s);
 int resize_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, hipStream_t s);
 int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &a, hipStream_t s);
+bool resize_step_draws_in_kernel(const dpsx_op *op);                        // resize_step_fwd takes StepFwdArgs::use_rng
 int resize_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s);
 int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials,
                  int64_t n, int64_t c, int l1, const Tail &tail, hipStream_t s);
@@ -496,6 +553,11 @@ int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n,
 // (z, x0, sample, inside stay per particle)
 int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, float *sample, uint8_t *inside,
                   int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false, int64_t states = 1);
+// the same launch with the noise drawn in the kernel (common.h: rng_unit)
+int posterior_fwd_rng(const float *x, const float *mo, const RngK &r, float *x0, float *sample, uint8_t *inside,
+                      int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false, int64_t states = 1);
+// out [n, chw] normals of the counters (unit, particle id of row p, r.step, r.tag); bits (nullable) [n, 4 ceil(chw / 4)]
+int randn_f32(float *out, uint32_t *bits, int64_t n, int64_t chw, const RngK &r, hipStream_t s);
 int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const float *mo, const float *z,
                   float *g_x, float *g_mo, int64_t n, int64_t chw, const Coefs &k, hipStream_t s);
 // mask [mask_n, hw]: plane q (of n * c) uses mask meas_row(q / c, mask_div), mask_div = row_div(mask_n, n)

@@ -20,10 +20,12 @@ static inline dim3 grid_for(int64_t work_per_particle, int64_t n)
 }
 
 // ===================================================================== S1 forward
-template <bool VEC>
+// RNG: the noise is drawn in the kernel (common.h: rng_unit) where S1 consumes it; `z` is then the RngK record instead of
+// the pointer, so the pointer instantiations keep their signature and their code
+template <bool VEC, bool RNG = false>
 __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restrict__ x,
                                                             const float *__restrict__ mo,
-                                                            const float *__restrict__ z,
+                                                            const std::conditional_t<RNG, RngK, const float *__restrict__> z,
                                                             float *__restrict__ x0o, float *__restrict__ so,
                                                             uint8_t *__restrict__ ins, int64_t chw, Coefs k,
                                                             unsigned sdiv)
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
         float4 vv = make_float4(0, 0, 0, 0), zv = vv;
         if (k.add_noise & 1) {
             vv = *reinterpret_cast<const float4 *>(vp);
-            zv = *reinterpret_cast<const float4 *>(z + o);
+            if constexpr (!RNG) zv = *reinterpret_cast<const float4 *>(z + o);
         }
         bool b0, b1, b2, b3;
         float4 x0, sm;
@@ -50,6 +52,8 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
         x0.y = post_x0(xv.y, ev.y, k, b1);
         x0.z = post_x0(xv.z, ev.z, k, b2);
         x0.w = post_x0(xv.w, ev.w, k, b3);
+        if constexpr (RNG)
+            if (k.add_noise & 1) zv = rng_unit(z, (uint32_t)(i >> 2), rng_particle(z, (unsigned)p));
         sm.x = post_sample(xv.x, x0.x, vv.x, zv.x, k);
         sm.y = post_sample(xv.y, x0.y, vv.y, zv.y, k);
         sm.z = post_sample(xv.z, x0.z, vv.z, zv.z, k);
@@ -60,7 +64,12 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
     } else {
         bool b;
         float x0 = post_x0(*xp, *ep, k, b);
-        float sm = post_sample(*xp, x0, (k.add_noise & 1) ? *vp : 0.f, (k.add_noise & 1) ? z[o] : 0.f, k);
+        float zs = 0.f;
+        if (k.add_noise & 1) {
+            if constexpr (RNG) zs = rng_elem(z, i, rng_particle(z, (unsigned)p));
+            else zs = z[o];
+        }
+        float sm = post_sample(*xp, x0, (k.add_noise & 1) ? *vp : 0.f, zs, k);
         if (x0o) x0o[o] = x0;
         if (so) so[o] = sm;
         if (ins) ins[o] = b;
@@ -78,6 +87,56 @@ int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, fl
         k_posterior_fwd<true><<<grid_for(chw / 4, n), kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
     else
         k_posterior_fwd<false><<<grid_for(chw, n), kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
+    return check_launch();
+}
+
+int posterior_fwd_rng(const float *x, const float *mo, const RngK &r, float *x0, float *sample, uint8_t *inside,
+                      int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state, int64_t states)
+{
+    if (n == 0 || chw == 0) return DPSX_OK;
+    const unsigned xs = one_state ? row_div(states, n) : 1u;
+    const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && aligned16(x0) && aligned16(sample) &&
+                     (reinterpret_cast<uintptr_t>(inside) & 3u) == 0;
+    if (vec)
+        k_posterior_fwd<true, true><<<grid_for(chw / 4, n), kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
+    else
+        k_posterior_fwd<false, true><<<grid_for(chw, n), kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
+    return check_launch();
+}
+
+// ===================================================================== stand-alone normal fill
+// out [n, chw]: one float4 unit per lane (the last unit of a particle with chw % 4 != 0 is cut); bits (nullable)
+// [n, 4 * units] receives the four Philox words of every unit
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_randn(float *__restrict__ out, uint32_t *__restrict__ bits, int64_t chw,
+                                                    int64_t units, RngK r)
+{
+    const int64_t p = blockIdx.y;
+    const int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (u >= units) return;
+    uint4 w;
+    const float4 z = rng_unit(r, (uint32_t)u, rng_particle(r, (unsigned)p), &w);
+    const int64_t i = 4 * u, o = p * chw + i;
+    if constexpr (VEC) {
+        *reinterpret_cast<float4 *>(out + o) = z;
+    } else {
+        out[o] = z.x;
+        if (i + 1 < chw) out[o + 1] = z.y;
+        if (i + 2 < chw) out[o + 2] = z.z;
+        if (i + 3 < chw) out[o + 3] = z.w;
+    }
+    if (bits) {
+        uint32_t *b = bits + (p * units + u) * 4;
+        b[0] = w.x; b[1] = w.y; b[2] = w.z; b[3] = w.w;
+    }
+}
+
+int randn_f32(float *out, uint32_t *bits, int64_t n, int64_t chw, const RngK &r, hipStream_t s)
+{
+    if (n == 0 || chw == 0) return DPSX_OK;
+    const int64_t units = (chw + 3) / 4;
+    if (chw % 4 == 0 && aligned16(out)) k_randn<true><<<grid_for(units, n), kThreads, 0, s>>>(out, bits, chw, units, r);
+    else k_randn<false><<<grid_for(units, n), kThreads, 0, s>>>(out, bits, chw, units, r);
     return check_launch();
 }
 
@@ -508,6 +567,7 @@ __device__ __forceinline__ int64_t mask_index(int64_t i, int64_t chw, int64_t hw
 
 // ===================================================================== inpainting fused step
 // fwd: S1 + r = y - mask*x0 (not stored) + norm partials.   bwd: recompute r from x0_hat.
+template <bool RNG>       // the noise drawn in the kernel from a.rng (common.h: rng_unit) instead of read from a.noise
 __global__ __launch_bounds__(kThreads) void k_mask_step_fwd(StepFwdArgs a, const float *__restrict__ mask,
                                                             int64_t chw, int64_t hw)
 {
@@ -523,7 +583,7 @@ __global__ __launch_bounds__(kThreads) void k_mask_step_fwd(StepFwdArgs a, const
         float4 vv = make_float4(0, 0, 0, 0), zv = vv;
         if (a.k.add_noise & 1) {
             vv = *reinterpret_cast<const float4 *>(a.model_out + e + chw);
-            zv = *reinterpret_cast<const float4 *>(a.noise + o);
+            if constexpr (!RNG) zv = *reinterpret_cast<const float4 *>(a.noise + o);
         }
         const float4 mv = *reinterpret_cast<const float4 *>(mask + (int64_t)meas_row((unsigned)p, a.mask_div) * hw +
                                                             mask_index(i, chw, hw));
@@ -534,6 +594,8 @@ __global__ __launch_bounds__(kThreads) void k_mask_step_fwd(StepFwdArgs a, const
         x0.y = post_x0(xv.y, ev.y, a.k, b1);
         x0.z = post_x0(xv.z, ev.z, a.k, b2);
         x0.w = post_x0(xv.w, ev.w, a.k, b3);
+        if constexpr (RNG)
+            if (a.k.add_noise & 1) zv = rng_unit(a.rng, (uint32_t)(i >> 2), rng_particle(a.rng, (unsigned)p));
         sm.x = post_sample(xv.x, x0.x, vv.x, zv.x, a.k);
         sm.y = post_sample(xv.y, x0.y, vv.y, zv.y, a.k);
         sm.z = post_sample(xv.z, x0.z, vv.z, zv.z, a.k);
@@ -555,7 +617,8 @@ int mask_step_fwd(const dpsx_op *op, const StepFwdArgs &f, int parts, hipStream_
     const int64_t chw = f.c * f.h * f.w;
     StepFwdArgs a = f;
     a.tail.blocks_per_particle = parts;
-    k_mask_step_fwd<<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
+    if (a.use_rng) k_mask_step_fwd<true><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
+    else k_mask_step_fwd<false><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
     return check_launch();
 }
 

@@ -80,6 +80,8 @@ struct ResizeArgs {
     Coefs k;
     int l1;                   // scoring (plain input): partials are sums of |r|
     Tail tail;                // in-launch finalisation of the per-particle reduction (common.h)
+    RngK rng;                 // in-kernel noise draw of the fused S1 (RNG instantiation; `noise` is then unused).  Last, so
+                              // that every other field keeps its kernel-argument offset
 };
 
 __device__ __forceinline__ float norm_coef_r(float nv, float gn, int power)
@@ -303,7 +305,8 @@ __global__ __launch_bounds__(RT) void k_resize_fwd(ResizeArgs a, ResizeDev d)
 // LDS: s_buf[4 waves][256] | s_tmp[fwd_rows][out_w] | s_red[16] | s_wh[taps_h][tp] | s_ih[taps_h][tp]
 __device__ float g_zero_unit_rz[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // never written; non-const keeps it global-space
 
-template <bool POST, bool RESID, int TWN, int B>
+// RNG (POST only): the noise unit of an owned row is drawn from a.rng where S1 consumes it (common.h: rng_unit)
+template <bool POST, bool RESID, int TWN, int B, bool RNG = false>
 __global__ __launch_bounds__(RT, 3) void k_resize_fwd_rows(ResizeArgs a, ResizeDev d)
 {
     extern __shared__ __align__(16) float lds[];
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(RT, 3) void k_resize_fwd_rows(ResizeArgs a, ResizeD
                 // rows this block does not own read a block of zeros: the loads themselves stay unconditional
                 const bool own = noisy && gy >= olo && gy < ohi;
                 vq[bb] = *reinterpret_cast<const float4 *>(own ? vv + o : g_zero_unit_rz);
-                zq[bb] = *reinterpret_cast<const float4 *>(own ? zz + o : g_zero_unit_rz);
+                if constexpr (!RNG) zq[bb] = *reinterpret_cast<const float4 *>(own ? zz + o : g_zero_unit_rz);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -393,7 +396,15 @@ __global__ __launch_bounds__(RT, 3) void k_resize_fwd_rows(ResizeArgs a, ResizeD
                 if (rr < cnt && gy >= olo && gy < ohi) {       // a row this block owns: the whole of S1 (packed: common.h)
                     float4 sm;
                     uchar4 gate;
-                    post_unit(xv[bb], ev[bb], vq[bb], zq[bb], a.k, x0, sm, gate);
+                    float4 zk = make_float4(0, 0, 0, 0);
+                    if constexpr (RNG) {     // the unit's index inside the particle: (channel plane, row, column) / 4
+                        if (noisy)
+                            zk = rng_unit(a.rng, ((unsigned)ch * ihw + (unsigned)(gy * d.in_w + 4 * cu)) >> 2,
+                                          rng_particle(a.rng, (unsigned)n));
+                    } else {
+                        zk = zq[bb];
+                    }
+                    post_unit(xv[bb], ev[bb], vq[bb], zk, a.k, x0, sm, gate);
                     const int64_t po = (int64_t)plane * ihw + (unsigned)(gy * d.in_w + 4 * cu);
                     if (a.x0_hat) *reinterpret_cast<float4 *>(a.x0_hat + po) = x0;
                     *reinterpret_cast<float4 *>(a.sample + po) = sm;
@@ -909,6 +920,30 @@ static int allow_lds(K kernel, bool &done)
         return check_launch();                                                       \
     } while (0)
 
+// the row-streaming kernel takes this operator (16-byte buffers assumed)
+static bool fwd_rows_ok(const ResizeDev &d)
+{
+    static const bool no_rows = getenv("DPSX_RESIZE_NO_ROWS") != nullptr;        // A/B switch for tools/kbench.py
+    const int wu = d.in_w / 4;
+    return !no_rows && d.in_w % 4 == 0 && wu >= 1 && wu <= 64 && 64 % wu == 0 && d.out_w <= wu && d.taps_w <= 32;
+}
+
+// K1 with the noise drawn in the kernel exists in the row-streaming kernel only; the staged-rows kernel declines
+bool resize_step_draws_in_kernel(const dpsx_op *op) { return fwd_rows_ok(dev_of(op)); }
+
+static int launch_fwd_rows_rng(const dpsx_op *op, const ResizeArgs &a, hipStream_t s)
+{
+    ResizeDev d = dev_of(op);
+    if (fwd_fine(d, a.planes)) {        // as launch_fwd
+        d.tp = d.tp2; d.fwd_rows = d.fwd_rows2; d.blk_lo = d.blk_lo2; d.blk_cnt = d.blk_cnt2; d.own_lo = d.own_lo2;
+        d.gparts = 1;
+    }
+    const unsigned grid_x = (unsigned)((a.planes + 7) / 8 * 8 * ((d.out_h + d.tp - 1) / d.tp));
+    const size_t lds_r = ((size_t)4 * 256 + (size_t)d.fwd_rows * d.out_w + 16 + 2 * (size_t)(d.taps_h * d.tp)) * 4;
+    if (d.taps_w <= 16) RZ_LAUNCH((k_resize_fwd_rows<true, true, 16, 4, true>), grid_x, lds_r, s, a, d);
+    RZ_LAUNCH((k_resize_fwd_rows<true, true, 32, 2, true>), grid_x, lds_r, s, a, d);
+}
+
 template <bool POST, bool RESID>
 static int launch_fwd(const dpsx_op *op, const ResizeArgs &a, bool vec, hipStream_t s)
 {
@@ -985,6 +1020,11 @@ int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     a.tail.blocks_per_particle = (int)resize_fwd_blocks_per_particle(op, f.c, f.n * f.c);
     const bool vec = rz_vec(op, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) &&
                      (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
+    if (f.use_rng) {
+        if (!vec || !resize_step_draws_in_kernel(op)) return DPSX_EUNSUPPORTED;      // nothing launched
+        a.rng = f.rng;
+        return launch_fwd_rows_rng(op, a, s);
+    }
     return launch_fwd<true, true>(op, a, vec, s);
 }
 

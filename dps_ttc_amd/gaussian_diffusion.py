@@ -151,6 +151,13 @@ class GaussianDiffusion:
         #: reference's draw) or "device" (kernels.resample: a pure function of the distances and one torch.rand per slot,
         #: computed per image on the device and fused with the particle gather -- the draw multi-image batches need)
         self.resample_draw = "multinomial"
+        #: the step noise: "torch" (torch.randn, one stream over the whole batch) or "device" (kernels.Rng: a counter-based
+        #: draw keyed on (noise_seed, loop index, path id, element), drawn inside the fused launches where the operator has
+        #: that form -- a path's noise then does not depend on the batch it runs in, the particle groups, the images per
+        #: batch or the ranks).  Batch row p is path path_base + p (path_base + p % K in a multi-image batch of K per image).
+        self.noise_draw = "torch"
+        self.noise_seed = 0
+        self.path_base = 0
         self.progress = False
         self.last_measurement_distance = None
         self.last_semantic_distance = None
@@ -190,6 +197,23 @@ class GaussianDiffusion:
         if value not in ("multinomial", "device"):
             raise ValueError(f"resample_draw must be 'multinomial' or 'device' (got {value!r})")
         return value
+
+    @staticmethod
+    def _check_noise_draw(value):
+        if value not in ("torch", "device"):
+            raise ValueError(f"noise_draw must be 'torch' or 'device' (got {value!r})")
+        return value
+
+    def _step_rng(self, idx, n, images=None):
+        """the kernels.Rng of loop index idx for a batch of n rows (images=M: M images x n / M paths), or None with
+        noise_draw = 'torch'.  Checked on every call, so a loop refuses a bad setting before its first launch."""
+        if self._check_noise_draw(self.noise_draw) == "torch":
+            return None
+        if self.rng_parity:
+            raise ValueError("noise_draw = 'device' draws its own stream: it cannot replay the reference's host RNG "
+                             "(rng_parity)")
+        per = n // int(images) if images is not None and int(images) > 1 else 0
+        return kernels.Rng(self.noise_seed, idx, kernels.Rng.TAG_STEP, self.path_base, per)
 
     # -- q ------------------------------------------------------------------
     def q_sample(self, x_start, t):
@@ -278,7 +302,7 @@ class GaussianDiffusion:
         return self._bufs[1]
 
     def dps_step(self, model, x_prev, idx, measurement, method, cond_kw, handle, noise=None, loop_kw=None,
-                 want_x0=False):
+                 want_x0=False, rng=None):
         """One fused DPS step at loop index idx.  Returns (x_next, norm[N]) -- device tensors that live in the
         sampler's persistent step buffers (valid until the next step; the loops clone what they hand out).
         loop_kw: the keyword arguments the calling loop passes to measurement_cond_fn besides the tensors
@@ -290,7 +314,7 @@ class GaussianDiffusion:
         if mo.shape[1] != 2 * x_prev.shape[1]:
             raise ValueError("the fused DPS step needs a learned-sigma model ([N, 2C, H, W] output)")
         coefs = self.sample_coefs(idx)
-        if noise is None:
+        if noise is None and rng is None:
             noise = self._randn(x_prev)
         buf = self._buffers(handle, x_prev)
         xp = kernels.f32c(x_prev.detach(), "x_t")
@@ -300,7 +324,7 @@ class GaussianDiffusion:
         spec = method.fused_spec(**loop_kw, **cond_kw)
         # x0_hat is consumed inside K1 (A(x0_hat), the clamp gate): the image itself is written out only when something
         # reads it afterwards -- the semantic term's embedder, a progress snapshot (want_x0)
-        kernels.step_fwd(handle, buf, xp, mo, noise, y, coefs, want_x0=want_x0 or "semantic" in spec)
+        kernels.step_fwd(handle, buf, xp, mo, noise, y, coefs, want_x0=want_x0 or "semantic" in spec, rng=rng)
         g_sem, self._step_semantic = None, None
         if "semantic" in spec:            # embedder forward + VJP on x0_hat (torch), between the two HIP halves
             g_sem, self._step_semantic = spec["semantic"](buf.x0_hat)
@@ -349,7 +373,8 @@ class GaussianDiffusion:
                 f"multi-image batch ({images} images): semantic guidance has one target for all particles; per-image "
                 "targets are not supported (set sem_guid_scale = 0 or run one image per call)")
 
-    def dps_step_grouped(self, model, img, idx, measurement, method, cond_kw, pg, noise, loop_kw=None, want_x0=False):
+    def dps_step_grouped(self, model, img, idx, measurement, method, cond_kw, pg, noise, loop_kw=None, want_x0=False,
+                         rng=None):
         """dps_step over kernels.ParticleGroups: every group's whole step -- model call, K1, [semantic term], K2, model VJP,
         K3 -- is enqueued on the group's own stream; nothing is joined between steps (group j's next step reads only what
         group j wrote).  img, noise: full-batch tensors.  Returns (x_next [N, C, H, W], norm [N]) -- views of the group
@@ -370,7 +395,7 @@ class GaussianDiffusion:
                 if mo.shape[1] != 2 * x_prev.shape[1]:
                     raise ValueError("the fused DPS step needs a learned-sigma model ([N, 2C, H, W] output)")
                 pg.step_fwd(j, kernels.f32c(x_prev.detach(), "x_t"), mo, noise, y, coefs,
-                            want_x0=want_x0 or "semantic" in spec)
+                            want_x0=want_x0 or "semantic" in spec, rng=rng)
                 g_sem = None
                 if "semantic" in spec:
                     g_sem, sem = spec["semantic"](pg.bufs[j].x0_hat)
@@ -408,28 +433,33 @@ class GaussianDiffusion:
         pg = None
         if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
             pg = self._particle_group_set(plan[0], plan[1], img, images=images)
+        self._step_rng(0, img.shape[0], images)       # validates noise_draw before the first step
         for idx in steps:
             projecting = project and returns_gradient and period != 0 and idx % period == 0
+            rng = self._step_rng(idx, img.shape[0], images)
             if plan is not None and not projecting:
-                noise = self._randn(img)
+                noise = self._randn(img) if rng is None else None
                 if self.rng_parity:
                     # the reference's q_sample draw (:224), result unused by ps*
                     self._randn(measurement, self.parity_measurement_stride)
                 snapshot = bool(record) and idx % 100 == 0
                 if pg is not None:
                     img, distance = self.dps_step_grouped(model, img, idx, measurement, plan[0], plan[1], pg, noise,
-                                                          want_x0=snapshot)
+                                                          want_x0=snapshot, rng=rng)
                     if snapshot:
                         pg.join()
                 else:
                     img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise,
-                                                  want_x0=snapshot)
+                                                  want_x0=snapshot, rng=rng)
                 if self._step_semantic is not None:
                     semantic = self._step_semantic
             else:
                 img = img.detach().requires_grad_()
                 time = torch.tensor([idx], device=img.device)
-                out = self.p_sample(x=img, t=time, model=model)
+                if rng is None:
+                    out = self.p_sample(x=img, t=time, model=model)
+                else:                     # per-op step: the same counters, filled by the stand-alone launch
+                    out = self.p_sample(x=img, t=time, model=model, noise=kernels.randn(img.shape, rng, img.device))
                 noisy_measurement = self.q_sample(measurement, t=idx)
                 ret = measurement_cond_fn(x_t=out['sample'], measurement=measurement,
                                           noisy_measurement=noisy_measurement, x_prev=img,
@@ -598,12 +628,13 @@ class SearchDDPM(DDPM):
     def search_step(self, model, img, idx, measurement, handle, noise=None, segments=None):
         with torch.no_grad():
             model_out = self._call_model(model, img, idx)
-        if noise is None:
+        rng = self._step_rng(idx, img.shape[0], segments) if noise is None else None
+        if noise is None and rng is None:
             noise = self._randn(img)
         # S1 -> scoring launch -> costs + select -> the winner's replication: one library call, nothing leaves the device
         local = self.global_select is None
         x_next, sample, costs, best, _ = handle.search_step(img, model_out, noise, measurement, self.step_coefs[idx],
-                                                            replicate=local, segments=segments)
+                                                            replicate=local, segments=segments, rng=rng)
         self.last_best = best
         if not local:
             return self.global_select(costs, sample), costs
@@ -614,12 +645,13 @@ class SearchDDPM(DDPM):
         segments=M: one state per image, [M,C,H,W] -> (winners [M,C,H,W], costs [n])."""
         with torch.no_grad():
             model_out = self._call_model(model, state, idx)
-        if noise is None:
+        rng = self._step_rng(idx, n, segments) if noise is None else None
+        if noise is None and rng is None:
             noise = self._randn(state, shape=(n,) + tuple(state.shape[1:]))
         local = self.global_select is None
         winner, sample, costs, best, _ = handle.search_step_one(state, model_out, noise, measurement,
                                                                 self.step_coefs[idx], want_winner=local,
-                                                                segments=segments)
+                                                                segments=segments, rng=rng, n=n if rng is not None else None)
         self.last_best = best
         if not local:
             winner = self.global_select(costs, sample, n_out=1)
@@ -651,6 +683,7 @@ class SearchDDPM(DDPM):
             raise ValueError(f"a measurement of {measurement.shape[0]} rows for {n} particles: pass n_images= for a "
                              "multi-image batch")
         per = n // (segments or 1)
+        self._step_rng(0, n, segments)    # validates noise_draw before the first step
         state = None                      # the single state particle(s), once a select has made all particles equal
         for idx in range(self.num_timesteps - 1, -1, -1):
             if state is None:
@@ -769,17 +802,20 @@ class TTC_DDIM(DDIM):
             except NotImplementedError as e:
                 raise NotImplementedError(f"ttc_ddim: {e}") from None
         self._resample_segments = segments      # the images of this trajectory's particle set (_resample draws per image)
+        self._step_rng(0, n, segments)    # validates noise_draw before the first step
         for idx in range(self.num_timesteps - 1, -1, -1):
+            rng = self._step_rng(idx, n, segments)
             if plan is not None:
-                noise = self._randn(img)
+                noise = self._randn(img) if rng is None else None
                 if self.rng_parity:
                     self._randn(measurement, self.parity_measurement_stride)      # q_sample's draw (:668)
                 # this loop passes no beta_scale / t to the conditioning method (:678-682): same on both routes
                 img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise,
-                                              loop_kw={})
+                                              loop_kw={}, rng=rng)
             else:
                 img = img.detach().requires_grad_()
-                out = self.p_sample(x=img, t=torch.tensor([idx], device=img.device), model=model)
+                out = self.p_sample(x=img, t=torch.tensor([idx], device=img.device), model=model,
+                                    noise=None if rng is None else kernels.randn(img.shape, rng, img.device))
                 noisy_measurement = self.q_sample(measurement, t=idx)
                 ret = measurement_cond_fn(x_t=out['sample'], measurement=measurement,
                                           noisy_measurement=noisy_measurement, x_prev=img,

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import Coefs, check, f32c, lib, ptr, require_cuda, stream_of
+from ._lib import Coefs, RngRec, check, f32c, lib, ptr, require_cuda, stream_of
 
 
 def make_coefs(a, b, c1, c2, min_log, max_log, add_noise):
@@ -30,10 +30,70 @@ def make_ddim_coefs(a, b, abar, abar_prev, eta, add_noise):
                  float(np.sqrt(one - abp - sigma ** 2)), float(sigma), 0.0, 2 | int(bool(add_noise)))
 
 
+# ------------------------------------------------------------------ counter-based normals
+class Rng:
+    """struct dpsx_rng: the normals of one step as a pure function of (seed, step, tag, particle id, element) -- see
+    include/dpsx.h.  Batch row p has particle id particle_base + (p % per_image if per_image > 0 else p); tag 0 is the step
+    noise, tag 1 x_start.  The same distribution as torch.randn, not the same stream."""
+
+    TAG_STEP, TAG_X_START = 0, 1
+
+    def __init__(self, seed, step, tag=0, particle_base=0, per_image=0):
+        self.seed, self.step, self.tag = int(seed), int(step), int(tag)
+        self.particle_base, self.per_image = int(particle_base), int(per_image)
+        if not 0 <= self.seed < 1 << 64 or not 0 <= self.step < 1 << 32 or not 0 <= self.tag < 1 << 32:
+            raise ValueError("Rng: seed must fit 64 bits, step and tag 32 bits")
+        if self.particle_base < 0 or self.per_image < 0:
+            raise ValueError("Rng: particle_base and per_image must not be negative")
+
+    def offset(self, rows):
+        """the record of the batch rows [rows, ...) of this one (a particle group's slice; with per_image set the slice
+        starts at an image boundary, so the id of a row stays particle_base + p % per_image)"""
+        if self.per_image > 0:
+            if rows % self.per_image:
+                raise ValueError("a slice of a multi-image batch must start at an image boundary")
+            return self
+        return Rng(self.seed, self.step, self.tag, self.particle_base + int(rows), 0)
+
+    def rec(self):
+        return RngRec(self.seed, self.step, self.tag, self.particle_base, self.per_image)
+
+    def __repr__(self):
+        return (f"Rng(seed={self.seed}, step={self.step}, tag={self.tag}, particle_base={self.particle_base}, "
+                f"per_image={self.per_image})")
+
+
+def randn(shape, rng, device, want_bits=False, out=None):
+    """[N, ...] fp32 normals of `rng` on `device`, one launch (dpsx_randn_f32).  want_bits: also the Philox words,
+    uint32 as an int32 tensor [N, 4 * ceil(chw / 4)].  out: fill this contiguous tensor instead of a new one."""
+    shape = tuple(int(v) for v in shape)
+    if out is None:
+        _cuda_device(device)
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 tensor of the requested shape")
+    require_cuda(out, "randn output")
+    n = shape[0] if shape else 1
+    chw = out.numel() // n if n else 0
+    bits = torch.empty((n, 4 * ((chw + 3) // 4)), dtype=torch.int32, device=out.device) if want_bits else None
+    check(lib().dpsx_randn_f32(ptr(out), ptr(bits), n, chw, byref(rng.rec()), stream_of(out)), "dpsx_randn_f32")
+    return (out, bits) if want_bits else out
+
+
+def _noise_or_rng(noise, rng):
+    if (noise is None) == (rng is None):
+        raise ValueError("give exactly one of noise= and rng=")
+
+
 # ------------------------------------------------------------------ S1
-def posterior_fwd(x_t, model_out, noise, coefs, want_inside=False, want_x0=True):
+def posterior_fwd(x_t, model_out, noise=None, coefs=None, want_inside=False, want_x0=True, rng=None):
     """p_mean_variance + DDPM.p_sample (gaussian_diffusion.py:308-330, 466-476) -> (x0_hat, sample[, inside]).
-    want_x0=False skips the x0_hat store (search_ddpm only consumes the sample): x0_hat is then None."""
+    want_x0=False skips the x0_hat store (search_ddpm only consumes the sample): x0_hat is then None.
+    rng= (instead of noise=): the noise is drawn inside the launch."""
+    if coefs is None:
+        raise ValueError("coefs is required")
+    if rng is not None and noise is not None:
+        raise ValueError("give exactly one of noise= and rng=")
     x_t, model_out = f32c(x_t, "x_t"), f32c(model_out, "model_out")
     noise = None if noise is None else f32c(noise, "noise")
     n, chw = x_t.shape[0], x_t[0].numel() if x_t.shape[0] else 0
@@ -41,6 +101,11 @@ def posterior_fwd(x_t, model_out, noise, coefs, want_inside=False, want_x0=True)
         raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of x {tuple(x_t.shape)}")
     x0, sample = (torch.empty_like(x_t) if want_x0 else None), torch.empty_like(x_t)
     inside = torch.empty(x_t.shape, dtype=torch.uint8, device=x_t.device) if want_inside else None
+    if rng is not None:
+        check(lib().dpsx_posterior_fwd_rng_f32(ptr(x_t), ptr(model_out), byref(rng.rec()), ptr(x0), ptr(sample),
+                                               ptr(inside), n, chw, byref(coefs), stream_of(x_t)),
+              "dpsx_posterior_fwd_rng_f32")
+        return (x0, sample, inside) if want_inside else (x0, sample)
     check(lib().dpsx_posterior_fwd_f32(ptr(x_t), ptr(model_out), ptr(noise), ptr(x0), ptr(sample), ptr(inside),
                                        n, chw, byref(coefs), stream_of(x_t)), "dpsx_posterior_fwd_f32")
     return (x0, sample, inside) if want_inside else (x0, sample)
@@ -164,6 +229,14 @@ class OpHandle:
         (GaussianDiffusion._fusion_plan asks before the first step)."""
         return self.kind != _lib.KIND_MASK or (int(h) * int(w)) % 4 == 0
 
+    def draws_in_kernel(self, c, h, w):
+        """whether step_fwd(rng=) draws the noise inside this handle's K1 at [N, c, h, w] (dpsx_step_draws_in_kernel, for
+        buffers torch allocated): both blur kernels on whole 64 x 64 tiles, the row-streaming resize kernel, inpainting
+        in its float4 form, the identity.
+        Elsewhere that call declines and step_fwd fills a persistent noise buffer with `randn` and runs the pointer
+        launch -- the same bits."""
+        return bool(lib().dpsx_step_draws_in_kernel(self._h, int(c), int(h), int(w)))
+
     def out_hw(self, h, w):
         oh, ow = c_int64(), c_int64()
         check(lib().dpsx_op_out_shape(self._h, h, w, byref(oh), byref(ow)), "dpsx_op_out_shape")
@@ -224,13 +297,15 @@ class OpHandle:
                                           n, c, h, w, ptr(ws), ws.numel(), stream_of(x)), "dpsx_score_argmin_f32")
         return costs, best, val
 
-    def search_step(self, x_t, model_out, noise, y, coefs, replicate=True, segments=None):
+    def search_step(self, x_t, model_out, noise=None, y=None, coefs=None, replicate=True, segments=None, rng=None):
         """One search_ddpm step (gaussian_diffusion.py:618-633): S1, costs of the proposals, select and -- with
         replicate=True -- the winner copied over all particles.  -> (x_next or None, sample, costs, best, costs[best]);
         one library call, nothing leaves the device.
         segments=M: a multi-image batch of M images x N / M particles (image-major), y [1 or M, ...]: the select runs per
         image, best / costs[best] are [M] (global particle indices) and each image's winner is replicated over its own
-        particles."""
+        particles.
+        rng= (instead of noise=): S1 draws the noise inside its launch."""
+        _noise_or_rng(noise, rng)
         x_t, model_out, y = _nchw(f32c(x_t, "x_t")), f32c(model_out, "model_out"), f32c(y, "measurement")
         noise = None if noise is None else f32c(noise, "noise")
         n, c, h, w = x_t.shape
@@ -242,6 +317,15 @@ class OpHandle:
         x_next = torch.empty_like(x_t) if replicate else None
         costs = torch.empty(n, dtype=torch.float32, device=x_t.device)
         ws = self.workspace(n, c, h, w, x_t.device)
+        if rng is not None:
+            seg = 1 if segments is None else int(segments)
+            best = torch.empty(seg if segments is not None else (), dtype=torch.int64, device=x_t.device)
+            val = torch.empty(seg, dtype=torch.float32, device=x_t.device)
+            check(lib().dpsx_search_step_seg_rng_f32(self._h, ptr(x_t), ptr(model_out), byref(rng.rec()), ptr(y),
+                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val),
+                                                     ptr(x_next), seg, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
+                                                     stream_of(x_t)), "dpsx_search_step_seg_rng_f32")
+            return x_next, sample, costs, best, val
         if segments is not None:
             best = torch.empty(int(segments), dtype=torch.int64, device=x_t.device)
             val = torch.empty(int(segments), dtype=torch.float32, device=x_t.device)
@@ -257,13 +341,20 @@ class OpHandle:
                                          ws.numel(), stream_of(x_t)), "dpsx_search_step_f32")
         return x_next, sample, costs, best, val
 
-    def search_step_one(self, x_one, model_out_one, noise, y, coefs, want_winner=True, segments=None):
+    def search_step_one(self, x_one, model_out_one, noise=None, y=None, coefs=None, want_winner=True, segments=None,
+                        rng=None, n=None):
         """The same step from ONE state particle (after a select all particles are copies of the winner): x_one
         [1,C,H,W], model_out_one [1,2C,H,W], noise [N,C,H,W] -> (winner [1,C,H,W] or None, sample [N,...], costs,
         best, costs[best]).  Bit-identical to search_step on N copies of the state; one model evaluation per step.
         segments=M: M images, one state each (x_one [M,C,H,W], model_out_one [M,2C,H,W]); proposal p reads state p / (N / M),
-        the select runs per image and winner / best / costs[best] are [M, ...] (best: global particle indices)."""
+        the select runs per image and winner / best / costs[best] are [M, ...] (best: global particle indices).
+        rng= with n= (instead of noise=): the N proposals' noise is drawn inside S1's launch."""
+        _noise_or_rng(noise, rng)
         x_one, model_out_one, y = _nchw(f32c(x_one, "x_t")), f32c(model_out_one, "model_out"), f32c(y, "measurement")
+        if rng is not None:
+            if n is None:
+                raise ValueError("search_step_one(rng=) needs n=, the number of proposals")
+            return self._search_step_one_rng(x_one, model_out_one, rng, int(n), y, coefs, want_winner, segments)
         noise = _nchw(f32c(noise, "noise"))
         n, c, h, w = noise.shape
         if n == 0:
@@ -292,6 +383,27 @@ class OpHandle:
                                              ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(winner), n, c, h, w,
                                              byref(coefs), ptr(ws), ws.numel(), stream_of(noise)),
               "dpsx_search_step_one_f32")
+        return winner, sample, costs, best, val
+
+    def _search_step_one_rng(self, x_one, model_out_one, rng, n, y, coefs, want_winner, segments):
+        states, c, h, w = x_one.shape
+        if n < 1:
+            raise ValueError("best-of-N over an empty particle set")
+        if states != (1 if segments is None else int(segments)) or model_out_one.shape[0] != states or \
+                model_out_one[0].numel() != 2 * c * h * w or n % states:
+            raise ValueError(f"{1 if segments is None else int(segments)} state particle(s) expected: x "
+                             f"{tuple(x_one.shape)}, model_out {tuple(model_out_one.shape)}, {n} proposals")
+        dev = x_one.device
+        sample = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+        winner = torch.empty_like(x_one) if want_winner else None
+        costs = torch.empty(n, dtype=torch.float32, device=dev)
+        best = torch.empty(states if segments is not None else (), dtype=torch.int64, device=dev)
+        val = torch.empty(states, dtype=torch.float32, device=dev)
+        ws = self.workspace(n, c, h, w, dev)
+        check(lib().dpsx_search_step_one_seg_rng_f32(self._h, ptr(x_one), ptr(model_out_one), byref(rng.rec()), ptr(y),
+                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val),
+                                                     ptr(winner), states, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
+                                                     stream_of(x_one)), "dpsx_search_step_one_seg_rng_f32")
         return winner, sample, costs, best, val
 
     def resample_cost(self, x, y, prev_costs=None, potential_type='min'):
@@ -557,6 +669,13 @@ class StepBuffers:
                 check(int(rb), "dpsx_step_resid_bytes")
         self.resid = torch.empty(max(int(rb), 256), dtype=torch.uint8, device=device)
         self.flip = 0
+        self._noise = None
+
+    def noise_buffer(self):
+        """[n, c, h, w] scratch that step_fwd(rng=) fills for operators without an in-kernel draw (allocated on first use)"""
+        if self._noise is None:
+            self._noise = torch.empty(self.shape, dtype=torch.float32, device=self.sample.device)
+        return self._noise
 
 
 def _stream_arg(stream, t):
@@ -573,20 +692,38 @@ def _stream_arg(stream, t):
     return ctypes.c_void_p(stream.cuda_stream)
 
 
-def step_fwd(handle, buf, x_t, model_out, noise, y, coefs, finalize_norm=False, want_x0=True, stream=None):
+def step_fwd(handle, buf, x_t, model_out, noise=None, y=None, coefs=None, finalize_norm=False, want_x0=True, stream=None,
+             rng=None):
     """K1.  finalize_norm=False (the loop's setting): buf.norm is filled by the following step_bwd, whose prologue
     finalises the per-tile partial sums this launch leaves in the workspace.  finalize_norm=True: the launch finishes
     buf.norm itself (each particle's last block re-sums the partials in the same fixed order -- same bits) and
     step_bwd reads one float per particle; measured at N = 64: K1 +4.8 us, K2 -3.3 us, so the loop does not use it.
     want_x0=False (blur and resize operators): x0_hat is consumed inside the launch and not written to buf.x0_hat --
     the `ps` step reads it nowhere afterwards (the backward half works from the clamp gate); other operators ignore
-    the flag."""
+    the flag.
+    rng= (instead of noise=): the noise of kernels.Rng is drawn inside the launch where the operator has that form
+    (handle.draws_in_kernel); elsewhere a persistent buffer of buf is filled by `randn` on the same stream and the pointer
+    launch runs -- the same bits either way."""
+    _noise_or_rng(noise, rng)
     n, c, h, w = buf.shape
     ws = handle.workspace(n, c, h, w, x_t.device)
     buf.norm_ready = bool(finalize_norm)
     optional = handle.kind in (_lib.KIND_SEP, _lib.KIND_TAPS, _lib.KIND_RESIZE) or \
         (handle.kind == _lib.KIND_PHASE and (h, w) == (256, 256) and getattr(handle, "spectral", False))
     x0_out = None if optional and not want_x0 else buf.x0_hat
+    if rng is not None:
+        if handle.draws_in_kernel(c, h, w):
+            rc = lib().dpsx_step_fwd_rng_f32(handle._h, ptr(x_t), ptr(model_out), byref(rng.rec()), ptr(y), y.shape[0],
+                                             ptr(x0_out), ptr(buf.sample), ptr(buf.inside), ptr(buf.resid),
+                                             ptr(buf.norm) if finalize_norm else None,
+                                             n, c, h, w, byref(coefs), ptr(ws), ws.numel(), _stream_arg(stream, x_t))
+            if rc != _lib.EUNSUPPORTED:      # declined (nothing was launched, e.g. an unaligned view): the pointer form
+                check(rc, "dpsx_step_fwd_rng_f32")
+                return
+        noise = buf.noise_buffer()
+        if coefs.add_noise & 1:          # the t = 0 step reads no noise
+            check(lib().dpsx_randn_f32(ptr(noise), None, n, c * h * w, byref(rng.rec()), _stream_arg(stream, x_t)),
+                  "dpsx_randn_f32")
     check(lib().dpsx_step_fwd_f32(handle._h, ptr(x_t), ptr(model_out), ptr(noise), ptr(y), y.shape[0],
                                   ptr(x0_out), ptr(buf.sample), ptr(buf.inside), ptr(buf.resid),
                                   ptr(buf.norm) if finalize_norm else None,
@@ -717,9 +854,12 @@ class ParticleGroups:
         return v
 
     # -- the three launches of group j, on its stream
-    def step_fwd(self, j, x_t, model_out, noise, y, coefs, want_x0=True):
+    def step_fwd(self, j, x_t, model_out, noise=None, y=None, coefs=None, want_x0=True, rng=None):
+        """rng= (instead of noise=): the record of the WHOLE batch; the group's slice start is added to its particle_base"""
+        _noise_or_rng(noise, rng)
         step_fwd(self.handles[j], self.bufs[j], self._slice(j, x_t), self._slice(j, model_out), self._slice(j, noise),
-                 self.y_rows(j, y), coefs, want_x0=want_x0, stream=self.streams[j])
+                 self.y_rows(j, y), coefs, want_x0=want_x0, stream=self.streams[j],
+                 rng=None if rng is None else rng.offset(self.starts[j]))
 
     def step_bwd(self, j, y, scale, power, coefs, g_x0_extra=None):
         step_bwd(self.handles[j], self.bufs[j], self.y_rows(j, y), scale, power, coefs,

@@ -300,6 +300,53 @@ int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int6
                           const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
                           int64_t n, int64_t chw, void *stream);
 
+/* ---- counter-based normals: the step noise as a pure function of (seed, step, tag, particle id, element), so a path's
+ * noise does not depend on the batch, the particle groups, the images per batch or the ranks it is computed with.
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), one call per float4 unit:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (unit = element offset inside the particle / 4, particle id, step, tag)    tag 0: step noise, 1: x_start
+ *   particle id of batch row p = particle_base + (per_image > 0 ? p % per_image : p); it must fit 32 bits (DPSX_EINVAL)
+ *   words r0..r3 -> u1 = ((r >> 8) + 1) 2^-24 in (0, 1], u2 = (r >> 8) 2^-24 in [0, 1); rad = sqrt(-2 ln u1);
+ *   (r0, r1) -> elements 0, 1 = (rad cos 2 pi u2, rad sin 2 pi u2), (r2, r3) -> elements 2, 3.   |z| <= 5.77, always finite.
+ * Element e of a particle takes word e % 4 of unit e / 4 (chw need not be a multiple of 4).  The same distribution as
+ * torch.randn, not the same stream.  One device function computes it everywhere: the fill below and the in-kernel draws
+ * of the _rng entry points agree bit for bit.  The record is read on the host when the call is enqueued: a captured
+ * graph replays the counters it was captured with. */
+typedef struct dpsx_rng { uint64_t seed; uint32_t step; uint32_t tag; int64_t particle_base; int64_t per_image; } dpsx_rng;
+
+/* out [n, chw] normals; bits_out (nullable) uint32 [n, 4 * ceil(chw / 4)]: the Philox words of every unit */
+int dpsx_randn_f32(float *out, uint32_t *bits_out, int64_t n, int64_t chw, const dpsx_rng *rng_host, void *stream);
+
+/* dpsx_posterior_fwd_f32 with the noise drawn inside the launch (no noise tensor is written or read) */
+int dpsx_posterior_fwd_rng_f32(const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                               float *x0_hat, float *sample, uint8_t *inside,
+                               int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream);
+
+/* dpsx_step_fwd_f32 without the noise pointer.  DPSX_EUNSUPPORTED, before anything is launched: this operator / shape
+ * has no in-kernel draw; the caller fills a noise buffer with dpsx_randn_f32 and calls dpsx_step_fwd_f32 -- the same bits.
+ * dpsx_step_draws_in_kernel: 1 where the _rng call draws in its launch for 16-byte aligned buffers (both blur kernels
+ * on whole 64 x 64 tiles, the row-streaming resize kernel, inpainting with H * W a multiple of 4, the identity), 0 where
+ * it declines (the blur kernels' general loaders, the staged-rows resize kernel, phase retrieval). */
+int dpsx_step_draws_in_kernel(const dpsx_op *op, int64_t c, int64_t h, int64_t w);
+int dpsx_step_fwd_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                          const float *y, int64_t y_n,
+                          float *x0_hat, float *sample, uint8_t *inside, void *resid, float *norm,
+                          int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+
+/* dpsx_search_step_seg_f32 / dpsx_search_step_one_seg_f32 with S1's noise drawn inside its launch (segments = 1: the
+ * unsegmented steps) */
+int dpsx_search_step_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                                 const float *y, int64_t y_n, float *sample, float *costs,
+                                 int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments,
+                                 int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
+int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
+                                     const float *y, int64_t y_n, float *sample, float *costs,
+                                     int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments,
+                                     int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

@@ -111,7 +111,22 @@ def parse_args(argv=None):
                    help='the resampling draw of ttc_ddim: torch.multinomial over all particles (default, the '
                         "reference's draw) or the library's per-image draw fused with the particle gather "
                         '(one launch; required for --images_per_batch > 1 with ttc_ddim)')
+    p.add_argument('--noise_draw', type=str, default='torch', choices=('torch', 'device'),
+                   help="the step noise and x_start: torch.randn over the whole batch (default) or the library's "
+                        'counter-based draw keyed on (--seed, step, path id, element): a path then draws the same noise '
+                        'whatever --batch_size, --particle_groups, --images_per_batch and the number of ranks are')
     return p.parse_args(argv)
+
+
+def start_particles(args, sampler, g, shape, device, per_image=0):
+    """x_start of particle group g.  --noise_draw device: the sampler is told the group's first path id (global over the
+    ranks: the groups shard contiguously) and x_start is the tag-1 draw of those paths; else torch.randn"""
+    if args.noise_draw != 'device':
+        return torch.randn(shape, device=device).requires_grad_()
+    from dps_ttc_amd import kernels
+    sampler.path_base = args.path_start_idx + g * args.batch_size
+    rng = kernels.Rng(sampler.noise_seed, 0, kernels.Rng.TAG_X_START, sampler.path_base, per_image)
+    return kernels.randn(shape, rng, device).requires_grad_()
 
 
 def image_batches(picks, m):
@@ -193,6 +208,8 @@ def main(argv=None):
     sampler = create_sampler(**diffusion_config)
     sampler.particle_groups = max(1, args.particle_groups)
     sampler.resample_draw = args.resample_draw
+    sampler.noise_draw = args.noise_draw
+    sampler.noise_seed = args.seed or 0          # the same on every rank: the path id tells the ranks' particles apart
     groups = args.n_paths // args.batch_size
     if world > 1 and diffusion_config['sampler'] in ('search_ddpm', 'ttc_ddim'):
         # these loops exchange particles at every select / resample point: every rank runs the same number of groups
@@ -231,7 +248,7 @@ def main(argv=None):
     if args.images_per_batch > 1:
         for batch in image_batches(picks, args.images_per_batch):
             run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn,
-                            mask_gen, groups, diffusion_config['sampler'], out_path)
+                            mask_gen, groups, diffusion_config['sampler'], out_path, sampler=sampler)
         return
 
     # particle groups shard contiguously over the ranks: the rank-major order of the gathered scores is the path order
@@ -275,7 +292,7 @@ def main(argv=None):
 
         distances, finals = [], []
         for g in my_groups:
-            x_start = torch.randn((args.batch_size, C, H, W), device=device).requires_grad_()
+            x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
             if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances) (reference :707)
                 sample = sample[0]
@@ -309,7 +326,7 @@ def main(argv=None):
 
 
 def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn, mask_gen,
-                    groups, sampler_name, out_path):
+                    groups, sampler_name, out_path, sampler=None):
     """--images_per_batch: the B = len(batch) images of `batch` as one multi-image batch per particle group --
     B x batch_size particles, image-major (particles [b K, (b + 1) K) belong to image b), y [B, ...] -- and the
     per-image best-of-N (one argmin per image over its n_paths distances, on the device)."""
@@ -342,7 +359,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
 
     distances, finals = [], []
     for g in range(groups):
-        x_start = torch.randn((B * K, C, H, W), device=device).requires_grad_()
+        x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
         if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances)
             sample = sample[0]

@@ -14,6 +14,11 @@ sequences with y[m] (and mask[m]) in the same process: us per step and particle-
 (a) torch.multinomial + its [N]-sized glue + two gathers (resample_draw = "multinomial", the non-parity branch),
 (b) kernels.resample_draw + two gathers, (c) the fused kernels.resample; single image at K = 16 / 64 / 512 and
 M (default 4) images x K = 16, there also against M single-image calls of each form.
+    python tools/kbench.py --noise-draw                                               (the step noise, 256^2, N = --particles)
+--noise-draw: K1 of every operator and the single-state search step with the step noise drawn three ways, alternated in
+one process: (a) torch.randn + the pointer launch (noise_draw = "torch"), (b) kernels.randn (dpsx_randn_f32) + the pointer
+launch, (c) the draw inside the launch (step_fwd(rng=) / search_step_one(rng=)); a route without an in-kernel form is
+marked and its (c) is the front end's fallback, which is (b).
 """
 import argparse
 import os
@@ -37,7 +42,10 @@ def main():
     ap.add_argument("--no-x0", action="store_true", help="K1 does not write x0_hat out (blur / resize; the `ps` loop's setting)")
     ap.add_argument("--images", type=int, default=None, help="time the multi-image step of M images x --particles")
     ap.add_argument("--resample", action="store_true", help="time the resampling step (multinomial / draw + gathers / fused)")
+    ap.add_argument("--noise-draw", action="store_true", help="time the step noise: torch.randn / device fill / in-kernel draw")
     args = ap.parse_args()
+    if args.noise_draw:
+        return noise_draw(args)
     if args.resample:
         return resample_step(args)
     if args.images is not None:
@@ -233,6 +241,85 @@ def resample_step(args):
             print(f"resample 256^2 M={M} K={k:3d} {name:36s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs})  "
                   f"{moved / ts.mean() / 1e6:6.2f} TB/s = {moved / ts.mean() / 1e6 / 8.0:.2f} of 8 TB/s", flush=True)
         del img, parts
+
+
+def noise_draw(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    n = args.particles
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    x_t, ring, truth, _ = bench.synth_inputs(n, 2, dev, 1234)
+    shape = tuple(x_t.shape)
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    def report(tag, forms, note):
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            print(f"noise 256^2 N={n} {tag:18s} {name:30s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs})  {note}",
+                  flush=True)
+
+    for name in ("gaussian_blur", "motion_blur", "super_resolution", "inpainting", "phase_retrieval"):
+        op, fkw = bench.build_operator(name, dev)
+        y = op.forward(truth.to(dev), **fkw).detach().contiguous()
+        handle = op.hip_handle_for(fkw["mask"]) if name == "inpainting" else op.hip_handle(x_t)
+        buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+        fill = buf.noise_buffer()
+        want_x0 = name in ("inpainting", "phase_retrieval")            # as the `ps` loop: x0_hat is stored only where K2 reads it
+        in_kernel = handle.draws_in_kernel(3, 256, 256)
+
+        def a_torch(i):
+            kernels.step_fwd(handle, buf, x_t, ring[i % 2]["model_out"], torch.randn(shape, device=dev), y, ck, want_x0=want_x0)
+
+        def b_fill(i):
+            kernels.randn(shape, kernels.Rng(7, i), dev, out=fill)
+            kernels.step_fwd(handle, buf, x_t, ring[i % 2]["model_out"], fill, y, ck, want_x0=want_x0)
+
+        def c_rng(i):
+            kernels.step_fwd(handle, buf, x_t, ring[i % 2]["model_out"], None, y, ck, want_x0=want_x0, rng=kernels.Rng(7, i))
+
+        report(name + " K1", (("a torch.randn + pointer", a_torch), ("b device fill + pointer", b_fill),
+                              ("c in-kernel draw", c_rng)), "in-kernel" if in_kernel else "declines: c is the fallback, = b")
+        del buf, handle, op
+
+    # the single-state search step (S1 from one state for N proposals, scoring, select, the winner's copy)
+    op, fkw = bench.build_operator("gaussian_blur", dev)
+    y = op.forward(truth.to(dev), **fkw).detach().contiguous()
+    handle = op.hip_handle(x_t)
+    x1 = x_t[:1].contiguous()
+    fill = torch.empty(shape, device=dev)
+
+    def sa(i):
+        handle.search_step_one(x1, ring[i % 2]["model_out"][:1], torch.randn(shape, device=dev), y, ck)
+
+    def sb(i):
+        kernels.randn(shape, kernels.Rng(7, i), dev, out=fill)
+        handle.search_step_one(x1, ring[i % 2]["model_out"][:1], fill, y, ck)
+
+    def sc(i):
+        handle.search_step_one(x1, ring[i % 2]["model_out"][:1], None, y, ck, rng=kernels.Rng(7, i), n=n)
+
+    report("search_step_one", (("a torch.randn + pointer", sa), ("b device fill + pointer", sb), ("c in-kernel draw", sc)),
+           "in-kernel (S1)")
 
 
 if __name__ == "__main__":
