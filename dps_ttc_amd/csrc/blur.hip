@@ -1293,14 +1293,21 @@ static int launch_sep_adj(const BlurArgs &a, const SepTaps &t, int reach, hipStr
 {
     // two or more full tiles per axis: every fold is a fast (register-window) fold and the scratch holds one norm slot
     const size_t lds = sep_lds_bytes(4 * R4, a.h % TH == 0 && a.w % TW == 0 && a.tiles_x >= 2 && a.tiles_y >= 2);
-    DPSX_LAUNCH((k_blur_sep_adj<R4, EPI>), grid_blocks(a), lds, s, a, t, reach);
+    // the fused epilogue is compiled with and without the extra cotangent: the default step carries neither its loads nor a branch
+    if constexpr (EPI) {
+        if (a.g_extra) DPSX_LAUNCH((k_blur_sep_adj<R4, true, true>), grid_blocks(a), lds, s, a, t, reach);
+    }
+    DPSX_LAUNCH((k_blur_sep_adj<R4, EPI, false>), grid_blocks(a), lds, s, a, t, reach);
 }
 
 template <int R4, bool EPI>
 static int launch_sep_adj_sym(const BlurArgs &a, const SepTaps &t, hipStream_t s)
 {
     const size_t lds = sep_lds_bytes(4 * R4, true);
-    DPSX_LAUNCH((k_blur_sep_adj_sym<R4, EPI>), grid_blocks(a), lds, s, a, t);
+    if constexpr (EPI) {
+        if (a.g_extra) DPSX_LAUNCH((k_blur_sep_adj_sym<R4, true, true>), grid_blocks(a), lds, s, a, t);
+    }
+    DPSX_LAUNCH((k_blur_sep_adj_sym<R4, EPI, false>), grid_blocks(a), lds, s, a, t);
 }
 
 // symmetric taps on both axes (bitwise), whole tiles, two or more of them per axis, reach inside the image: the adjoint

@@ -94,6 +94,63 @@ __device__ __forceinline__ void halo_unit(int hu, int &rr, int &cu)
     cu = tb ? (int)c_tb : (int)(c_lr < Q ? c_lr : c_lr + (TW / 4));
 }
 
+// n / D for n < 4096 as one 24-bit multiply and a shift (the general expansion of a division by a constant is a
+// quarter-rate mul-hi plus fix-up shifts and adds); exact: checked below for every n the halo deals can hold
+template <int D>
+constexpr bool small_div_exact()
+{
+    for (unsigned n = 0; n < 4096; ++n)
+        if (((n * (((1u << 20) + D - 1) / D)) >> 20) != n / D) return false;
+    return true;
+}
+template <int D>
+__device__ __forceinline__ unsigned small_div(unsigned n)
+{
+    static_assert(small_div_exact<D>(), "small_div: not exact below 4096");
+    if constexpr ((D & (D - 1)) == 0) return n / D;
+    else return (n * (((1u << 20) + D - 1) / D)) >> 20;
+}
+
+// The regular loader's form of halo_unit: the K-th halo unit of thread t, hu = min(t + K NT, HALO - 1) (surplus lanes repeat
+// the last unit).  K is a compile-time constant, so which band(s) the 256 units of deal K fall into is known: a deal that lies
+// wholly in one band carries neither the other band's arithmetic nor the selects between them (sigma = 3: deals 0 and 1 are
+// top / bottom rows, deal 3 is left / right columns, only deal 2 straddles).  Same unit -> (row, column) map as halo_unit.
+template <int RR, int K>
+__device__ __forceinline__ void halo_unit_deal(int t, int &rr, int &cu)
+{
+    using G = SepGeom<RR>;
+    static_assert(G::HALO <= 4096, "small_div range");
+    constexpr int Q = RR / 4, TB2 = 2 * G::HALO_TB, LO = K * NT, HI = (LO + NT - 1 < G::HALO - 1) ? LO + NT - 1 : G::HALO - 1;
+    const unsigned hu = (HI == LO + NT - 1) ? (unsigned)(t + LO) : (unsigned)min(t + LO, G::HALO - 1);
+    int rr_tb = 0, cu_tb = 0, rr_lr = 0, cu_lr = 0;
+    if constexpr (LO < TB2) {
+        const unsigned r = small_div<G::RWU>(hu);
+        cu_tb = (int)(hu - r * G::RWU);
+        if constexpr (HI / G::RWU < RR) rr_tb = (int)r;                 // all above the tile
+        else if constexpr (LO / G::RWU >= RR) rr_tb = (int)r + TH;      // all below it
+        else rr_tb = (int)(r < RR ? r : r + TH);
+    }
+    if constexpr (HI >= TB2) {
+        const unsigned v = LO >= TB2 ? hu - TB2 : (unsigned)max((int)hu - TB2, 0);
+        const unsigned r = small_div<2 * Q>(v), c = v - r * (2 * Q);
+        rr_lr = (int)r + RR;
+        cu_lr = (int)(c < Q ? c : c + (TW / 4));
+    }
+    if constexpr (HI < TB2) { rr = rr_tb; cu = cu_tb; }
+    else if constexpr (LO >= TB2) { rr = rr_lr; cu = cu_lr; }
+    else {
+        const bool tb = hu < (unsigned)TB2;
+        rr = tb ? rr_tb : rr_lr;
+        cu = tb ? cu_tb : cu_lr;
+    }
+}
+template <int RR, int K = 0>
+__device__ __forceinline__ void halo_units_deal(int t, int (&rr)[SepGeom<RR>::HALO_PER_THREAD], int (&cu)[SepGeom<RR>::HALO_PER_THREAD])
+{
+    halo_unit_deal<RR, K>(t, rr[K], cu[K]);
+    if constexpr (K + 1 < SepGeom<RR>::HALO_PER_THREAD) halo_units_deal<RR, K + 1>(t, rr, cu);
+}
+
 // load one float4 unit of a plane at image row gy (already mapped), columns gx..gx+3
 template <bool REFLECT>
 __device__ __forceinline__ float4 load_unit(const float *plane, int sy, int gx, int w, bool rowok)
@@ -261,16 +318,24 @@ __device__ __forceinline__ void load_region_fast(float *s, const int h0, const i
 
 // ---- loader for REGULAR geometry: h % TH == 0, w % TW == 0, RR < min(h, w).  Every tile is full and
 // every float4 unit lies wholly inside or wholly outside the image, so each unit is exactly one
-// unconditional 16-byte load (a wholly reflected unit is the mirrored unit read backwards; a wholly
-// zero-extended one reads a clamped address and is zeroed) -- no divergent branch, no per-element path,
+// unconditional 16-byte load (a wholly reflected unit is the mirrored unit, reversed; a wholly
+// zero-extended one reads a block of zeros) -- no divergent branch, no per-element path,
 // hence nothing for the compiler to serialise: all loads issue back to back, one wait.
+// The reversal of a mirrored unit is done on the LOADED REGISTERS, where the unit is consumed (unit_unmirror), behind an
+// empty asm: a select between the unit and its reverse that the compiler can see through is folded into the addresses,
+// and the one 16-byte load becomes four 4-byte loads with a selected 64-bit address each (the symmetric adjoint's loader
+// spread its halo over ~300 instructions that way).
 typedef float v4fu __attribute__((ext_vector_type(4), aligned(4)));
 __device__ float g_zero_unit[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // never written; non-const keeps it a global-space pointer
 
+// is the unit at columns gx..gx+3 a mirrored one (REFLECT only: wholly left or right of the image)
+__device__ __forceinline__ bool unit_mirrored(int gx, int w) { return gx < 0 || gx >= w; }
+
+// the unit as it lies in memory: a mirrored unit still has to be reversed (unit_unmirror)
 template <bool REFLECT>
-__device__ __forceinline__ float4 load_unit_reg(const float *plane, int gy, int gx, int h, int w)
+__device__ __forceinline__ float4 load_unit_raw(const float *plane, int gy, int gx, int h, int w)
 {
-    const bool outx = gx < 0 || gx >= w, outy = gy < 0 || gy >= h;
+    const bool outx = unit_mirrored(gx, w), outy = gy < 0 || gy >= h;
     int sy, sx;
     if constexpr (REFLECT) {
         sy = gy < 0 ? -gy : (gy >= h ? 2 * (h - 1) - gy : gy);
@@ -283,8 +348,25 @@ __device__ __forceinline__ float4 load_unit_reg(const float *plane, int gy, int 
     // zero extension: a unit outside the image reads a block of zeros -- the load itself stays unconditional
     if constexpr (!REFLECT) p = (outx || outy) ? g_zero_unit : p;
     const v4fu v = *reinterpret_cast<const v4fu *>(p);
-    if constexpr (REFLECT) return outx ? make_float4(v.w, v.z, v.y, v.x) : make_float4(v.x, v.y, v.z, v.w);
-    else return make_float4(v.x, v.y, v.z, v.w);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ float4 unit_unmirror(const float4 &u, bool mirrored)
+{
+    float x = u.x, y = u.y, z = u.z, w = u.w;
+    // the loaded registers, opaque and one by one: the selects below stay four selects of registers (as ONE vector they
+    // become an element read at a selected index, three selects per element)
+    asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));
+    return make_float4(mirrored ? w : x, mirrored ? z : y, mirrored ? y : z, mirrored ? x : w);
+}
+
+// the unit in image order, reversal left to the compiler (the tap-list kernels' loaders in blur.hip)
+template <bool REFLECT>
+__device__ __forceinline__ float4 load_unit_reg(const float *plane, int gy, int gx, int h, int w)
+{
+    const float4 v = load_unit_raw<REFLECT>(plane, gy, gx, h, w);
+    if constexpr (REFLECT) return unit_mirrored(gx, w) ? make_float4(v.w, v.z, v.y, v.x) : v;
+    else return v;
 }
 
 // RNG (POST only): the noise unit is drawn from a.rng where S1 consumes it instead of loaded up front (common.h: rng_unit)
@@ -308,6 +390,10 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
     constexpr int NI = TH * TW / 4 / NT;  // interior units per thread (4)
     constexpr int NH = G::HALO_PER_THREAD;
     float4 xi[NI], ei[NI], vi[NI], zi[NI], xh[NH], eh[NH];
+    int hrr[NH], hcu[NH];                 // the lane's halo units, mapped once: load address here, LDS word below
+    halo_units_deal<RR>(threadIdx.x, hrr, hcu);
+    int tid = threadIdx.x;
+    if constexpr (POST) asm volatile("" : "+v"(tid));    // see below: K1 maps them a second time instead
     // streams with reuse first and grouped per stream (a neighbour's halo is this tile's interior: both
     // requests for a shared line then reach the L2 close together); once-read streams last, non-temporal
 #pragma unroll
@@ -321,10 +407,7 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
         }
 #pragma unroll
         for (int k = 0; k < NH; ++k) {
-            const int hu = min((int)threadIdx.x + k * NT, G::HALO - 1);   // surplus lanes repeat the last unit
-            int rr, cu;
-            halo_unit<RR>(hu, rr, cu);
-            const float4 v = load_unit_reg<REFLECT || POST>(p, h0 - RR + rr, w0 - RR + 4 * cu, h, w);
+            const float4 v = load_unit_raw<REFLECT || POST>(p, h0 - RR + hrr[k], w0 - RR + 4 * hcu[k], h, w);
             if (pass) eh[k] = v; else xh[k] = v;
         }
     }
@@ -349,12 +432,8 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
         const int u = threadIdx.x + k * NT, row = u >> 4, cu = u & 15;
         float4 val = xi[k];
         if constexpr (POST) {
-            bool b0, b1, b2, b3;
             float4 x0, sm;
-            x0.x = post_x0(xi[k].x, ei[k].x, a.k, b0);
-            x0.y = post_x0(xi[k].y, ei[k].y, a.k, b1);
-            x0.z = post_x0(xi[k].z, ei[k].z, a.k, b2);
-            x0.w = post_x0(xi[k].w, ei[k].w, a.k, b3);
+            uchar4 gate;
             float4 zk = make_float4(0, 0, 0, 0);
             if constexpr (RNG) {     // the unit's index inside the particle: (channel plane, row, column) / 4
                 if (a.k.add_noise & 1)
@@ -363,34 +442,26 @@ __device__ __forceinline__ void load_region_reg(float *s, const int h0, const in
             } else {
                 zk = zi[k];
             }
-            sm.x = post_sample(xi[k].x, x0.x, vi[k].x, zk.x, a.k);
-            sm.y = post_sample(xi[k].y, x0.y, vi[k].y, zk.y, a.k);
-            sm.z = post_sample(xi[k].z, x0.z, vi[k].z, zk.z, a.k);
-            sm.w = post_sample(xi[k].w, x0.w, vi[k].w, zk.w, a.k);
+            post_unit(xi[k], ei[k], vi[k], zk, a.k, x0, sm, gate);     // packed S1, bit for bit post_x0 / post_sample
             const int64_t o = (int64_t)plane * hw + (unsigned)((h0 + row) * w + w0 + 4 * cu);
             if (a.x0_hat) *reinterpret_cast<float4 *>(a.x0_hat + o) = x0;          // launch-uniform: optional output
             *reinterpret_cast<float4 *>(a.sample + o) = sm;
-            *reinterpret_cast<uchar4 *>(a.inside_w + o) = make_uchar4(b0, b1, b2, b3);
+            *reinterpret_cast<uchar4 *>(a.inside_w + o) = gate;
             val = x0;
         }
         *reinterpret_cast<float4 *>(s + (RR + row) * G::SW + RR + 4 * cu) = val;
     }
     // ---- halo: x0_hat recomputed from the neighbours' x_t / eps (served by L2)
+    // K1 sits at its register budget with four streams of interior units in flight: there the (cheap) map is evaluated
+    // again from an opaque copy of the thread index instead of staying live across the loads
+    if constexpr (POST) halo_units_deal<RR>(tid, hrr, hcu);
 #pragma unroll
     for (int k = 0; k < NH; ++k) {
-        const int hu = threadIdx.x + k * NT;
-        if (hu >= G::HALO) continue;
-        int rr, cu;
-        halo_unit<RR>(hu, rr, cu);
+        if (k * NT + NT > G::HALO && (int)threadIdx.x + k * NT >= G::HALO) continue;     // only the last deal is partial
         float4 val = xh[k];
-        if constexpr (POST) {
-            bool b;
-            val.x = post_x0(xh[k].x, eh[k].x, a.k, b);
-            val.y = post_x0(xh[k].y, eh[k].y, a.k, b);
-            val.z = post_x0(xh[k].z, eh[k].z, a.k, b);
-            val.w = post_x0(xh[k].w, eh[k].w, a.k, b);
-        }
-        *reinterpret_cast<float4 *>(s + rr * G::SW + 4 * cu) = val;
+        if constexpr (POST) val = post_x0_unit(xh[k], eh[k], a.k);      // elementwise: x_t and eps reverse together, afterwards
+        if constexpr (REFLECT || POST) val = unit_unmirror(val, unit_mirrored(w0 - RR + 4 * hcu[k], w));
+        *reinterpret_cast<float4 *>(s + hrr[k] * G::SW + 4 * hcu[k]) = val;
     }
 }
 
@@ -566,6 +637,40 @@ constexpr int sep_waves_per_simd(int r4, bool light = false)
 }
 constexpr int sep_adj_waves_per_simd(int r4) { return r4 <= 6 ? sep_waves_per_simd(r4) : 1; }
 
+// Fused adjoint epilogue of a lane's 4 x 4 outputs (regular geometry): g_model_out = gate ? -b (coef acc + extra) : +0.
+// EXTRA: the launch has an extra cotangent on x0_hat (the semantic term; rides the same gate).  Without one the term is the
+// constant +0.0, which is STILL ADDED: coef * acc = -0.0 becomes +0.0 there, so dropping the add would flip the sign of a
+// zero; as an inline constant it costs no load and no register.  Two outputs per v_pk_mul_f32 / v_pk_add_f32, which round
+// each element as the scalar forms do (no contraction), so both forms give the bits of the scalar expression.
+template <bool EXTRA>
+__device__ __forceinline__ void adj_gate_epilogue(const BlurArgs &a, const int plane, const unsigned o, const float (&acc)[4][4],
+                                                  const uchar4 (&gate)[4], const float coef)
+{
+    const unsigned hw = (unsigned)(a.h * a.w);
+    const int n = plane / a.c, ch = plane % a.c;
+    float *gp = a.g_model_out + ((int64_t)n * 2 * a.c + ch) * hw + o;
+    const v2f mb2{-a.k.b, -a.k.b}, c2{coef, coef};
+    float4 ex[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ex[i] = make_float4(0, 0, 0, 0);
+    if constexpr (EXTRA) {
+        const float *ep = a.g_extra + (int64_t)plane * hw + o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ex[i] = *reinterpret_cast<const float4 *>(ep + (unsigned)(i * a.w));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const v2f lo = mb2 * (c2 * v2f{acc[i][0], acc[i][1]} + v2f{ex[i].x, ex[i].y});
+        const v2f hi = mb2 * (c2 * v2f{acc[i][2], acc[i][3]} + v2f{ex[i].z, ex[i].w});
+        float4 g;
+        g.x = gate[i].x ? lo.x : 0.0f;
+        g.y = gate[i].y ? lo.y : 0.0f;
+        g.z = gate[i].z ? hi.x : 0.0f;
+        g.w = gate[i].w ? hi.y : 0.0f;
+        *reinterpret_cast<float4 *>(gp + (unsigned)(i * a.w)) = g;
+    }
+}
+
 // RNG: K1 with the noise drawn in the kernel; launched for regular geometry only (blur.hip: blur_step_draws_in_kernel)
 template <int R4, bool POST, bool RESID, bool RNG = false>
 __global__ __launch_bounds__(NT, sep_waves_per_simd(R4, !POST && !RESID)) void k_blur_sep_fwd(BlurArgs a, SepTaps taps)
@@ -638,7 +743,8 @@ __global__ __launch_bounds__(NT, sep_waves_per_simd(R4, !POST && !RESID)) void k
 // terms into LDS words the horizontal pass left dead (columns 64.. of rows 0..2RR-1).  Other geometries
 // (tiny or ragged images) take the generic slow folds.
 
-template <int R4, bool EPI>
+// EXTRA (EPI only): the launch carries an extra cotangent (a.g_extra != nullptr, chosen at launch): adj_gate_epilogue
+template <int R4, bool EPI, bool EXTRA = false>
 __global__ __launch_bounds__(NT, sep_adj_waves_per_simd(R4)) void k_blur_sep_adj(BlurArgs a, SepTaps taps, int reach)
 {
     constexpr int RR = 4 * R4;
@@ -776,29 +882,7 @@ __global__ __launch_bounds__(NT, sep_adj_waves_per_simd(R4)) void k_blur_sep_adj
     }
     const int ox = w0 + 4 * cg;
     if (EPI && regular) {
-        if (!ABL(8)) {
-            const unsigned hw = (unsigned)(a.h * a.w), o = (unsigned)((h0 + 4 * rg) * a.w + ox);
-            const int n = plane / a.c, ch = plane % a.c;
-            float *gp = a.g_model_out + ((int64_t)n * 2 * a.c + ch) * hw + o;
-            const float mb = -a.k.b;
-            float4 ex[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ex[i] = make_float4(0, 0, 0, 0);
-            if (a.g_extra) {            // block-uniform: the semantic term's cotangent on x0_hat rides the same gate
-                const float *ep = a.g_extra + (int64_t)plane * hw + o;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ex[i] = *reinterpret_cast<const float4 *>(ep + (unsigned)(i * a.w));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float4 g;
-                g.x = gate[i].x ? mb * (coef * acc[i][0] + ex[i].x) : 0.0f;
-                g.y = gate[i].y ? mb * (coef * acc[i][1] + ex[i].y) : 0.0f;
-                g.z = gate[i].z ? mb * (coef * acc[i][2] + ex[i].z) : 0.0f;
-                g.w = gate[i].w ? mb * (coef * acc[i][3] + ex[i].w) : 0.0f;
-                *reinterpret_cast<float4 *>(gp + (unsigned)(i * a.w)) = g;
-            }
-        }
+        if (!ABL(8)) adj_gate_epilogue<EXTRA>(a, plane, (unsigned)((h0 + 4 * rg) * a.w + ox), acc, gate, coef);
     } else if (ox < a.w && !ABL(8)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) out_epilogue<true>(a, plane, h0 + 4 * rg + i, ox, acc[i], coef, EPI);
@@ -815,7 +899,7 @@ __global__ __launch_bounds__(NT, sep_adj_waves_per_simd(R4)) void k_blur_sep_adj
 // FORWARD pipeline on the cotangent -- reflecting loader, plain passes -- plus a x2 on one staged row / column of the
 // border tiles and a x0.5 on their outermost outputs (both exact), instead of up to RR extra FMAs per border pixel and
 // axis under divergence: at 256 x 256, twelve of the sixteen tiles of a plane are border tiles.
-template <int R4, bool EPI>
+template <int R4, bool EPI, bool EXTRA = false>
 __global__ __launch_bounds__(NT, sep_adj_waves_per_simd(R4)) void k_blur_sep_adj_sym(BlurArgs a, SepTaps taps)
 {
     constexpr int RR = 4 * R4;
@@ -872,27 +956,7 @@ __global__ __launch_bounds__(NT, sep_adj_waves_per_simd(R4)) void k_blur_sep_adj
         }
     }
     if constexpr (EPI) {
-        const unsigned hw = (unsigned)(a.h * a.w), o = (unsigned)(oy * a.w + ox);
-        const int n = plane / a.c, ch = plane % a.c;
-        float *gp = a.g_model_out + ((int64_t)n * 2 * a.c + ch) * hw + o;
-        const float mb = -a.k.b;
-        float4 ex[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ex[i] = make_float4(0, 0, 0, 0);
-        if (a.g_extra) {            // block-uniform: the semantic term's cotangent on x0_hat rides the same gate
-            const float *ep = a.g_extra + (int64_t)plane * hw + o;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ex[i] = *reinterpret_cast<const float4 *>(ep + (unsigned)(i * a.w));
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float4 g;
-            g.x = gate[i].x ? mb * (coef * acc[i][0] + ex[i].x) : 0.0f;
-            g.y = gate[i].y ? mb * (coef * acc[i][1] + ex[i].y) : 0.0f;
-            g.z = gate[i].z ? mb * (coef * acc[i][2] + ex[i].z) : 0.0f;
-            g.w = gate[i].w ? mb * (coef * acc[i][3] + ex[i].w) : 0.0f;
-            *reinterpret_cast<float4 *>(gp + (unsigned)(i * a.w)) = g;
-        }
+        adj_gate_epilogue<EXTRA>(a, plane, (unsigned)(oy * a.w + ox), acc, gate, coef);
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) out_epilogue<true>(a, plane, oy + i, ox, acc[i], coef, false);
