@@ -47,7 +47,7 @@ int dpsx_posterior_fwd_f32(const float *x_t, const float *model_out, const float
     if (n == 0 || chw == 0) return DPSX_OK;   // empty particle set: nothing to do (pointers may be null)
     if (!x_t || !model_out) return DPSX_EINVAL;
     if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    return posterior_fwd(x_t, model_out, noise, x0_hat, sample, inside, n, chw, to_coefs(coefs_host),
+    return posterior_fwd(x_t, model_out, noise, false, RngK{}, x0_hat, sample, inside, n, chw, to_coefs(coefs_host),
                          (hipStream_t)stream);
 }
 
@@ -97,8 +97,8 @@ int dpsx_posterior_fwd_rng_f32(const float *x_t, const float *model_out, const d
     if (rc != DPSX_OK) return rc;
     if (n == 0 || chw == 0) return DPSX_OK;
     if (!x_t || !model_out) return DPSX_EINVAL;
-    return posterior_fwd_rng(x_t, model_out, r, x0_hat, sample, inside, n, chw, to_coefs(coefs_host),
-                             (hipStream_t)stream);
+    return posterior_fwd(x_t, model_out, nullptr, true, r, x0_hat, sample, inside, n, chw, to_coefs(coefs_host),
+                         (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ operator objects
@@ -614,8 +614,7 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
         rc = mask_step_fwd(op, a, parts, s);
         break;
     case OP_IDENT:
-        rc = rng ? posterior_fwd_rng(x_t, model_out, rk, x0_hat, sample, inside, n, chw, k, s)
-                 : posterior_fwd(x_t, model_out, noise, x0_hat, sample, inside, n, chw, k, s);
+        rc = posterior_fwd(x_t, model_out, noise, a.use_rng, rk, x0_hat, sample, inside, n, chw, k, s);
         if (rc != DPSX_OK) return rc;
         parts = 64;
         rc = residual_partials(y, y_n, x0_hat, static_cast<float *>(resid), ws.partials, n, chw, parts, s, 0, a.tail);
@@ -802,7 +801,72 @@ static int score_impl(dpsx_op *op, const float *x, const float *y, int64_t y_n, 
     hipStream_t s = (hipStream_t)stream;
     const int parts = score_parts(op, c, h, w);
     if ((rc = score_launch(op, ws, x, y, y_n, l1, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    return finalize_select(score_tail(ws, parts, l1, prev, potential, raw_out, costs, best_idx, best_val, n, c * h * w), s);
+    return finalize_select(score_tail(ws, parts, l1, prev, potential, raw_out, costs, best_idx, best_val, n, c * h * w), 1, s);
+}
+
+// ------------------------------------------------------------------ the search_ddpm step
+// The one argument check of the search step.  segments == 0: unsegmented (y rows as everywhere else); segments >= 1: a
+// multi-image batch of `segments` images x n / segments particles, y holds one row (broadcast) or one per image.
+static int search_seg_args(const dpsx_op *op, const float *x_t, const float *model_out, const void *noise, const float *y,
+                           int64_t y_n, const float *sample, const float *costs, const int64_t *best_idx_dev,
+                           const float *x_next, int64_t segments, bool one_state, int64_t n, int64_t c, int64_t h,
+                           int64_t w, const dpsx_coefs *coefs_host)
+{
+    int rc = check_geom(op, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
+    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
+    if (n == 0 || segments < 0) return DPSX_EINVAL;
+    if (segments ? n % segments != 0 || (y_n != 1 && y_n != segments) : !rows_ok(y_n, n)) return DPSX_EINVAL;
+    // dpsx_search_step_f32 alone accepts x_next == x_t (the replication runs after S1 has read every state)
+    if (x_next == sample || (x_next == x_t && (segments || one_state))) return DPSX_EINVAL;
+    return DPSX_OK;
+}
+
+// All six exported search steps.  noise / rng: the source of S1's noise (rng != NULL: drawn inside S1's launch, noise is
+// then NULL).  segments: 0 = one particle set; M >= 1 = M images of n / M particles, the select runs per image and
+// best_idx_dev / best_val_dev are [M].  one_state: x_t / model_out hold ONE state per image instead of one per particle.
+static int search_step_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const dpsx_rng *rng,
+                            const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
+                            float *best_val_dev, float *x_next, int64_t segments, bool one_state, int64_t n, int64_t c,
+                            int64_t h, int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
+                            void *stream)
+{
+    int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
+                             best_idx_dev, x_next, segments, one_state, n, c, h, w, coefs_host);
+    if (rc != DPSX_OK) return rc;
+    RngK rk{};
+    if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
+    // S1 (no x0_hat store) -> scoring launch -> one launch for costs + select -> the winner's replication.
+    // Measured and dropped (N = 64, Gaussian, 89.7 us for this sequence): S1 fused into the separable scoring kernel (the
+    // proposal's halo needs all four input streams: 72 us for the fused launch against 37 + 30 for the two); costs +
+    // select + replication in one launch (92.5 us per step); the particles in 2 / 3 / 4 chunks with the (latency-bound)
+    // scoring of chunk k on a second stream beside the (bandwidth-bound) S1 of chunk k + 1, forked and joined by events:
+    // 94.8 / 100.8 / 113.6 us -- the cross-stream dependencies cost more than the overlap returns.
+    // one_state: after a select every particle of SearchDDPM is a copy of the winner (img[best_path.repeat(n_paths)],
+    // :633), so the loop's state is ONE particle per image: S1 reads that state and its model output once for all its
+    // proposals (proposal p reads state p / (n / images); the per-particle noise makes them differ), the scoring launch
+    // and the select are the n-particle ones, and each winner is copied out once instead of n / images times: 3P of
+    // traffic per particle-step (noise in, proposal out, proposal scored) instead of the 8P of the replicated form --
+    // and one model evaluation per step instead of n for the caller.
+    Ws ws;
+    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chw = c * h * w;
+    const int64_t images = std::max<int64_t>(segments, 1);
+    const int parts = score_parts(op, c, h, w);
+    rc = posterior_fwd(x_t, model_out, noise, rng != nullptr, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s,
+                       one_state, images);
+    if (rc != DPSX_OK) return rc;
+    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
+    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
+    static const bool unfused = getenv("DPSX_SEARCH_ONE_UNFUSED") != nullptr;       // A/B switch for tools/kbench_search.py
+    if (one_state && !unfused && x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))
+        return finalize_select_copy(tail, (int)images, sample, x_next, chw, s);   // costs + select + the winners' copies: one launch
+    rc = finalize_select(tail, (int)images, s);
+    if (rc != DPSX_OK || !x_next) return rc;
+    if (one_state) return gather_f32(sample, best_idx_dev, x_next, images, n, chw, s);
+    return replicate_seg_f32(sample, best_idx_dev, x_next, n, n / images, n, chw, s);
 }
 
 int dpsx_search_step_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
@@ -810,28 +874,8 @@ int dpsx_search_step_f32(dpsx_op *op, const float *x_t, const float *model_out, 
                          float *x_next, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
                          void *workspace, int64_t workspace_bytes, void *stream)
 {
-    int rc = check_geom(op, n, c, h, w);
-    if (rc != DPSX_OK) return rc;
-    if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
-    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if (!rows_ok(y_n, n) || n == 0 || x_next == sample) return DPSX_EINVAL;
-    // S1 (no x0_hat store) -> scoring launch -> one launch for costs + select -> the winner's replication.
-    // Measured and dropped (N = 64, Gaussian, 89.7 us for this sequence): S1 fused into the separable scoring kernel (the
-    // proposal's halo needs all four input streams: 72 us for the fused launch against 37 + 30 for the two); costs +
-    // select + replication in one launch (92.5 us per step); the particles in 2 / 3 / 4 chunks with the (latency-bound)
-    // scoring of chunk k on a second stream beside the (bandwidth-bound) S1 of chunk k + 1, forked and joined by events:
-    // 94.8 / 100.8 / 113.6 us -- the cross-stream dependencies cost more than the overlap returns.
-    Ws ws;
-    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t chw = c * h * w;
-    const int parts = score_parts(op, c, h, w);
-    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s);
-    if (rc != DPSX_OK) return rc;
-    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    rc = finalize_select(score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw), s);
-    if (rc != DPSX_OK || !x_next) return rc;
-    return gather_f32(sample, best_idx_dev, x_next, n, n, chw, true, s);
+    return search_step_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev, x_next,
+                            0, false, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
 }
 
 int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
@@ -839,84 +883,19 @@ int dpsx_search_step_one_f32(dpsx_op *op, const float *x_t, const float *model_o
                              float *x_next, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
                              void *workspace, int64_t workspace_bytes, void *stream)
 {
-    int rc = check_geom(op, n, c, h, w);
-    if (rc != DPSX_OK) return rc;
-    if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
-    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if (!rows_ok(y_n, n) || n == 0 || x_next == sample || x_next == x_t) return DPSX_EINVAL;
-    // After a select every particle of SearchDDPM is a copy of the winner (img[best_path.repeat(n_paths)], :633), so the
-    // loop's state is ONE particle: S1 reads that state and its model output once for all n proposals (the per-particle
-    // noise makes them differ), the scoring launch and the select are the n-particle ones, and the winner is copied out
-    // once instead of n times: 3P of traffic per particle-step (noise in, proposal out, proposal scored) instead of the
-    // 8P of the replicated form -- and one model evaluation per step instead of n for the caller.
-    Ws ws;
-    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t chw = c * h * w;
-    const int parts = score_parts(op, c, h, w);
-    rc = posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true);
-    if (rc != DPSX_OK) return rc;
-    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
-    static const bool unfused = getenv("DPSX_SEARCH_ONE_UNFUSED") != nullptr;       // A/B switch for tools/kbench_search.py
-    if (!unfused && x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))   // costs + select + the one copy: one launch
-        return finalize_select_copy(tail, sample, x_next, chw, s);
-    rc = finalize_select(tail, s);
-    if (rc != DPSX_OK || !x_next) return rc;
-    return gather_f32(sample, best_idx_dev, x_next, 1, n, chw, true, s);
+    return search_step_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev, x_next,
+                            0, true, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
 }
 
-// ------------------------------------------------------------------ multi-image search (segments of n / segments particles)
-// The argument checks of both segmented steps; y holds one row (broadcast) or one per segment.
-static int search_seg_args(const dpsx_op *op, const float *x_t, const float *model_out, const void *noise, const float *y,
-                           int64_t y_n, const float *sample, const float *costs, const int64_t *best_idx_dev,
-                           const float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
-                           const dpsx_coefs *coefs_host)
-{
-    int rc = check_geom(op, n, c, h, w);
-    if (rc != DPSX_OK) return rc;
-    if (!x_t || !model_out || !y || !sample || !costs || !best_idx_dev || !coefs_host) return DPSX_EINVAL;
-    if ((coefs_host->add_noise & 1) && !noise) return DPSX_EINVAL;
-    if (n == 0 || segments < 1 || n % segments != 0 || (y_n != 1 && y_n != segments)) return DPSX_EINVAL;
-    if (x_next == sample || x_next == x_t) return DPSX_EINVAL;
-    return DPSX_OK;
-}
-
-static int search_step_seg_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
-                                const dpsx_rng *rng, const float *y,
-                             int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev, float *best_val_dev,
-                             float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
-                             const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
-                             best_idx_dev, x_next, segments, n, c, h, w, coefs_host);
-    if (rc != DPSX_OK) return rc;
-    RngK rk{};
-    if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
-    // the launches of dpsx_search_step_f32; the select runs one block per segment and the replication copies each
-    // segment's winner over that segment's particles
-    Ws ws;
-    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t chw = c * h * w;
-    const int parts = score_parts(op, c, h, w);
-    rc = rng ? posterior_fwd_rng(x_t, model_out, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s)
-             : posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s);
-    if (rc != DPSX_OK) return rc;
-    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
-    rc = finalize_select_seg(tail, (int)segments, s);
-    if (rc != DPSX_OK || !x_next) return rc;
-    return replicate_seg_f32(sample, best_idx_dev, x_next, n, n / segments, n, chw, s);
-}
-
+// multi-image forms (segments of n / segments particles): a segment count below 1 is refused here, 0 being the
+// unsegmented step of the shared body
 int dpsx_search_step_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const float *y,
                              int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev, float *best_val_dev,
                              float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h, int64_t w,
                              const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    return search_step_seg_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev,
-                                x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
+    return search_step_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev, x_next,
+                            segments < 1 ? -1 : segments, false, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
 }
 
 int dpsx_search_step_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
@@ -926,38 +905,9 @@ int dpsx_search_step_seg_rng_f32(dpsx_op *op, const float *x_t, const float *mod
                                  void *stream)
 {
     if (!rng_host) return DPSX_EINVAL;
-    return search_step_seg_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev, best_val_dev,
-                                x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
-}
-
-static int search_step_one_seg_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
-                                    const dpsx_rng *rng,
-                                 const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
-                                 float *best_val_dev, float *x_next, int64_t segments, int64_t n, int64_t c, int64_t h,
-                                 int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
-                                 void *stream)
-{
-    int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
-                             best_idx_dev, x_next, segments, n, c, h, w, coefs_host);
-    if (rc != DPSX_OK) return rc;
-    RngK rk{};
-    if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
-    // one state per segment: proposal p reads state p / (n / segments); x_next receives each segment's winner once
-    Ws ws;
-    if ((rc = carve(op, workspace, workspace_bytes, n, c, h, w, ws)) != DPSX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t chw = c * h * w;
-    const int parts = score_parts(op, c, h, w);
-    rc = rng ? posterior_fwd_rng(x_t, model_out, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments)
-             : posterior_fwd(x_t, model_out, noise, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s, true, segments);
-    if (rc != DPSX_OK) return rc;
-    if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
-    if (x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))   // costs + select + the winners' copies: one launch
-        return finalize_select_copy_seg(tail, (int)segments, sample, x_next, chw, s);
-    rc = finalize_select_seg(tail, (int)segments, s);
-    if (rc != DPSX_OK || !x_next) return rc;
-    return gather_f32(sample, best_idx_dev, x_next, segments, n, chw, false, s);
+    return search_step_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev, best_val_dev,
+                            x_next, segments < 1 ? -1 : segments, false, n, c, h, w, coefs_host, workspace,
+                            workspace_bytes, stream);
 }
 
 int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
@@ -966,8 +916,8 @@ int dpsx_search_step_one_seg_f32(dpsx_op *op, const float *x_t, const float *mod
                                  int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
                                  void *stream)
 {
-    return search_step_one_seg_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev,
-                                    x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
+    return search_step_impl(op, x_t, model_out, noise, nullptr, y, y_n, sample, costs, best_idx_dev, best_val_dev, x_next,
+                            segments < 1 ? -1 : segments, true, n, c, h, w, coefs_host, workspace, workspace_bytes, stream);
 }
 
 int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float *model_out, const dpsx_rng *rng_host,
@@ -977,9 +927,9 @@ int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float 
                                      int64_t workspace_bytes, void *stream)
 {
     if (!rng_host) return DPSX_EINVAL;
-    return search_step_one_seg_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev,
-                                    best_val_dev, x_next, segments, n, c, h, w, coefs_host, workspace, workspace_bytes,
-                                    stream);
+    return search_step_impl(op, x_t, model_out, nullptr, rng_host, y, y_n, sample, costs, best_idx_dev, best_val_dev,
+                            x_next, segments < 1 ? -1 : segments, true, n, c, h, w, coefs_host, workspace, workspace_bytes,
+                            stream);
 }
 
 int dpsx_score_f32(dpsx_op *op, const float *x, const float *y, int64_t y_n, float *costs, int64_t n, int64_t c,
@@ -1010,7 +960,7 @@ int dpsx_resample_cost_f32(dpsx_op *op, const float *x, const float *y, int64_t 
 int dpsx_argmin_f32(const float *v, int64_t n, int64_t *idx_out_dev, float *val_out_dev, void *stream)
 {
     if (!v || !idx_out_dev || n < 1) return DPSX_EINVAL;
-    return argmin_f32(v, n, idx_out_dev, val_out_dev, (hipStream_t)stream);
+    return argmin_seg_f32(v, 1, n, idx_out_dev, val_out_dev, (hipStream_t)stream);
 }
 
 int dpsx_argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx_out_dev, float *val_out_dev,
@@ -1026,7 +976,7 @@ int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst, int64_
     if (n_out < 0 || chw < 0) return DPSX_EINVAL;
     if (n_out == 0 || chw == 0) return DPSX_OK;
     if (!src || !ids_dev || !dst || n_src < 1 || src == dst) return DPSX_EINVAL;
-    return gather_f32(src, ids_dev, dst, n_out, n_src, chw, false, (hipStream_t)stream);
+    return gather_f32(src, ids_dev, dst, n_out, n_src, chw, (hipStream_t)stream);
 }
 
 int dpsx_replicate_f32(const float *src, const int64_t *idx_dev, float *dst, int64_t n_out, int64_t n_src,
@@ -1035,7 +985,7 @@ int dpsx_replicate_f32(const float *src, const int64_t *idx_dev, float *dst, int
     if (n_out < 0 || chw < 0) return DPSX_EINVAL;
     if (n_out == 0 || chw == 0) return DPSX_OK;
     if (!src || !idx_dev || !dst || n_src < 1 || src == dst) return DPSX_EINVAL;
-    return gather_f32(src, idx_dev, dst, n_out, n_src, chw, true, (hipStream_t)stream);
+    return replicate_seg_f32(src, idx_dev, dst, n_out, n_out, n_src, chw, (hipStream_t)stream);     // one id for all rows
 }
 
 // shared argument checks of the two resampling entry points

@@ -551,11 +551,11 @@ int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n,
 // elementwise.hip
 // one_state: x [states, chw] and mo [states, 2 chw] feed all n particles, n / states consecutive particles per state
 // (z, x0, sample, inside stay per particle)
-int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, float *sample, uint8_t *inside,
-                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false, int64_t states = 1);
-// the same launch with the noise drawn in the kernel (common.h: rng_unit)
-int posterior_fwd_rng(const float *x, const float *mo, const RngK &r, float *x0, float *sample, uint8_t *inside,
-                      int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false, int64_t states = 1);
+// the noise: read from z, or with use_rng drawn in the kernel from r (common.h: rng_unit; z is then not read) -- the
+// trio StepFwdArgs carries
+int posterior_fwd(const float *x, const float *mo, const float *z, bool use_rng, const RngK &r, float *x0, float *sample,
+                  uint8_t *inside, int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state = false,
+                  int64_t states = 1);
 // out [n, chw] normals of the counters (unit, particle id of row p, r.step, r.tag); bits (nullable) [n, 4 ceil(chw / 4)]
 int randn_f32(float *out, uint32_t *bits, int64_t n, int64_t chw, const RngK &r, hipStream_t s);
 int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const float *mo, const float *z,
@@ -569,13 +569,11 @@ int residual_partials(const float *y, int64_t y_n, const float *ax, float *r, fl
                       const float *mask = nullptr, int64_t hw = 0, int64_t mask_n = 1);
 int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipStream_t s);
 // one small launch: per-particle values from the partials (t.partials / parts / mode / prev / potential -> raw_out, out)
-// and, if t.best_idx, the torch.argmin-order select over them (t.counters is not used)
-int finalize_select(const Tail &t, hipStream_t s);
-int finalize_select_copy(const Tail &t, const float *src, float *dst, int64_t chw, hipStream_t s);
-// the same per segment: `segments` consecutive groups of t.n / segments particles; t.best_idx / t.best_val are [segments]
+// and, if t.best_idx, the torch.argmin-order select over them (t.counters is not used).  The select runs per segment:
+// `segments` consecutive groups of t.n / segments particles (1: the whole set); t.best_idx / t.best_val are [segments]
 // and receive each segment's winner as a global particle index.  _copy: dst[m] = src[best[m]] (chw % 4 == 0, aligned)
-int finalize_select_seg(const Tail &t, int segments, hipStream_t s);
-int finalize_select_copy_seg(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
+int finalize_select(const Tail &t, int segments, hipStream_t s);
+int finalize_select_copy(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
 // segmented argmin over v [segments, k] -> idx[m] = m * k + argmin (torch.argmin order), val[m] (nullable)
 int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s);
 // dst[p] = src[ids[p / per]] for p < n_out (per = particles per id); an id outside [0, n_src) fills dst[p] with NaN
@@ -592,9 +590,7 @@ int step_update(const float *sample, const float *g_mo, const float *g_unet, flo
 int plain_update(const float *sample, const float *ga, const float *gb, float *out, int64_t count, hipStream_t s);
 int mask_step_fwd(const dpsx_op *op, const StepFwdArgs &a, int parts, hipStream_t s);
 int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s);
-int argmin_f32(const float *v, int64_t n, int64_t *idx, float *val, hipStream_t s);
-int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw,
-               bool replicate, hipStream_t s);
+int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw, hipStream_t s);
 // the per-segment resampling draw (include/dpsx.h): d, u [segments * k]; ids [segments * k] global particle indices,
 // q_out (nullable) the integer weights.  resample_seg_f32: the draw + dst[p] = src[ids[p]] + d_out[p] = d[ids[p]] in one
 // launch (chw >= 1, src and dst do not alias; the caller checked k <= 4096 and the grid limits)

@@ -76,31 +76,18 @@ __global__ __launch_bounds__(kThreads) void k_posterior_fwd(const float *__restr
     }
 }
 
-int posterior_fwd(const float *x, const float *mo, const float *z, float *x0, float *sample, uint8_t *inside,
-                  int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state, int64_t states)
+int posterior_fwd(const float *x, const float *mo, const float *z, bool use_rng, const RngK &r, float *x0, float *sample,
+                  uint8_t *inside, int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state, int64_t states)
 {
     if (n == 0 || chw == 0) return DPSX_OK;
     const unsigned xs = one_state ? row_div(states, n) : 1u;
-    const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && aligned16(z) && aligned16(x0) &&
+    const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && (use_rng || aligned16(z)) && aligned16(x0) &&
                      aligned16(sample) && (reinterpret_cast<uintptr_t>(inside) & 3u) == 0;
-    if (vec)
-        k_posterior_fwd<true><<<grid_for(chw / 4, n), kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
-    else
-        k_posterior_fwd<false><<<grid_for(chw, n), kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
-    return check_launch();
-}
-
-int posterior_fwd_rng(const float *x, const float *mo, const RngK &r, float *x0, float *sample, uint8_t *inside,
-                      int64_t n, int64_t chw, const Coefs &k, hipStream_t s, bool one_state, int64_t states)
-{
-    if (n == 0 || chw == 0) return DPSX_OK;
-    const unsigned xs = one_state ? row_div(states, n) : 1u;
-    const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && aligned16(x0) && aligned16(sample) &&
-                     (reinterpret_cast<uintptr_t>(inside) & 3u) == 0;
-    if (vec)
-        k_posterior_fwd<true, true><<<grid_for(chw / 4, n), kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
-    else
-        k_posterior_fwd<false, true><<<grid_for(chw, n), kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
+    const dim3 grid = grid_for(vec ? chw / 4 : chw, n);
+    if (vec && use_rng) k_posterior_fwd<true, true><<<grid, kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
+    else if (vec) k_posterior_fwd<true><<<grid, kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
+    else if (use_rng) k_posterior_fwd<false, true><<<grid, kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
+    else k_posterior_fwd<false><<<grid, kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
     return check_launch();
 }
 
@@ -383,32 +370,18 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
     return s_best;
 }
 
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t)
-{
-    (void)finalize_select_body(t, true, 0, t.n, 0);
-}
-
-// segmented: block m finishes and selects over particles [m k, (m + 1) k)
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select_seg(Tail t, int k)
+// block m finishes and selects over the particles [m k, (m + 1) k) of segment m (one block and k = t.n: the whole set)
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t, int k)
 {
     const int m = blockIdx.x;
     (void)finalize_select_body(t, true, m * k, (m + 1) * k, m);
 }
 
-// the same + ONE copy of the winner (the single-state search step: dpsx_search_step_one_f32): every block of the copy
-// finishes the costs and the select for itself (n * parts floats from the L2 -- 12 KB at N = 64) and copies its slice;
+// the same + ONE copy of each segment's winner (the single-state search step): block (x, m) finishes segment m's costs
+// and select for itself (k * parts floats from the L2 -- 12 KB at N = 64) and copies slice x of its winner to dst[m];
 // one launch and one launch boundary less than finalisation + dpsx_replicate_f32(n_out = 1)
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(Tail t, const float *__restrict__ src,
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(Tail t, int k, const float *__restrict__ src,
                                                                       float *__restrict__ dst, int64_t chw4)
-{
-    const int64_t b = finalize_select_body(t, blockIdx.x == 0, 0, t.n, 0);
-    const int64_t i = (int64_t)blockIdx.x * kSelThreads + threadIdx.x;
-    if (i < chw4) reinterpret_cast<float4 *>(dst)[i] = (reinterpret_cast<const float4 *>(src) + b * chw4)[i];
-}
-
-// segmented: block (x, m) finishes segment m's costs and select and copies slice x of its winner to dst[m]
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy_seg(Tail t, int k, const float *__restrict__ src,
-                                                                          float *__restrict__ dst, int64_t chw4)
 {
     const int m = blockIdx.y;
     const int64_t b = finalize_select_body(t, blockIdx.x == 0, m * k, (m + 1) * k, m);
@@ -417,34 +390,19 @@ __global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy_seg(Tail t
         (reinterpret_cast<float4 *>(dst) + (int64_t)m * chw4)[i] = (reinterpret_cast<const float4 *>(src) + b * chw4)[i];
 }
 
-int finalize_select(const Tail &t, hipStream_t s)
+int finalize_select(const Tail &t, int segments, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
-    k_finalize_select<<<1, kSelThreads, 0, s>>>(t);
+    k_finalize_select<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments);
     return check_launch();
 }
 
-int finalize_select_seg(const Tail &t, int segments, hipStream_t s)
-{
-    if (t.n == 0) return DPSX_OK;
-    k_finalize_select_seg<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments);
-    return check_launch();
-}
-
-int finalize_select_copy_seg(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s)
+int finalize_select_copy(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
     const int64_t chw4 = chw / 4;
     const dim3 grid((unsigned)((chw4 + kSelThreads - 1) / kSelThreads), (unsigned)segments);
-    k_finalize_select_copy_seg<<<grid, kSelThreads, 0, s>>>(t, t.n / segments, src, dst, chw4);
-    return check_launch();
-}
-
-int finalize_select_copy(const Tail &t, const float *src, float *dst, int64_t chw, hipStream_t s)
-{
-    if (t.n == 0) return DPSX_OK;
-    const int64_t chw4 = chw / 4;
-    k_finalize_select_copy<<<(unsigned)((chw4 + kSelThreads - 1) / kSelThreads), kSelThreads, 0, s>>>(t, src, dst, chw4);
+    k_finalize_select_copy<<<grid, kSelThreads, 0, s>>>(t, t.n / segments, src, dst, chw4);
     return check_launch();
 }
 
@@ -660,19 +618,20 @@ int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s)
 }
 
 // ===================================================================== select
-// torch.argmin: first minimum; NaN is the minimum.  One block; n is small (<= a few thousand).
+// torch.argmin: first minimum; NaN is the minimum.  One block per segment; k is small (<= a few thousand).
 // (value, index) pairs are reduced with a total order -- NaN before everything, then the smaller value, then the
 // smaller index -- by wave shuffles and one LDS hop, so the result does not depend on the reduction shape.
 // (ArgMin / argmin_better: common.h, shared with the in-launch tail)
-// (the block's body; `base` is added to the stored index: the segmented form stores global indices)
-__device__ __forceinline__ void argmin_block(const float *__restrict__ v, int64_t n, int64_t *__restrict__ out,
-                                             float *__restrict__ val_out, int64_t base)
+// block m selects over v[m k .. (m + 1) k) and stores the global index (one segment: the plain argmin)
+__global__ __launch_bounds__(kThreads) void k_argmin_seg(const float *__restrict__ v, int64_t k, int64_t *__restrict__ out,
+                                                         float *__restrict__ val_out)
 {
     __shared__ float s_val[kThreads / kWave];
     __shared__ int64_t s_idx[kThreads / kWave];
+    const int64_t m = blockIdx.x;
     ArgMin best{0.0f, -1};
-    for (int64_t i = threadIdx.x; i < n; i += kThreads) {
-        const ArgMin c{v[i], i};
+    for (int64_t i = threadIdx.x; i < k; i += kThreads) {
+        const ArgMin c{v[m * k + i], i};
         if (argmin_better(c, best)) best = c;
     }
 #pragma unroll
@@ -690,29 +649,9 @@ __device__ __forceinline__ void argmin_block(const float *__restrict__ v, int64_
             const ArgMin c{s_val[w], s_idx[w]};
             if (argmin_better(c, best)) best = c;
         }
-        *out = base + (best.i < 0 ? 0 : best.i);
-        if (val_out) *val_out = best.v;
+        out[m] = m * k + (best.i < 0 ? 0 : best.i);
+        if (val_out) val_out[m] = best.v;
     }
-}
-
-__global__ __launch_bounds__(kThreads) void k_argmin(const float *__restrict__ v, int64_t n, int64_t *__restrict__ out,
-                                                     float *__restrict__ val_out)
-{
-    argmin_block(v, n, out, val_out, 0);
-}
-
-int argmin_f32(const float *v, int64_t n, int64_t *idx, float *val, hipStream_t s)
-{
-    k_argmin<<<1, kThreads, 0, s>>>(v, n, idx, val);
-    return check_launch();
-}
-
-// one block per segment: block m runs k_argmin over v[m k .. (m + 1) k) and stores the global index
-__global__ __launch_bounds__(kThreads) void k_argmin_seg(const float *__restrict__ v, int64_t k, int64_t *__restrict__ out,
-                                                         float *__restrict__ val_out)
-{
-    const int64_t m = blockIdx.x;
-    argmin_block(v + m * k, k, out + m, val_out ? val_out + m : nullptr, m * k);
 }
 
 int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s)
@@ -722,11 +661,10 @@ int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, fl
 }
 
 __global__ __launch_bounds__(kThreads) void k_gather(const float *__restrict__ src, const int64_t *__restrict__ ids,
-                                                     float *__restrict__ dst, int64_t n_src, int64_t chw4,
-                                                     int replicate)
+                                                     float *__restrict__ dst, int64_t n_src, int64_t chw4)
 {
     const int64_t p = blockIdx.y;
-    int64_t sidx = replicate ? ids[0] : ids[p];
+    const int64_t sidx = ids[p];
     float4 *d4 = reinterpret_cast<float4 *>(dst) + p * chw4;
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= chw4) return;
@@ -742,35 +680,18 @@ __global__ __launch_bounds__(kThreads) void k_gather(const float *__restrict__ s
 
 __global__ __launch_bounds__(kThreads) void k_gather_scalar(const float *__restrict__ src,
                                                             const int64_t *__restrict__ ids,
-                                                            float *__restrict__ dst, int64_t n_src, int64_t chw,
-                                                            int replicate)
+                                                            float *__restrict__ dst, int64_t n_src, int64_t chw)
 {
     const int64_t p = blockIdx.y;
-    int64_t sidx = replicate ? ids[0] : ids[p];
+    const int64_t sidx = ids[p];
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= chw) return;
     dst[p * chw + i] = (sidx < 0 || sidx >= n_src) ? __builtin_nanf("") : src[sidx * chw + i];
 }
 
-// dst[p] = src[*idx] for all p: a lane reads its float4 of the winner once and stores it to kRepl destinations
-// (one block per (slice, group of kRepl particles): 8x fewer, fatter blocks than one per destination particle)
+// replication (k_replicate_seg, k_select_champion): one block per (slice, group of kRepl destination particles) -- 8x
+// fewer, fatter blocks than one per destination particle
 constexpr int kRepl = 8;
-__global__ __launch_bounds__(kThreads) void k_replicate(const float *__restrict__ src, const int64_t *__restrict__ idx,
-                                                        float *__restrict__ dst, int64_t n_out, int64_t n_src,
-                                                        int64_t chw4)
-{
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= chw4) return;
-    const int64_t sidx = idx[0];
-    const float q = __builtin_nanf("");
-    const float4 v = (sidx < 0 || sidx >= n_src) ? make_float4(q, q, q, q)
-                                                 : (reinterpret_cast<const float4 *>(src) + sidx * chw4)[i];
-    const int64_t p0 = (int64_t)blockIdx.y * kRepl;
-    float4 *d4 = reinterpret_cast<float4 *>(dst) + p0 * chw4 + i;
-#pragma unroll
-    for (int k = 0; k < kRepl; ++k)
-        if (p0 + k < n_out) d4[(int64_t)k * chw4] = v;
-}
 
 // ---- the device half of the per-rank champion exchange (distributed.py: _exchange_champions)
 // pack: out[0 .. chw) = particles[best], out[chw] = value (costs[best] or *val), out[chw + 1] = (float)best, two zeros --
@@ -884,7 +805,9 @@ int select_champion(const float *table, int world, int64_t chw, float *dst, int6
     return check_launch();
 }
 
-// dst[p] = src[ids[p / per]]: each segment's winner replicated over its own particles (k_replicate per segment)
+// dst[p] = src[ids[p / per]]: each segment's winner replicated over its own particles (per = n_out: ONE winner over all).
+// Measured (profiles/search_unify_ab.txt): a kernel of its own for the one-winner case, which read the winner once per
+// kRepl destinations, was indistinguishable from this one at N = 64 and was removed.
 __global__ __launch_bounds__(kThreads) void k_replicate_seg(const float *__restrict__ src, const int64_t *__restrict__ ids,
                                                             float *__restrict__ dst, int64_t n_out, unsigned per,
                                                             int64_t n_src, int64_t chw4)
@@ -927,19 +850,13 @@ int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t 
     return check_launch();
 }
 
-int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw,
-               bool replicate, hipStream_t s)
+int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw, hipStream_t s)
 {
     if (n_out == 0 || chw == 0) return DPSX_OK;
-    if (replicate && chw % 4 == 0 && aligned16(src) && aligned16(dst)) {
-        const dim3 grid((unsigned)((chw / 4 + kThreads - 1) / kThreads), (unsigned)((n_out + kRepl - 1) / kRepl));
-        k_replicate<<<grid, kThreads, 0, s>>>(src, ids, dst, n_out, n_src, chw / 4);
-        return check_launch();
-    }
     if (chw % 4 == 0 && aligned16(src) && aligned16(dst))
-        k_gather<<<grid_for(chw / 4, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw / 4, replicate);
+        k_gather<<<grid_for(chw / 4, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw / 4);
     else
-        k_gather_scalar<<<grid_for(chw, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw, replicate);
+        k_gather_scalar<<<grid_for(chw, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw);
     return check_launch();
 }
 

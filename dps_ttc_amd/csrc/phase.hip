@@ -435,7 +435,7 @@ int phase_step_fwd(dpsx_op *op, const StepFwdArgs &f, float *resid_c, hipStream_
             f.x_t, f.model_out, f.noise, f.x0_hat, f.sample, f.inside, real, h, pad, sz, (int)c, f.k);
         rc = check_launch();
     } else {
-        rc = posterior_fwd(f.x_t, f.model_out, f.noise, f.x0_hat, f.sample, f.inside, n, c * h * h, f.k, s);
+        rc = posterior_fwd(f.x_t, f.model_out, f.noise, f.use_rng, f.rng, f.x0_hat, f.sample, f.inside, n, c * h * h, f.k, s);
         if (rc != DPSX_OK) return rc;
         k_phase_pre_real<<<dim3((sz * sz + PT - 1) / PT, (unsigned)planes), PT, 0, s>>>(f.x0_hat, real, h, pad, sz);
         rc = check_launch();

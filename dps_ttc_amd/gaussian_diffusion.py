@@ -359,6 +359,33 @@ class GaussianDiffusion:
             raise ValueError(f"a measurement of {y_n} rows does not split {n} particles into whole images")
         return y_n
 
+    def _segments(self, measurement, n, n_images, infer=True, refuse_multi=None):
+        """The images of a call's particle set: M images x n / M particles, image-major.  The policy is the loop's:
+        infer=True (the resampling loops): M is the measurement's row count where it holds one row per image, else
+        n_images, else 1; refuse_multi: why this call cannot take M > 1 (NotImplementedError).
+        infer=False (search_ddpm): only n_images= makes a multi-image batch, of a measurement with 1 or M rows; -> None
+        without it."""
+        if not infer:
+            if n_images is None:
+                if self._measurement_images(measurement, n) is not None:
+                    raise ValueError(f"a measurement of {measurement.shape[0]} rows for {n} particles: pass n_images= for "
+                                     "a multi-image batch")
+                return None
+            segments, y_n = int(n_images), measurement.shape[0]
+            if segments < 1 or n % segments or y_n not in (1, segments):
+                raise ValueError(f"n_images={segments}: {n} particles and a measurement of {y_n} rows do not form "
+                                 f"{segments} images")
+            return segments
+        images, n_images = self._measurement_images(measurement, n), int(n_images or 1)
+        if images is not None and n_images > 1 and images != n_images:
+            raise ValueError(f"n_images={n_images} with a measurement of {images} rows")
+        segments = images or n_images
+        if segments > 1 and refuse_multi:
+            raise NotImplementedError(refuse_multi)
+        if segments < 1 or n % segments:
+            raise ValueError(f"{n} particles do not split into {segments} images")
+        return segments
+
     def _check_multi_image(self, plan, method, projecting, images, n):
         """a multi-image batch runs the fused ps / ps_anneal / ps_semantic-without-embedder step only"""
         name = type(method).__name__ if method is not None else "this conditioning function"
@@ -625,12 +652,18 @@ class SearchDDPM(DDPM):
     #: noise draws, costs and winner indices are the same); False keeps N copies as the reference does.
     single_state = True
 
+    def _proposal_noise(self, like, n, idx, segments, noise):
+        """the noise source of a step's n proposals -> (noise, rng): the caller's tensor; else the record of the in-launch
+        draw (noise_draw = 'device'); else a torch draw [n, C, H, W] on like's device"""
+        rng = self._step_rng(idx, n, segments) if noise is None else None
+        if noise is None and rng is None:
+            noise = self._randn(like, shape=None if like.shape[0] == n else (n,) + tuple(like.shape[1:]))
+        return noise, rng
+
     def search_step(self, model, img, idx, measurement, handle, noise=None, segments=None):
         with torch.no_grad():
             model_out = self._call_model(model, img, idx)
-        rng = self._step_rng(idx, img.shape[0], segments) if noise is None else None
-        if noise is None and rng is None:
-            noise = self._randn(img)
+        noise, rng = self._proposal_noise(img, img.shape[0], idx, segments, noise)
         # S1 -> scoring launch -> costs + select -> the winner's replication: one library call, nothing leaves the device
         local = self.global_select is None
         x_next, sample, costs, best, _ = handle.search_step(img, model_out, noise, measurement, self.step_coefs[idx],
@@ -645,9 +678,7 @@ class SearchDDPM(DDPM):
         segments=M: one state per image, [M,C,H,W] -> (winners [M,C,H,W], costs [n])."""
         with torch.no_grad():
             model_out = self._call_model(model, state, idx)
-        rng = self._step_rng(idx, n, segments) if noise is None else None
-        if noise is None and rng is None:
-            noise = self._randn(state, shape=(n,) + tuple(state.shape[1:]))
+        noise, rng = self._proposal_noise(state, n, idx, segments, noise)
         local = self.global_select is None
         winner, sample, costs, best, _ = handle.search_step_one(state, model_out, noise, measurement,
                                                                 self.step_coefs[idx], want_winner=local,
@@ -669,19 +700,10 @@ class SearchDDPM(DDPM):
         n = img.shape[0]
         # n_images=M: M images x n / M particles (image-major), measurement [1 or M, ...]: every select is per image
         # (last_best: [M] global particle indices) and the state is one particle per image
-        segments = kwargs.get('n_images', None)
-        if segments is not None:
-            segments = int(segments)
-            y_n = measurement.shape[0]
-            if segments < 1 or n % segments or y_n not in (1, segments):
-                raise ValueError(f"n_images={segments}: {n} particles and a measurement of {y_n} rows do not form "
-                                 f"{segments} images")
-            if segments > 1 and self.global_select is not None:
-                raise NotImplementedError("n_images > 1 with a global (multi-rank) select is not supported: the champion "
-                                          "exchange picks one winner for all particles")
-        elif self._measurement_images(measurement, n) is not None:
-            raise ValueError(f"a measurement of {measurement.shape[0]} rows for {n} particles: pass n_images= for a "
-                             "multi-image batch")
+        segments = self._segments(measurement, n, kwargs.get('n_images', None), infer=False)
+        if (segments or 1) > 1 and self.global_select is not None:
+            raise NotImplementedError("n_images > 1 with a global (multi-rank) select is not supported: the champion "
+                                      "exchange picks one winner for all particles")
         per = n // (segments or 1)
         self._step_rng(0, n, segments)    # validates noise_draw before the first step
         state = None                      # the single state particle(s), once a select has made all particles equal
@@ -710,17 +732,9 @@ class SearchDDPM(DDPM):
             raise NotImplementedError
         n = denoised_candidates.shape[0]
         draw = self._check_resample_draw(kwargs.get('resample_draw', None) or self.resample_draw)
-        images = self._measurement_images(measurement, n)
-        n_images = int(kwargs.get('n_images', None) or 1)
-        if images is not None and n_images > 1 and images != n_images:
-            raise ValueError(f"n_images={n_images} with a measurement of {images} rows")
-        segments = images or n_images
-        if segments > 1 and draw != "device":
-            raise NotImplementedError("resample_update over a multi-image batch is not supported: the multinomial draw "
-                                      "would mix particles of different images (it needs a per-image RNG stream policy; "
-                                      "resample_draw='device' draws per image)")
-        if segments < 1 or n % segments:
-            raise ValueError(f"{n} particles do not split into {segments} images")
+        segments = self._segments(measurement, n, kwargs.get('n_images', None), refuse_multi=None if draw == "device" else (
+            "resample_update over a multi-image batch is not supported: the multinomial draw would mix particles of "
+            "different images (it needs a per-image RNG stream policy; resample_draw='device' draws per image)"))
         if draw == "device":
             if resample and prev_costs is not None:
                 # one uniform per slot whatever the weights turn out to be (a flat segment keeps its particles: the
@@ -776,13 +790,7 @@ class TTC_DDIM(DDIM):
         kernels.require_cuda(img, "x_start")
         draw = self._check_resample_draw(self.resample_draw)
         n = img.shape[0]
-        images = self._measurement_images(measurement, n)
-        n_images = int(kwargs.get('n_images', None) or 1)
-        if images is not None and n_images > 1 and images != n_images:
-            raise ValueError(f"n_images={n_images} with a measurement of {images} rows")
-        segments = images or n_images
-        if segments < 1 or n % segments:
-            raise ValueError(f"{n} particles do not split into {segments} images")
+        segments = self._segments(measurement, n, kwargs.get('n_images', None))
         resample_every_steps, resample_scale = 10, 100
         distance = None
         self.last_resample_ids = None

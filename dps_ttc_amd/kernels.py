@@ -101,13 +101,11 @@ def posterior_fwd(x_t, model_out, noise=None, coefs=None, want_inside=False, wan
         raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of x {tuple(x_t.shape)}")
     x0, sample = (torch.empty_like(x_t) if want_x0 else None), torch.empty_like(x_t)
     inside = torch.empty(x_t.shape, dtype=torch.uint8, device=x_t.device) if want_inside else None
+    tail = (ptr(x0), ptr(sample), ptr(inside), n, chw, byref(coefs), stream_of(x_t))
     if rng is not None:
-        check(lib().dpsx_posterior_fwd_rng_f32(ptr(x_t), ptr(model_out), byref(rng.rec()), ptr(x0), ptr(sample),
-                                               ptr(inside), n, chw, byref(coefs), stream_of(x_t)),
-              "dpsx_posterior_fwd_rng_f32")
-        return (x0, sample, inside) if want_inside else (x0, sample)
-    check(lib().dpsx_posterior_fwd_f32(ptr(x_t), ptr(model_out), ptr(noise), ptr(x0), ptr(sample), ptr(inside),
-                                       n, chw, byref(coefs), stream_of(x_t)), "dpsx_posterior_fwd_f32")
+        check(lib().dpsx_posterior_fwd_rng_f32(ptr(x_t), ptr(model_out), byref(rng.rec()), *tail), "dpsx_posterior_fwd_rng_f32")
+    else:
+        check(lib().dpsx_posterior_fwd_f32(ptr(x_t), ptr(model_out), ptr(noise), *tail), "dpsx_posterior_fwd_f32")
     return (x0, sample, inside) if want_inside else (x0, sample)
 
 
@@ -297,6 +295,28 @@ class OpHandle:
                                           n, c, h, w, ptr(ws), ws.numel(), stream_of(x)), "dpsx_score_argmin_f32")
         return costs, best, val
 
+    def _search(self, x, model_out, noise, rng, y, coefs, n, n_out, segments, one):
+        """The library call of search_step / search_step_one: x [N or states, C, H, W] and model_out as checked by them,
+        n proposals, x_next / winner of n_out rows (0: not wanted) -> (x_next or None, sample, costs, best, costs[best]).
+        The entry point follows from the arguments: _one for one state per image, _seg with segments= (and for every
+        rng= call: the in-launch draw exists in the segmented forms only, one segment being the whole set)."""
+        c, h, w = x.shape[1:]
+        dev = x.device
+        seg = 1 if segments is None else int(segments)
+        sample = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+        x_next = torch.empty((n_out, c, h, w), dtype=torch.float32, device=dev) if n_out else None
+        costs = torch.empty(n, dtype=torch.float32, device=dev)
+        best = torch.empty(seg if segments is not None else (), dtype=torch.int64, device=dev)
+        val = torch.empty(seg, dtype=torch.float32, device=dev)
+        ws = self.workspace(n, c, h, w, dev)
+        segmented = segments is not None or rng is not None
+        name = f"dpsx_search_step{'_one' if one else ''}{'_seg' if segmented else ''}{'_rng' if rng is not None else ''}_f32"
+        check(getattr(lib(), name)(self._h, ptr(x), ptr(model_out), ptr(noise) if rng is None else byref(rng.rec()), ptr(y),
+                                   y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(x_next),
+                                   *((seg,) if segmented else ()), n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
+                                   stream_of(x)), name)
+        return x_next, sample, costs, best, val
+
     def search_step(self, x_t, model_out, noise=None, y=None, coefs=None, replicate=True, segments=None, rng=None):
         """One search_ddpm step (gaussian_diffusion.py:618-633): S1, costs of the proposals, select and -- with
         replicate=True -- the winner copied over all particles.  -> (x_next or None, sample, costs, best, costs[best]);
@@ -313,33 +333,7 @@ class OpHandle:
             raise ValueError("best-of-N over an empty particle set")
         if model_out.shape[0] != n or model_out[0].numel() != 2 * c * h * w:
             raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of x {tuple(x_t.shape)}")
-        sample = torch.empty_like(x_t)
-        x_next = torch.empty_like(x_t) if replicate else None
-        costs = torch.empty(n, dtype=torch.float32, device=x_t.device)
-        ws = self.workspace(n, c, h, w, x_t.device)
-        if rng is not None:
-            seg = 1 if segments is None else int(segments)
-            best = torch.empty(seg if segments is not None else (), dtype=torch.int64, device=x_t.device)
-            val = torch.empty(seg, dtype=torch.float32, device=x_t.device)
-            check(lib().dpsx_search_step_seg_rng_f32(self._h, ptr(x_t), ptr(model_out), byref(rng.rec()), ptr(y),
-                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val),
-                                                     ptr(x_next), seg, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
-                                                     stream_of(x_t)), "dpsx_search_step_seg_rng_f32")
-            return x_next, sample, costs, best, val
-        if segments is not None:
-            best = torch.empty(int(segments), dtype=torch.int64, device=x_t.device)
-            val = torch.empty(int(segments), dtype=torch.float32, device=x_t.device)
-            check(lib().dpsx_search_step_seg_f32(self._h, ptr(x_t), ptr(model_out), ptr(noise), ptr(y), y.shape[0],
-                                                 ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(x_next), int(segments),
-                                                 n, c, h, w, byref(coefs), ptr(ws), ws.numel(), stream_of(x_t)),
-                  "dpsx_search_step_seg_f32")
-            return x_next, sample, costs, best, val
-        best = torch.empty((), dtype=torch.int64, device=x_t.device)
-        val = torch.empty(1, dtype=torch.float32, device=x_t.device)
-        check(lib().dpsx_search_step_f32(self._h, ptr(x_t), ptr(model_out), ptr(noise), ptr(y), y.shape[0], ptr(sample),
-                                         ptr(costs), ptr(best), ptr(val), ptr(x_next), n, c, h, w, byref(coefs), ptr(ws),
-                                         ws.numel(), stream_of(x_t)), "dpsx_search_step_f32")
-        return x_next, sample, costs, best, val
+        return self._search(x_t, model_out, noise, rng, y, coefs, n, n if replicate else 0, segments, one=False)
 
     def search_step_one(self, x_one, model_out_one, noise=None, y=None, coefs=None, want_winner=True, segments=None,
                         rng=None, n=None):
@@ -351,60 +345,23 @@ class OpHandle:
         rng= with n= (instead of noise=): the N proposals' noise is drawn inside S1's launch."""
         _noise_or_rng(noise, rng)
         x_one, model_out_one, y = _nchw(f32c(x_one, "x_t")), f32c(model_out_one, "model_out"), f32c(y, "measurement")
+        states = 1 if segments is None else int(segments)
         if rng is not None:
             if n is None:
                 raise ValueError("search_step_one(rng=) needs n=, the number of proposals")
-            return self._search_step_one_rng(x_one, model_out_one, rng, int(n), y, coefs, want_winner, segments)
-        noise = _nchw(f32c(noise, "noise"))
-        n, c, h, w = noise.shape
-        if n == 0:
-            raise ValueError("best-of-N over an empty particle set")
-        states = 1 if segments is None else int(segments)
-        if x_one.shape != (states, c, h, w) or model_out_one.shape[0] != states or \
-                model_out_one[0].numel() != 2 * c * h * w:
-            raise ValueError(f"{states} state particle(s) expected: x {tuple(x_one.shape)}, "
-                             f"model_out {tuple(model_out_one.shape)}, noise {tuple(noise.shape)}")
-        sample = torch.empty_like(noise)
-        winner = torch.empty_like(x_one) if want_winner else None
-        costs = torch.empty(n, dtype=torch.float32, device=noise.device)
-        if segments is not None:
-            best = torch.empty(states, dtype=torch.int64, device=noise.device)
-            val = torch.empty(states, dtype=torch.float32, device=noise.device)
-            ws = self.workspace(n, c, h, w, noise.device)
-            check(lib().dpsx_search_step_one_seg_f32(self._h, ptr(x_one), ptr(model_out_one), ptr(noise), ptr(y),
-                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(winner),
-                                                     states, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
-                                                     stream_of(noise)), "dpsx_search_step_one_seg_f32")
-            return winner, sample, costs, best, val
-        best = torch.empty((), dtype=torch.int64, device=noise.device)
-        val = torch.empty(1, dtype=torch.float32, device=noise.device)
-        ws = self.workspace(n, c, h, w, noise.device)
-        check(lib().dpsx_search_step_one_f32(self._h, ptr(x_one), ptr(model_out_one), ptr(noise), ptr(y), y.shape[0],
-                                             ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(winner), n, c, h, w,
-                                             byref(coefs), ptr(ws), ws.numel(), stream_of(noise)),
-              "dpsx_search_step_one_f32")
-        return winner, sample, costs, best, val
-
-    def _search_step_one_rng(self, x_one, model_out_one, rng, n, y, coefs, want_winner, segments):
-        states, c, h, w = x_one.shape
+            n, (c, h, w) = int(n), x_one.shape[1:]
+            what, whole = f"{n} proposals", states > 0 and n % states == 0
+        else:
+            noise = _nchw(f32c(noise, "noise"))
+            n, c, h, w = noise.shape
+            what, whole = f"noise {tuple(noise.shape)}", True      # the library refuses n % states != 0
         if n < 1:
             raise ValueError("best-of-N over an empty particle set")
-        if states != (1 if segments is None else int(segments)) or model_out_one.shape[0] != states or \
-                model_out_one[0].numel() != 2 * c * h * w or n % states:
-            raise ValueError(f"{1 if segments is None else int(segments)} state particle(s) expected: x "
-                             f"{tuple(x_one.shape)}, model_out {tuple(model_out_one.shape)}, {n} proposals")
-        dev = x_one.device
-        sample = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
-        winner = torch.empty_like(x_one) if want_winner else None
-        costs = torch.empty(n, dtype=torch.float32, device=dev)
-        best = torch.empty(states if segments is not None else (), dtype=torch.int64, device=dev)
-        val = torch.empty(states, dtype=torch.float32, device=dev)
-        ws = self.workspace(n, c, h, w, dev)
-        check(lib().dpsx_search_step_one_seg_rng_f32(self._h, ptr(x_one), ptr(model_out_one), byref(rng.rec()), ptr(y),
-                                                     y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val),
-                                                     ptr(winner), states, n, c, h, w, byref(coefs), ptr(ws), ws.numel(),
-                                                     stream_of(x_one)), "dpsx_search_step_one_seg_rng_f32")
-        return winner, sample, costs, best, val
+        if x_one.shape != (states, c, h, w) or model_out_one.shape[0] != states or \
+                model_out_one[0].numel() != 2 * c * h * w or not whole:
+            raise ValueError(f"{states} state particle(s) expected: x {tuple(x_one.shape)}, "
+                             f"model_out {tuple(model_out_one.shape)}, {what}")
+        return self._search(x_one, model_out_one, noise, rng, y, coefs, n, states if want_winner else 0, segments, one=True)
 
     def resample_cost(self, x, y, prev_costs=None, potential_type='min'):
         """SearchDDPM.resample_update's cost update (gaussian_diffusion.py:556-585) in one launch:

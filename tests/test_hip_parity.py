@@ -1115,7 +1115,11 @@ def test_taps_regular_multi_tile(K, oracle, kind, seed, hw):
 @pytest.mark.parametrize("t", [700, 0])
 def test_search_step_fused_equals_separate(K, oracle, name, hw, n, t):
     """dpsx_search_step_f32 (S1, scoring launch, one launch for costs + select + replication) ==
-    dpsx_posterior_fwd_f32 + dpsx_score_argmin_f32 + dpsx_replicate_f32, bit for bit: sample, costs, winner, x_next"""
+    dpsx_posterior_fwd_f32 + dpsx_score_argmin_f32 + dpsx_replicate_f32, bit for bit: sample, costs, winner, x_next.
+    The segmented forms (segments = 1, 2; below 256 x 256, n made even for two segments by one more particle) against the
+    same separate launches scored with each particle's own measurement row, the select being torch.argmin on the host
+    per segment: best[m] = m k + argmin(costs[m k : (m + 1) k]), val[m] = costs[best[m]], x_next[m k : (m + 1) k] =
+    sample[best[m]]"""
     ih, iw, hw = _pair(hw)
     rng = np.random.RandomState(hw + n + t)
     mask = (np.random.RandomState(3).rand(1, 1, ih, iw) < 0.5).astype(np.float32)
@@ -1137,6 +1141,28 @@ def test_search_step_fused_equals_separate(K, oracle, name, hw, n, t):
                 assert torch.equal(x_next, ref_sample[int(ref_best)].unsqueeze(0).expand_as(x_next))
             else:
                 assert x_next is None
+    if hw == 256:
+        return
+    y_b = op.forward(dev(rng.uniform(-1, 1, (1, 3, ih, iw)).astype(np.float32)), **fkw).detach().contiguous()
+    for segments in (1, 2):
+        pad = n % segments
+        xs, mos, zs = (torch.cat([a, a[:pad]]) for a in (x, mo, z))
+        k = (n + pad) // segments
+        for yy in ((y,) if segments == 1 else (y, torch.cat([y, y_b]))):       # one row for all, or one per segment
+            _, ref_sample = K.posterior_fwd(xs, mos, zs, ck, want_x0=False)
+            ref_costs = handle.score(ref_sample, yy.repeat_interleave((n + pad) // yy.shape[0], dim=0))
+            for replicate in (True, False):
+                x_next, sample, costs, best, val = handle.search_step(xs, mos, zs, yy, ck, replicate=replicate,
+                                                                      segments=segments)
+                assert torch.equal(sample, ref_sample) and torch.equal(costs, ref_costs)
+                assert best.shape == (segments,) and val.shape == (segments,)
+                assert (x_next is None) == (not replicate)
+                for m in range(segments):
+                    sl = slice(m * k, (m + 1) * k)
+                    assert int(best[m]) == m * k + int(torch.argmin(ref_costs[sl])), (segments, m)
+                    assert torch.equal(val[m], ref_costs[int(best[m])])
+                    if replicate:
+                        assert torch.equal(x_next[sl], ref_sample[int(best[m])].unsqueeze(0).expand(k, -1, -1, -1))
 
 
 @pytest.mark.parametrize("name,hw,n", [("gauss", 256, 9), ("gauss", 64, 5), ("sr4", 256, 5), ("inpaint", 64, 4), ("motion", 128, 3),
@@ -1144,7 +1170,9 @@ def test_search_step_fused_equals_separate(K, oracle, name, hw, n, t):
 @pytest.mark.parametrize("t", [700, 0])
 def test_search_step_one_state_equals_replicated(K, oracle, name, hw, n, t):
     """dpsx_search_step_one_f32 (one state particle feeds all N proposals, the winner is copied out once) ==
-    dpsx_search_step_f32 on N copies of that state, bit for bit: proposals, costs, winner index, winner"""
+    dpsx_search_step_f32 on N copies of that state, bit for bit: proposals, costs, winner index, winner.
+    The segmented forms (segments = 1, 2; below 256 x 256) with one state per segment against the segmented replicated
+    step on each state's copies, and the winners against the proposals themselves"""
     rng = np.random.RandomState(hw + n + t + 1)
     mask = (np.random.RandomState(3).rand(1, 1, hw, hw) < 0.5).astype(np.float32)
     op, fkw = make_product_op(name, hw=hw, kernel=synthetic_motion_kernel(61, 5), mask=mask)
@@ -1161,6 +1189,22 @@ def test_search_step_one_state_equals_replicated(K, oracle, name, hw, n, t):
     assert torch.equal(w_one, x_rep[:1]) and torch.equal(w_one, s_rep[int(b_rep)].unsqueeze(0))
     w_none = handle.search_step_one(x1, mo1, z, y, ck, want_winner=False)[0]
     assert w_none is None
+    if hw == 256:
+        return
+    x2 = torch.cat([x1, dev(rng.randn(1, 3, hw, hw).astype(np.float32))])
+    mo2 = torch.cat([mo1, dev(rng.randn(1, 6, hw, hw).astype(np.float32) * 0.5)])
+    y2 = torch.cat([y, op.forward(dev(rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32)), **fkw).detach()]).contiguous()
+    for segments in (1, 2):
+        zs = torch.cat([z, z[:n % segments]])
+        k = zs.shape[0] // segments
+        xs, mos, yy = x2[:segments].contiguous(), mo2[:segments].contiguous(), y2[:segments].contiguous()
+        x_rep, s_rep, c_rep, b_rep, v_rep = handle.search_step(xs.repeat_interleave(k, dim=0), mos.repeat_interleave(k, dim=0),
+                                                                zs, yy, ck, segments=segments)
+        w_one, s_one, c_one, b_one, v_one = handle.search_step_one(xs, mos, zs, yy, ck, segments=segments)
+        assert torch.equal(s_one, s_rep) and torch.equal(c_one, c_rep)
+        assert b_one.shape == (segments,) and torch.equal(b_one, b_rep) and torch.equal(v_one, v_rep)
+        assert torch.equal(w_one, x_rep[::k]) and torch.equal(w_one, s_rep[b_rep])
+        assert handle.search_step_one(xs, mos, zs, yy, ck, want_winner=False, segments=segments)[0] is None
 
 
 @pytest.mark.parametrize("name", ["gauss", "motion", "sr4", "phase"])
