@@ -5,6 +5,7 @@
     cm.conditioning(x_prev=, x_t=, x_0_hat=, measurement=, **kw)
         'ps' / 'ps_anneal' / 'mcg' / 'ps+'  -> (x_t_updated, norm, ...)  (:85-106, 206-232)
         'ps_semantic'                       -> (norm_grad, measurement_err, semantic_err)   (:190-195)
+        'cg' (not in the reference)         -> (x_{t-1}, dist): needs coefs= from the loop, no autograd graph
 
 Called on tensors that came out of this package's p_sample (PosteriorStepFn) and
 operator.forward (OperatorFn), `torch.autograd.grad` walks:  UNet  <-  [HIP S1 VJP]
@@ -18,23 +19,28 @@ from abc import ABC, abstractmethod
 import torch
 
 from .kernels import ResidualNormFn
+from .measurements import LinearOperator
 
-__CONDITIONING_METHOD__ = {}
+__CONDITIONING_METHOD__ = {}      # the reference's methods, under the reference's names
+__EXTENSION_METHOD__ = {}         # methods the reference does not have ('cg'): same lookup, their own table
 
 
-def register_conditioning_method(name: str):
+def register_conditioning_method(name: str, extension: bool = False):
+    """extension=True: a method that is not in the reference; it is found by get_conditioning_method like the others
+    and kept out of the table that mirrors the reference's registry"""
     def wrapper(cls):
-        if __CONDITIONING_METHOD__.get(name, None):
+        if __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None):
             raise NameError(f"Name {name} is already registered!")
-        __CONDITIONING_METHOD__[name] = cls
+        (__EXTENSION_METHOD__ if extension else __CONDITIONING_METHOD__)[name] = cls
         return cls
     return wrapper
 
 
 def get_conditioning_method(name: str, operator, noiser, **kwargs):
-    if __CONDITIONING_METHOD__.get(name, None) is None:
+    cls = __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None)
+    if cls is None:
         raise NameError(f"Name {name} is not defined!")
-    return __CONDITIONING_METHOD__[name](operator=operator, noiser=noiser, **kwargs)
+    return cls(operator=operator, noiser=noiser, **kwargs)
 
 
 class ConditioningMethod(ABC):
@@ -248,3 +254,46 @@ class PosteriorSamplingPlus(ConditioningMethod):
         norm_grad = torch.autograd.grad(outputs=norm, inputs=x_prev)[0]
         x_t = x_t - norm_grad * self.scale
         return x_t, norm
+
+
+@register_conditioning_method(name='cg', extension=True)
+class ConjugateGradientConsistency(ConditioningMethod):
+    """Jacobian-free conditioning (not in the reference; the proximal step of DiffPIR / DDS): per particle, `iters`
+    conjugate-gradient iterations on (A^T A + rho I)(x0_hat + d) = A^T y + rho x0_hat from d = 0, then the sampler's own
+    step with x0_hat + d in place of x0_hat: x_{t-1} = sample + kappa d.  It needs A and its exact adjoint only: the
+    model runs under no_grad.  rho = rho_scale * sigma_n^2 / b^2 with b = sqrt(1 / abar_t - 1) and
+    sigma_n = max(noiser.sigma, 0.05) as in ps_anneal.  Linear operators only."""
+    returns_gradient = False
+
+    def __init__(self, operator, noiser, **kwargs):
+        super().__init__(operator, noiser)
+        if not isinstance(operator, LinearOperator):
+            raise NotImplementedError(
+                f"cg solves a linear system in A^T A: {getattr(operator, 'name', type(operator).__name__)} is not a linear "
+                "operator")
+        self.rho_scale = float(kwargs.get('rho_scale', 1.0))
+        self.iters = int(kwargs.get('iters', 5))
+        if not 0 <= self.iters <= 64:
+            raise ValueError(f"cg: iters must be in [0, 64] (got {self.iters})")
+        if not (self.rho_scale >= 0 and math.isfinite(self.rho_scale)):
+            raise ValueError(f"cg: rho_scale must be finite and not negative (got {self.rho_scale})")
+        self.noise_sigma = max(getattr(noiser, 'sigma', 0.0), 0.05)
+        self.operator_name = operator.name
+
+    def rho(self, b):
+        """the regulariser of the step whose record carries b (float64 on the host; the launch takes it as one fp32)"""
+        return self.rho_scale * float(self.noise_sigma) ** 2 / float(b) ** 2
+
+    def conditioning(self, x_t, x_0_hat, measurement, *, coefs=None, **kwargs):
+        """x_t: the sampler's unconditioned `sample`; coefs: the step's dpsx_coefs record.  -> (x_{t-1}, dist[N]) in the
+        operator handle's persistent buffers (valid until the next call)."""
+        if coefs is None:
+            raise ValueError("cg.conditioning needs coefs= (the step's dpsx_coefs record): the sampling loop supplies it")
+        op, mask = self.operator, kwargs.get('mask', None)
+        if op.name == 'inpainting':
+            if mask is None:
+                raise ValueError("Require mask")
+            handle = op.hip_handle_for(mask)
+        else:
+            handle = op.hip_handle(x_0_hat)
+        return handle.cg_step(x_0_hat, x_t, measurement, self.rho(coefs.b), self.iters, coefs)

@@ -732,6 +732,98 @@ int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, flo
     return plain_update(sample, g_a, g_b, out, count, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ CG data-consistency step
+// workspace: [the operator's own workspace | residual-norm partials | rs (x2), pp, tt partials | per-particle scalars |
+//             t, r_y (measurement-sized) | r, p, s, d (image-sized)]
+struct CgWs {
+    void *op_ws;
+    int64_t op_bytes;
+    float *norm_part, *rs[2], *pp, *tt, *scal, *t, *ry, *r, *p, *s, *d;
+};
+
+// carves `base` (nullable: sizes only) and returns the bytes needed, or a negative DPSX_E* code
+static int64_t cg_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, char *base, CgWs *o)
+{
+    const int64_t op_bytes = dpsx_op_workspace_bytes(op, n, c, h, w), m = meas_elems(op, c, h, w);
+    if (op_bytes < 0 || m < 0) return DPSX_EINVAL;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += align256(bytes);
+        return p;
+    };
+    const int64_t part = n * 256 * 4, img = n * c * h * w * 4;
+    CgWs k{};
+    k.op_ws = take(op_bytes);
+    k.op_bytes = op_bytes;
+    float **f[] = {&k.norm_part, &k.rs[0], &k.rs[1], &k.pp, &k.tt};
+    for (float **q : f) *q = reinterpret_cast<float *>(take(part));
+    k.scal = reinterpret_cast<float *>(take(n * 4 * 4));
+    k.t = reinterpret_cast<float *>(take(n * m * 4));
+    k.ry = reinterpret_cast<float *>(take(n * m * 4));
+    float **g[] = {&k.r, &k.p, &k.s, &k.d};
+    for (float **q : g) *q = reinterpret_cast<float *>(take(img));
+    if (o) *o = k;
+    return off;
+}
+
+int64_t dpsx_cg_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
+{
+    int rc = check_geom(op, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    if (op->kind == OP_PHASE) return DPSX_EUNSUPPORTED;
+    return cg_carve(op, n, c, h, w, nullptr, nullptr);
+}
+
+int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, const float *y, int64_t y_n, float rho,
+                     int iters, const dpsx_coefs *coefs_host, float *x_next, float *dist, float *d_out, int64_t n,
+                     int64_t c, int64_t h, int64_t w, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    int rc = check_geom(op, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    if (op->kind == OP_PHASE) return DPSX_EUNSUPPORTED;          // no adjoint independent of the point: not a linear solve
+    if (!x0_hat || !sample || !y || !coefs_host || !x_next || !dist) return DPSX_EINVAL;
+    if (iters < 0 || iters > kCgMaxIters || !(rho >= 0.0f) || !std::isfinite(rho) || !rows_ok(y_n, n)) return DPSX_EINVAL;
+    if (n > 65535) return DPSX_EUNSUPPORTED;                      // particles are the grid's y dimension
+    // the slope of the sampler's `sample` in x0_hat (fp32, in this order): DDPM c1; DDIM c1 - c2 / b
+    float kappa = coefs_host->c1;
+    if (coefs_host->add_noise & 2) {
+        if (coefs_host->b == 0.0f) return DPSX_EINVAL;
+        const float q = coefs_host->c2 / coefs_host->b;
+        kappa = coefs_host->c1 - q;
+    }
+    if (n == 0) return DPSX_OK;
+    CgWs k;
+    const int64_t need = cg_carve(op, n, c, h, w, static_cast<char *>(workspace), &k);
+    if (need < 0) return (int)need;
+    if (!workspace || workspace_bytes < need || !aligned16(workspace)) return DPSX_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t e = c * h * w, m = meas_elems(op, c, h, w);
+    // r_y = y - A x0_hat, dist = ||r_y||_2 (the residual-norm path), r = A^T r_y
+    if ((rc = dpsx_op_forward_f32(op, x0_hat, k.t, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
+    if ((rc = dpsx_residual_norm_f32(y, y_n, k.t, k.ry, dist, n, m, k.norm_part, n * 256 * 4, stream)) != DPSX_OK) return rc;
+    if ((rc = dpsx_op_adjoint_f32(op, k.ry, nullptr, k.r, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
+    if (iters == 0) {
+        if (x_next != sample) DPSX_HIP_TRY(hipMemcpyAsync(x_next, sample, (size_t)(n * e) * 4, hipMemcpyDeviceToDevice, s));
+        if (d_out) DPSX_HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)(n * e) * 4, s));
+        return DPSX_OK;
+    }
+    if ((rc = cg_init(k.r, k.p, k.rs[0], n, e, s)) != DPSX_OK) return rc;
+    float *d = d_out ? d_out : k.d;
+    for (int it = 0; it < iters; ++it) {
+        const float *rs_old = k.rs[it & 1], *pp = it == 0 ? k.rs[0] : k.pp;       // p = r before the first iteration
+        float *rs_new = k.rs[(it + 1) & 1];
+        if ((rc = dpsx_op_forward_f32(op, k.p, k.t, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
+        if ((rc = dpsx_op_adjoint_f32(op, k.t, nullptr, k.s, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
+        if ((rc = cg_sumsq(k.t, k.tt, n, m, s)) != DPSX_OK) return rc;
+        if (it == iters - 1)
+            return cg_final(sample, d, k.p, x_next, d_out, rs_old, k.tt, pp, k.scal, rho, kappa, it == 0, n, e, m, s);
+        if ((rc = cg_update(d, k.p, k.r, k.s, rs_old, k.tt, pp, rs_new, k.scal, rho, it == 0, n, e, m, s)) != DPSX_OK) return rc;
+        if ((rc = cg_pupdate(k.r, k.p, rs_old, rs_new, k.pp, k.scal, n, e, s)) != DPSX_OK) return rc;
+    }
+    return DPSX_OK;
+}
+
 // ------------------------------------------------------------------ best-of-N
 // Residual partials per block (one launch; two for the operators that materialise A x first), then one small launch
 // that finishes costs[p] and, when asked, the combine with the previous costs and the argmin over all particles.

@@ -604,6 +604,24 @@ int pack_champion(const float *particles, const float *costs, const int64_t *bes
 int select_champion(const float *table, int world, int64_t chw, float *dst, int64_t n_out, int64_t *win_rank,
                     int64_t *win_local, hipStream_t s);
 
+// cg.hip: the vector launches of dpsx_cg_step_f32 (the recurrence is stated in include/dpsx.h).  Particles of e image
+// elements and m measurement elements; every sum of squares is left as cg_slots(size) fp32 partials per particle
+// ([n, cg_slots] arrays) and finished in double by the prologue of the launch that consumes it.
+constexpr int kCgMaxIters = 64;
+int cg_slots(int64_t size);                     // partial slots per particle: a function of the size only (<= 256)
+int cg_init(const float *r, float *p, float *rs_part, int64_t n, int64_t e, hipStream_t s);          // p = r, ||r||^2
+int cg_sumsq(const float *t, float *part, int64_t n, int64_t m, hipStream_t s);                      // ||t||^2
+// alpha = rs / (tt + rho pp); d += alpha p (first: d = alpha p); r -= alpha (sv + rho p); ||r||^2 -> rs_new
+int cg_update(float *d, const float *p, float *r, const float *sv, const float *rs_old, const float *tt, const float *pp,
+              float *rs_new, float *scal, float rho, bool first, int64_t n, int64_t e, int64_t m, hipStream_t s);
+// beta = rs_new / rs_old; p = r + beta p; ||p||^2 -> pp
+int cg_pupdate(const float *r, float *p, const float *rs_old, const float *rs_new, float *pp, float *scal, int64_t n,
+               int64_t e, hipStream_t s);
+// alpha as above; x_next = sample + kappa (d + alpha p); d_out (nullable) = d + alpha p.  x_next may be sample, d_out may be d
+int cg_final(const float *sample, const float *d, const float *p, float *x_next, float *d_out, const float *rs,
+             const float *tt, const float *pp, float *scal, float rho, float kappa, bool first, int64_t n, int64_t e,
+             int64_t m, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op);
 void phase_destroy(dpsx_op *op);

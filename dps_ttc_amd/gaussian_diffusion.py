@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import kernels
-from .condition_methods import ConditioningMethod
+from .condition_methods import ConditioningMethod, ConjugateGradientConsistency
 from .diffstategrad_utils import apply_diffstategrad, compute_svd_and_adaptive_rank
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
@@ -168,6 +168,7 @@ class GaussianDiffusion:
         #: call, three HIP launches, model VJP) on its own HIP stream with its own operator handle (kernels.ParticleGroups):
         #: the tile kernels' load / compute / store phases add up inside one chain, side by side they fill each other's gaps.
         #: Per-particle results do not depend on it (the noise is still drawn for the whole batch, in the same order).
+        #: Groups exist only under a fused plan: the `cg` method has none and runs one chain whatever this says.
         self.particle_groups = 1
         self._pgroups = None
 
@@ -387,7 +388,8 @@ class GaussianDiffusion:
         return segments
 
     def _check_multi_image(self, plan, method, projecting, images, n):
-        """a multi-image batch runs the fused ps / ps_anneal / ps_semantic-without-embedder step only"""
+        """a multi-image batch runs the fused ps / ps_anneal / ps_semantic-without-embedder step only (and `cg`, whose
+        loops do not come here: every launch of its step takes one measurement row and one mask per image)"""
         name = type(method).__name__ if method is not None else "this conditioning function"
         if plan is None or projecting:
             raise NotImplementedError(
@@ -437,12 +439,40 @@ class GaussianDiffusion:
         self._step_semantic = sems if sems else None
         return pg.x_next(), pg.full.norm
 
+    # -- the Jacobian-free step ('cg') -----------------------------------------
+    def _cg_plan(self, measurement_cond_fn):
+        """-> (method, bound keyword arguments) when measurement_cond_fn is the `cg` method's conditioning, else None"""
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if not isinstance(method, ConjugateGradientConsistency):
+            return None
+        if not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
+            raise NotImplementedError("cg needs the epsilon / learned_range / clip_denoised posterior (the HIP S1) under a "
+                                      "DDPM or DDIM sampler")
+        return method, kw
+
+    def cg_step(self, model, x_prev, idx, measurement, method, cond_kw, noise=None, rng=None):
+        """One `cg` step at loop index idx: the model forward without a graph, S1, then method.conditioning (the CG solve
+        and the sampler's step with x0_hat + d).  Returns (x_next, dist[N]) in the operator handle's persistent buffers
+        (valid until the next step; the loops clone what they hand out)."""
+        with torch.no_grad():
+            x = kernels.f32c(x_prev.detach(), "x_t")
+            mo = kernels.f32c(self._call_model(model, x, idx), "model output")
+            if mo.shape[1] != 2 * x.shape[1]:
+                raise ValueError("the cg step needs a learned-sigma model ([N, 2C, H, W] output)")
+            coefs = self.sample_coefs(idx)
+            if noise is None and rng is None:
+                noise = self._randn(x)
+            x0_hat, sample = kernels.posterior_fwd(x, mo, noise, coefs, rng=rng)
+            return method.conditioning(x_t=sample, x_0_hat=x0_hat, measurement=kernels.f32c(measurement, "measurement"),
+                                       coefs=coefs, **cond_kw)
+
     # -- the base loop (reference :175-303) -------------------------------------
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
         kernels.require_cuda(img, "x_start")
         ttc_driver_call = 'operator' in kwargs      # sample_condition_batched_ttc.py:91-100
         plan = self._fusion_plan(measurement_cond_fn, img)
+        cg = self._cg_plan(measurement_cond_fn)
         method, _ = self._unwrap_cond_fn(measurement_cond_fn)
         returns_gradient = True if method is None else method.returns_gradient
         distance, semantic = None, torch.zeros((), device=img.device)
@@ -455,7 +485,7 @@ class GaussianDiffusion:
         period, project = kwargs.get('period', 20), kwargs.get('project', False)
         # particle groups on streams (sampler.particle_groups > 1): only where every step is a fused step
         images = self._measurement_images(measurement, img.shape[0])
-        if images is not None:
+        if images is not None and cg is None:
             self._check_multi_image(plan, method, project and returns_gradient, images, img.shape[0])
         pg = None
         if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
@@ -464,7 +494,12 @@ class GaussianDiffusion:
         for idx in steps:
             projecting = project and returns_gradient and period != 0 and idx % period == 0
             rng = self._step_rng(idx, img.shape[0], images)
-            if plan is not None and not projecting:
+            if cg is not None:
+                noise = self._randn(img) if rng is None else None
+                if self.rng_parity:
+                    self._randn(measurement, self.parity_measurement_stride)      # the reference's q_sample draw (:224)
+                img, distance = self.cg_step(model, img, idx, measurement, cg[0], cg[1], noise=noise, rng=rng)
+            elif plan is not None and not projecting:
                 noise = self._randn(img) if rng is None else None
                 if self.rng_parity:
                     # the reference's q_sample draw (:224), result unused by ps*
@@ -797,6 +832,7 @@ class TTC_DDIM(DDIM):
         # 'ps'-type methods run the three fused launches with the DDIM variant of S1; the rest (e.g. 'mcg', the
         # method whose two return values fit the reference loop's unpacking at :672) go through the per-op path
         plan = self._fusion_plan(measurement_cond_fn, img)
+        cg = self._cg_plan(measurement_cond_fn)
         if segments > 1:
             if draw != "device":
                 raise NotImplementedError("ttc_ddim over a multi-image batch is not supported: its resampling would mix "
@@ -806,14 +842,20 @@ class TTC_DDIM(DDIM):
                 raise NotImplementedError("ttc_ddim over a multi-image batch with global (multi-rank) resampling is not "
                                           "supported: the exchange draws over all ranks' particles as one set")
             try:
-                self._check_multi_image(plan, self._unwrap_cond_fn(measurement_cond_fn)[0], False, segments, n)
+                if cg is None:
+                    self._check_multi_image(plan, self._unwrap_cond_fn(measurement_cond_fn)[0], False, segments, n)
             except NotImplementedError as e:
                 raise NotImplementedError(f"ttc_ddim: {e}") from None
         self._resample_segments = segments      # the images of this trajectory's particle set (_resample draws per image)
         self._step_rng(0, n, segments)    # validates noise_draw before the first step
         for idx in range(self.num_timesteps - 1, -1, -1):
             rng = self._step_rng(idx, n, segments)
-            if plan is not None:
+            if cg is not None:
+                noise = self._randn(img) if rng is None else None
+                if self.rng_parity:
+                    self._randn(measurement, self.parity_measurement_stride)      # q_sample's draw (:668)
+                img, distance = self.cg_step(model, img, idx, measurement, cg[0], cg[1], noise=noise, rng=rng)
+            elif plan is not None:
                 noise = self._randn(img) if rng is None else None
                 if self.rng_parity:
                     self._randn(measurement, self.parity_measurement_stride)      # q_sample's draw (:668)

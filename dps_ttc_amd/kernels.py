@@ -147,6 +147,7 @@ class OpHandle:
         self.device = device
         self._keep = keep          # tensors the op borrows (mask)
         self._ws = None
+        self._cg = None            # CgBuffers of the last cg_step shape
         self.kind = lib().dpsx_op_kind(self._h)
 
     @classmethod
@@ -362,6 +363,28 @@ class OpHandle:
             raise ValueError(f"{states} state particle(s) expected: x {tuple(x_one.shape)}, "
                              f"model_out {tuple(model_out_one.shape)}, {what}")
         return self._search(x_one, model_out_one, noise, rng, y, coefs, n, states if want_winner else 0, segments, one=True)
+
+    def cg_step(self, x0_hat, sample, y, rho, iters, coefs, want_d=False):
+        """The CG data-consistency step (include/dpsx.h: dpsx_cg_step_f32): `iters` conjugate-gradient iterations per
+        particle on (A^T A + rho I)(x0_hat + d) = A^T y + rho x0_hat from d = 0, then x_next = sample + kappa d with the
+        slope kappa of the sampler's step in x0_hat (cg_kappa).  -> (x_next [N, C, H, W], dist [N] = ||y - A x0_hat||_2
+        [, d]).  One chain of launches on the current stream, no host read.  The results live in this handle's persistent
+        CgBuffers (x_next alternates between two buffers; dist and d are overwritten by the next call): callers clone
+        what they keep."""
+        x0_hat, sample, y = _nchw(f32c(x0_hat, "x0_hat")), _nchw(f32c(sample, "sample")), f32c(y, "measurement")
+        if sample.shape != x0_hat.shape:
+            raise ValueError(f"sample {tuple(sample.shape)} and x0_hat {tuple(x0_hat.shape)} differ in shape")
+        n, c, h, w = x0_hat.shape
+        buf = self._cg
+        if buf is None or buf.shape != (n, c, h, w) or buf.dist.device != x0_hat.device:
+            buf = self._cg = CgBuffers(self, n, c, h, w, x0_hat.device)
+        out = buf.x_next[buf.flip]
+        buf.flip ^= 1
+        d = buf.d_buffer() if want_d else None
+        check(lib().dpsx_cg_step_f32(self._h, ptr(x0_hat), ptr(sample), ptr(y), y.shape[0], float(rho), int(iters),
+                                     byref(coefs), ptr(out), ptr(buf.dist), ptr(d), n, c, h, w, ptr(buf.ws),
+                                     buf.ws.numel(), stream_of(x0_hat)), "dpsx_cg_step_f32")
+        return (out, buf.dist, d) if want_d else (out, buf.dist)
 
     def resample_cost(self, x, y, prev_costs=None, potential_type='min'):
         """SearchDDPM.resample_update's cost update (gaussian_diffusion.py:556-585) in one launch:
@@ -633,6 +656,36 @@ class StepBuffers:
         if self._noise is None:
             self._noise = torch.empty(self.shape, dtype=torch.float32, device=self.sample.device)
         return self._noise
+
+
+class CgBuffers:
+    """Persistent device buffers of OpHandle.cg_step for one (N, C, H, W): the two x_next buffers it alternates between,
+    dist, the solve's workspace (dpsx_cg_workspace_bytes) and, on first request, d.  One allocation per (handle, shape),
+    reused across steps and trajectories."""
+
+    def __init__(self, handle, n, c, h, w, device):
+        self.shape = (n, c, h, w)
+        f = dict(dtype=torch.float32, device=device)
+        need = lib().dpsx_cg_workspace_bytes(handle._h, n, c, h, w)
+        if need < 0:
+            check(int(need), "dpsx_cg_workspace_bytes")
+        self.ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+        self.x_next = [torch.empty((n, c, h, w), **f), torch.empty((n, c, h, w), **f)]
+        self.dist = torch.empty(n, **f)
+        self.flip = 0
+        self._d = None
+
+    def d_buffer(self):
+        if self._d is None:
+            self._d = torch.empty(self.shape, dtype=torch.float32, device=self.dist.device)
+        return self._d
+
+
+def cg_kappa(coefs):
+    """the slope of the sampler's `sample` in x0_hat, as dpsx_cg_step_f32 evaluates it (fp32, in this order): c1 for a
+    DDPM record, c1 - c2 / b for a DDIM record (eps is re-derived from x0_hat; the variance does not depend on it)"""
+    c1, c2, b = np.float32(coefs.c1), np.float32(coefs.c2), np.float32(coefs.b)
+    return float(c1 - c2 / b) if coefs.add_noise & 2 else float(c1)
 
 
 def _stream_arg(stream, t):

@@ -201,6 +201,36 @@ int dpsx_step_update_f32(const float *sample, const float *g_model_out, const fl
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out,
                     int64_t count, void *stream);
 
+/* ---- Jacobian-free conditioning: a fixed number of conjugate-gradient iterations per particle on the data-consistency
+ * system (A^T A + rho I)(x0_hat + d) = A^T y + rho x0_hat, from d = 0, followed by the sampler's own step with x0_hat
+ * replaced by x0_hat + d.  Linear operators only (kinds 0-4); needs A and A^T, no derivative of the model.
+ *   r_y = y - A x0_hat ;  dist[p] = ||r_y||_2            (the quantity dpsx_residual_norm_f32 reports, same bits)
+ *   r = A^T r_y ;  p = r ;  rs = ||r||^2
+ *   repeat iters times:
+ *       t = A p ;  s = A^T t
+ *       pq = ||t||^2 + rho ||p||^2                       (= p^T (A^T A + rho I) p, never negative)
+ *       alpha = pq > 0 ? rs / pq : 0
+ *       d += alpha p ;  r -= alpha (s + rho p)
+ *       rs' = ||r||^2 ;  beta = rs > 0 ? rs' / rs : 0 ;  rs = rs'
+ *       p = r + beta p
+ *   x_next = sample + kappa d                            (x0_hat + d is not clamped)
+ * kappa is the slope of the sampler's `sample` in x0_hat, evaluated in fp32 on the host: c1 for a DDPM record,
+ * c1 - c2 / b for a DDIM record (bit 1 of add_noise: eps is re-derived from x0_hat, the variance does not depend on it).
+ * Every ||.||^2 is one particle's sum: fp32 per-block partials in a fixed order, whose count depends on the particle size
+ * only, added in double by the launch that consumes them; alpha and beta are formed in double and rounded to fp32 once.
+ * A non-finite sum gives that particle the alpha / beta IEEE arithmetic yields and touches no other particle.  The last
+ * iteration updates neither r nor p.  iters = 0 copies sample to x_next (and zeroes d_out) and still reports dist.
+ * One linear chain of launches on `stream`: no allocation, no host read, no branch on data (graph-capturable).
+ * sample, x_next: [n, c, h, w], x_next may be sample.  dist: [n].  d_out (nullable): [n, c, h, w] receives d.
+ * DPSX_EUNSUPPORTED: phase retrieval, n > 65535.  DPSX_EINVAL: iters < 0 or > 64, rho negative or not finite, y_n not
+ * dividing n, a DDIM record with b = 0, a null pointer.  All of them return before anything is launched. */
+int64_t dpsx_cg_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w);
+int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, const float *y, int64_t y_n,
+                     float rho, int iters, const dpsx_coefs *coefs_host,
+                     float *x_next, float *dist /* [n] */, float *d_out /* [n,c,h,w], may be NULL */,
+                     int64_t n, int64_t c, int64_t h, int64_t w,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- best-of-N scoring / select (gaussian_diffusion.py:626-633, 687-698;
  *      best_of_n_simple.py:32-40) */
 /* costs[p] = ||y - A(x_p)||_2 without materialising the residual */

@@ -230,6 +230,8 @@ def main(argv=None):
     sigma = measure_config['noise'].get('sigma', 0)
     if cond_config['method'] == 'ps_anneal':
         dir_name = f"{op_name}_noise_sigma_{sigma}_dps_anneal_amp_{args.anneal_amp}"
+    elif cond_config['method'] == 'cg':
+        dir_name = (f"{op_name}_noise_sigma_{sigma}_cg_rho_scale_{cond_method.rho_scale}_iters_{cond_method.iters}")
     else:
         dir_name = f"{op_name}_noise_sigma_{sigma}_dps_scale_{cond_config['params']['scale']}"
     out_path = os.path.join(args.save_dir, dir_name)

@@ -3,6 +3,8 @@
 (SURVEY.md 8d): how much of a real step is the UNet (PyTorch-ROCm) and how much the HIP tail.
 
     python tools/e2e_unet.py [--particles 16] [--steps 5] [--operator gaussian_blur]
+The last line is the same loop with the `cg` method (model forward under no_grad, S1, the CG solve): the whole-step time
+of `ps` (forward + VJP) against `cg` (forward only).
 """
 import argparse
 import os
@@ -67,6 +69,17 @@ def main():
     print(f"N={n} {args.operator}: full DPS step {dt * 1e3:.1f} ms ({n / dt:.1f} particle-steps/s); "
           f"UNet fwd+VJP alone {du * 1e3:.1f} ms -> HIP tail + glue {max(dt - du, 0) * 1e3:.2f} ms "
           f"({100 * max(dt - du, 0) / dt:.1f} % of the step); norm[0]={float(norm[0]):.3f}")
+    cg = get_conditioning_method("cg", op, get_noise("gaussian", sigma=0.05), rho_scale=1.0, iters=5)
+    for i in range(2):
+        x, _ = smp.cg_step(model, x, 999 - i, y, cg, fkw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        x, dist = smp.cg_step(model, x, 997 - i, y, cg, fkw)
+    torch.cuda.synchronize()
+    dc = (time.perf_counter() - t0) / args.steps
+    print(f"N={n} {args.operator}: full cg step (iters=5) {dc * 1e3:.1f} ms ({n / dc:.1f} particle-steps/s) = "
+          f"{dc / dt:.2f} x the ps step; dist[0]={float(dist[0]):.3f}")
 
 
 if __name__ == "__main__":

@@ -19,6 +19,11 @@ M (default 4) images x K = 16, there also against M single-image calls of each f
 one process: (a) torch.randn + the pointer launch (noise_draw = "torch"), (b) kernels.randn (dpsx_randn_f32) + the pointer
 launch, (c) the draw inside the launch (step_fwd(rng=) / search_step_one(rng=)); a route without an in-kernel form is
 marked and its (c) is the front end's fallback, which is (b).
+    python tools/kbench.py --cg                                                       (the CG data-consistency step, 256^2)
+--cg: OpHandle.cg_step at iters = 1 and 5 beside the fused `ps` step (K1 + K2 + K3) and the plain A / A^T / K3 launches,
+N = 64 and 16, Gaussian / motion / SR x4 / inpainting, 3 x --reps repetitions alternated in one process.  Per launch: the
+step's time over its enqueued launches (5 + 5 iters - 1).  The vector side of one middle iteration (||t||^2, the d / r
+update, the p update: (9 + m / e) P by shape arithmetic) is priced as (t(5) - t(1)) / 4 - t(A) - t(A^T), beside K3's rate.
 """
 import argparse
 import os
@@ -43,7 +48,10 @@ def main():
     ap.add_argument("--images", type=int, default=None, help="time the multi-image step of M images x --particles")
     ap.add_argument("--resample", action="store_true", help="time the resampling step (multinomial / draw + gathers / fused)")
     ap.add_argument("--noise-draw", action="store_true", help="time the step noise: torch.randn / device fill / in-kernel draw")
+    ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
     args = ap.parse_args()
+    if args.cg:
+        return cg_step(args)
     if args.noise_draw:
         return noise_draw(args)
     if args.resample:
@@ -177,6 +185,76 @@ def multi_image(args):
         ts = np.concatenate(res[name])
         print(f"images {args.operator} M={M} K={k} {label:28s} avg {ts.mean():8.1f} us/step  min {ts.min():8.1f}  "
               f"{n / ts.mean():8.3f} M particle-steps/s (x0_hat store {'off' if args.no_x0 else 'on'})", flush=True)
+
+
+def cg_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    P = bench.P_BYTES
+    rho = 0.05 ** 2 / float(ck.b) ** 2                    # the method's default: rho_scale = 1, sigma_n = 0.05
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for n in (64, 16):
+        for name in ("gaussian_blur", "motion_blur", "super_resolution", "inpainting"):
+            op, fkw = bench.build_operator(name, dev, sigma=args.sigma)
+            x_t, ring, truth, meas_noise = bench.synth_inputs(n, 2, dev, 1234)
+            yy = op.forward(truth.to(dev), **fkw).detach()
+            y = (yy + meas_noise.to(dev)[..., :yy.shape[-2], :yy.shape[-1]]).contiguous()
+            handle = op.hip_handle_for(fkw["mask"]) if name == "inpainting" else op.hip_handle(x_t)
+            buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+            u = torch.randn((n,) + tuple(y.shape[1:]), device=dev)
+            x0_hat = truth.to(dev).expand(n, -1, -1, -1).contiguous()
+            x0_hat = (x0_hat + 0.3 * torch.randn_like(x0_hat)).clamp_(-1, 1)
+
+            def ps(i):
+                r = ring[i % 2]
+                kernels.step_fwd(handle, buf, x_t, r["model_out"], r["noise"], y, ck, want_x0=False)
+                kernels.step_bwd(handle, buf, y, 0.3, 1, ck)
+                kernels.step_update(buf, r["g_unet"], ck)
+
+            ps(0)
+            forms = {"ps": ps,
+                     "cg1": lambda i: handle.cg_step(x0_hat, buf.sample, y, rho, 1, ck),
+                     "cg5": lambda i: handle.cg_step(x0_hat, buf.sample, y, rho, 5, ck),
+                     "A": lambda i: handle.forward(x_t),
+                     "At": lambda i: handle.adjoint(u, x=x_t, in_hw=(256, 256)),
+                     "K3": lambda i: kernels.step_update(buf, ring[i % 2]["g_unet"], ck)}
+            res = {}
+            for rep in range(3):                       # alternated: every form sees the same box state
+                for key, fn in forms.items():
+                    res.setdefault(key, []).append(timed(fn))
+            t = {key: float(np.concatenate(v).mean()) for key, v in res.items()}
+            lo = {key: float(np.concatenate(v).min()) for key, v in res.items()}
+            m_over_e = y[0].numel() / x_t[0].numel()
+            vec_us = (t["cg5"] - t["cg1"]) / 4 - t["A"] - t["At"]
+            vec_bytes = (9 + m_over_e) * P * n
+            k3_bytes = bench.algo_p(name, x0_store=False)["algorithmic"]["upd"] * P * n
+            tag = f"cg {name:16s} N={n:2d}"
+            print(f"{tag} ps step (K1+K2+K3) avg {t['ps']:8.1f} us  min {lo['ps']:8.1f}", flush=True)
+            for it, key in ((1, "cg1"), (5, "cg5")):
+                launches = 5 + 5 * it - 1
+                print(f"{tag} cg_step iters={it}     avg {t[key]:8.1f} us  min {lo[key]:8.1f}   {launches:2d} launches, "
+                      f"{t[key] / launches:6.1f} us each   {t[key] / t['ps']:5.2f} x the ps step", flush=True)
+            print(f"{tag} A {t['A']:7.1f} us  A^T {t['At']:7.1f} us  K3 {t['K3']:7.1f} us = {k3_bytes / t['K3'] / 1e3:7.1f} GB/s"
+                  f"   vector side of one iteration {vec_us:7.1f} us = {vec_bytes / max(vec_us, 1e-3) / 1e3:7.1f} GB/s "
+                  f"({9 + m_over_e:.2f} P/particle) = {vec_bytes / max(vec_us, 1e-3) / (k3_bytes / t['K3']):4.2f} x K3's rate",
+                  flush=True)
 
 
 def resample_step(args):
