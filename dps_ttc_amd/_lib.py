@@ -103,6 +103,9 @@ SIGNATURES = {
                                              _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
     "dpsx_search_step_one_seg_rng_f32": (c_int, [c_void_p, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _f, _f, _i64,
                                                  _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_topk_seg_f32": (c_int, [_f, _i64, _i64, _i64, _p, _f, _p]),
+    "dpsx_search_step_beam_f32": (c_int, [c_void_p, _f, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _f, _f, _i64, _i64,
+                                          _i64, _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

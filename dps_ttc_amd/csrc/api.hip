@@ -918,15 +918,22 @@ static int search_seg_args(const dpsx_op *op, const float *x_t, const float *mod
 // All six exported search steps.  noise / rng: the source of S1's noise (rng != NULL: drawn inside S1's launch, noise is
 // then NULL).  segments: 0 = one particle set; M >= 1 = M images of n / M particles, the select runs per image and
 // best_idx_dev / best_val_dev are [M].  one_state: x_t / model_out hold ONE state per image instead of one per particle.
+// beam >= 1 (the beam step, with one_state): x_t / model_out hold `states` states, n / states consecutive proposals each,
+// and the select keeps the first `beam` particles of every image: best_idx_dev / best_val_dev and x_next are [M beam].
 static int search_step_impl(dpsx_op *op, const float *x_t, const float *model_out, const float *noise, const dpsx_rng *rng,
                             const float *y, int64_t y_n, float *sample, float *costs, int64_t *best_idx_dev,
                             float *best_val_dev, float *x_next, int64_t segments, bool one_state, int64_t n, int64_t c,
                             int64_t h, int64_t w, const dpsx_coefs *coefs_host, void *workspace, int64_t workspace_bytes,
-                            void *stream)
+                            void *stream, int64_t states = 0, int64_t beam = 0)
 {
     int rc = search_seg_args(op, x_t, model_out, rng ? (const void *)rng : (const void *)noise, y, y_n, sample, costs,
                              best_idx_dev, x_next, segments, one_state, n, c, h, w, coefs_host);
     if (rc != DPSX_OK) return rc;
+    if (beam) {
+        if (segments < 1 || states < 1 || n % states != 0 || states % segments != 0 || beam < 1 || beam > n / segments)
+            return DPSX_EINVAL;
+        if (n / segments > kTopbMaxK || segments > (1 << 24)) return DPSX_EUNSUPPORTED;
+    }
     RngK rk{};
     if (rng && (rc = to_rngk(rng, n, rk)) != DPSX_OK) return rc;
     // S1 (no x0_hat store) -> scoring launch -> one launch for costs + select -> the winner's replication.
@@ -948,10 +955,15 @@ static int search_step_impl(dpsx_op *op, const float *x_t, const float *model_ou
     const int64_t images = std::max<int64_t>(segments, 1);
     const int parts = score_parts(op, c, h, w);
     rc = posterior_fwd(x_t, model_out, noise, rng != nullptr, rk, nullptr, sample, nullptr, n, chw, to_coefs(coefs_host), s,
-                       one_state, images);
+                       one_state, beam ? states : images);
     if (rc != DPSX_OK) return rc;
     if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
     const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
+    if (beam) {       // costs + the top-`beam` select per image: one launch; the winners' copies: one more (DESIGN.md "beam search")
+        rc = finalize_topb(tail, (int)images, (int)beam, s);
+        if (rc != DPSX_OK || !x_next) return rc;
+        return gather_f32(sample, best_idx_dev, x_next, images * beam, n, chw, s);
+    }
     static const bool unfused = getenv("DPSX_SEARCH_ONE_UNFUSED") != nullptr;       // A/B switch for tools/kbench_search.py
     if (one_state && !unfused && x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))
         return finalize_select_copy(tail, (int)images, sample, x_next, chw, s);   // costs + select + the winners' copies: one launch
@@ -1024,6 +1036,19 @@ int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float 
                             stream);
 }
 
+int dpsx_search_step_beam_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                              const dpsx_rng *rng_host, const float *y, int64_t y_n, float *sample, float *costs,
+                              int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments, int64_t states,
+                              int64_t beam, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                              void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!coefs_host || ((coefs_host->add_noise & 1) && (noise != nullptr) == (rng_host != nullptr))) return DPSX_EINVAL;
+    if (segments < 1 || beam < 1) return DPSX_EINVAL;
+    return search_step_impl(op, x_t, model_out, rng_host ? nullptr : noise, rng_host, y, y_n, sample, costs, best_idx_dev,
+                            best_val_dev, x_next, segments, true, n, c, h, w, coefs_host, workspace, workspace_bytes, stream,
+                            states, beam);
+}
+
 int dpsx_score_f32(dpsx_op *op, const float *x, const float *y, int64_t y_n, float *costs, int64_t n, int64_t c,
                    int64_t h, int64_t w, void *workspace, int64_t workspace_bytes, void *stream)
 {
@@ -1060,6 +1085,14 @@ int dpsx_argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *id
 {
     if (!v || !idx_out_dev || segments < 1 || segments > (1 << 24) || k < 1) return DPSX_EINVAL;
     return argmin_seg_f32(v, segments, k, idx_out_dev, val_out_dev, (hipStream_t)stream);
+}
+
+int dpsx_topk_seg_f32(const float *v, int64_t segments, int64_t k, int64_t b, int64_t *idx_out_dev, float *val_out_dev,
+                      void *stream)
+{
+    if (!v || !idx_out_dev || segments < 1 || k < 1 || b < 1 || b > k) return DPSX_EINVAL;
+    if (k > kTopbMaxK || segments > (1 << 24)) return DPSX_EUNSUPPORTED;
+    return topk_seg_f32(v, segments, k, b, idx_out_dev, val_out_dev, (hipStream_t)stream);
 }
 
 int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst, int64_t n_out, int64_t n_src,

@@ -574,8 +574,13 @@ int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipS
 // and receive each segment's winner as a global particle index.  _copy: dst[m] = src[best[m]] (chw % 4 == 0, aligned)
 int finalize_select(const Tail &t, int segments, hipStream_t s);
 int finalize_select_copy(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
+// costs + the first b particles of every segment (of t.n / segments <= kTopbMaxK particles) under the select's order:
+// t.best_idx / t.best_val (nullable) are [segments, b]
+constexpr int kTopbMaxK = 4096;          // a segment's keys and costs live in 12 k bytes of LDS (48 KB at the cap)
+int finalize_topb(const Tail &t, int segments, int b, hipStream_t s);
 // segmented argmin over v [segments, k] -> idx[m] = m * k + argmin (torch.argmin order), val[m] (nullable)
 int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s);
+int topk_seg_f32(const float *v, int64_t segments, int64_t k, int64_t b, int64_t *idx, float *val, hipStream_t s);
 // dst[p] = src[ids[p / per]] for p < n_out (per = particles per id); an id outside [0, n_src) fills dst[p] with NaN
 int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t per, int64_t n_src,
                       int64_t chw, hipStream_t s);

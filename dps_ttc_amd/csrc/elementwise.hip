@@ -301,20 +301,13 @@ int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipS
 // Measured alternative (r02): finishing inside the scoring launch ("last block done", common.h: Tail) costs every short
 // scoring block two dependent memory round trips while it holds its LDS -- 42 us instead of ~25 us at N = 64.
 constexpr int kSelThreads = 1024;
-// the body of the finalisation + select; `writer`: this block stores the costs / the select's outputs (with several blocks
-// -- k_finalize_select_copy -- every block computes the same values in the same order and ONE of them stores).
-// -> the winner's index (block-uniform, valid in every thread), -1 when no select was asked for.
-// [lo, hi): the particles this block finishes and selects over (a segment of a multi-image batch; 0, t.n otherwise) -- each
-// particle's value comes out of the same loads and adds whatever the range, so segmented and whole launches agree bit for
-// bit; the winner (a global particle index) goes to best_idx[slot] / best_val[slot].
-__device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const bool writer, const int lo, const int hi,
-                                                        const int slot)
+// the cost-finishing loop of the finalisation launches (k_finalize_select*, k_finalize_topb): one copy, so a particle's
+// cost is the same bits whichever of them finishes it.  `writer`: this block stores the costs.  [lo, hi): the particles this
+// block finishes.  each(v, p): called by lane 0 of the wave that finished particle p, with its (combined) cost.
+template <class Each>
+__device__ __forceinline__ void finalize_costs(const Tail &t, const bool writer, const int lo, const int hi, Each &&each)
 {
-    __shared__ float s_v[kSelThreads / kWave];
-    __shared__ int64_t s_i[kSelThreads / kWave];
-    __shared__ int64_t s_best;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nw = kSelThreads / kWave;
-    ArgMin best{0.0f, -1};
     constexpr int B = 4;          // particles per wave in flight: their partial loads are issued together (one latency)
     for (int p0 = lo + wave; p0 < hi; p0 += nw * B) {
         double acc[B];
@@ -347,11 +340,30 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
                     else if (t.potential == POT_DIFF) v = v - q;
                 }
                 if (writer) t.out[p] = v;
-                const ArgMin c{v, p};
-                if (argmin_better(c, best)) best = c;
+                each(v, p);
             }
         }
     }
+}
+
+// the body of the finalisation + select; `writer`: this block stores the costs / the select's outputs (with several blocks
+// -- k_finalize_select_copy -- every block computes the same values in the same order and ONE of them stores).
+// -> the winner's index (block-uniform, valid in every thread), -1 when no select was asked for.
+// [lo, hi): the particles this block finishes and selects over (a segment of a multi-image batch; 0, t.n otherwise) -- each
+// particle's value comes out of the same loads and adds whatever the range, so segmented and whole launches agree bit for
+// bit; the winner (a global particle index) goes to best_idx[slot] / best_val[slot].
+__device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const bool writer, const int lo, const int hi,
+                                                        const int slot)
+{
+    __shared__ float s_v[kSelThreads / kWave];
+    __shared__ int64_t s_i[kSelThreads / kWave];
+    __shared__ int64_t s_best;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nw = kSelThreads / kWave;
+    ArgMin best{0.0f, -1};
+    finalize_costs(t, writer, lo, hi, [&](float v, int p) {
+        const ArgMin c{v, p};
+        if (argmin_better(c, best)) best = c;
+    });
     if (!t.best_idx) return -1;
     if (lane == 0) { s_v[wave] = best.v; s_i[wave] = best.i; }
     __syncthreads();
@@ -403,6 +415,153 @@ int finalize_select_copy(const Tail &t, int segments, const float *src, float *d
     const int64_t chw4 = chw / 4;
     const dim3 grid((unsigned)((chw4 + kSelThreads - 1) / kSelThreads), (unsigned)segments);
     k_finalize_select_copy<<<grid, kSelThreads, 0, s>>>(t, t.n / segments, src, dst, chw4);
+    return check_launch();
+}
+
+// ---- top-B select: the first b particles of a segment under argmin_better's total order, in that order (rank 0 is what
+// the selects above return).  The order as integers: an order-preserving uint32 key of the cost (NaN -> 0, below -inf's
+// 0x007fffff; -0.0 and +0.0 share a key), ties broken by the lower index -- (key << 32 | index) as one 64-bit integer.
+// Rank r is the particle with r such integers below its own: a property of the segment, not of how the work is split, and
+// every output slot has exactly one writer (no atomics).  Two forms, chosen by the segment length (measured: DESIGN.md
+// "beam search"): up to kTopbCountMax particles a thread per candidate COUNTS the pairs before its own (every lane reads the
+// same LDS words: broadcasts, no barrier after the load); above it the block SORTS the 64-bit integers (LDS bitonic
+// network), since the count grows with the square of the length.
+#ifndef DPSX_TOPB_COUNT_MAX
+#define DPSX_TOPB_COUNT_MAX 512          // overridden only to measure one form alone over all lengths
+#endif
+constexpr int kTopbCountMax = DPSX_TOPB_COUNT_MAX;
+
+__device__ __forceinline__ uint32_t order_key(float v)
+{
+    if (v != v) return 0u;
+    if (v == 0.0f) return 0x80000000u;
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// one segment's select state in LDS: the costs, and the keys -- uint32 [k] for the count, uint64 (key << 32 | index) [the
+// power of two >= k] for the sort
+struct TopbLds {
+    unsigned long long sort[kTopbMaxK];
+    float val[kTopbMaxK];
+};
+
+__device__ __forceinline__ int topb_pow2(const int k)
+{
+    int p = 1;
+    while (p < k) p <<= 1;
+    return p;
+}
+
+// entry j of the segment (any thread, each j once)
+__device__ __forceinline__ void topb_put(TopbLds &l, const int k, const int j, const float v)
+{
+    l.val[j] = v;
+    if (k > kTopbCountMax) l.sort[j] = ((unsigned long long)order_key(v) << 32) | (unsigned)j;
+    else reinterpret_cast<uint32_t *>(l.sort)[j] = order_key(v);
+}
+
+// the count.  keys[0 .. k rounded up to 4): the surplus holds 0xffffffff (no cost has that key).  Candidate i's wave reads
+// the keys in three runs -- all j below its 64 candidates (j < i: key <= counts), its own 64 (the full comparison), all j
+// above (key < counts) -- so the long runs cost one compare and one add per pair.
+__device__ __forceinline__ void topb_count_store(const TopbLds &l, const int k, const int b, const int64_t base,
+                                                 int64_t *idx, float *val)
+{
+    const uint32_t *keys = reinterpret_cast<const uint32_t *>(l.sort);
+    const uint4 *k4 = reinterpret_cast<const uint4 *>(l.sort);
+    const int n4 = (k + 3) / 4;
+    for (int i = threadIdx.x; i < k; i += kSelThreads) {
+        const uint32_t ki = keys[i];
+        const int q0 = __builtin_amdgcn_readfirstlane(i) / kWave * (kWave / 4), q1 = min(q0 + kWave / 4, n4);
+        int cnt = 0;
+        for (int q = 0; q < q0; ++q) {
+            const uint4 c = k4[q];
+            cnt += (c.x <= ki) + (c.y <= ki) + (c.z <= ki) + (c.w <= ki);
+        }
+        for (int q = q0; q < q1; ++q) {
+            const uint4 c = k4[q];
+            const int j = 4 * q;
+            cnt += (c.x < ki || (c.x == ki && j < i)) + (c.y < ki || (c.y == ki && j + 1 < i)) +
+                   (c.z < ki || (c.z == ki && j + 2 < i)) + (c.w < ki || (c.w == ki && j + 3 < i));
+        }
+        for (int q = q1; q < n4; ++q) {
+            const uint4 c = k4[q];
+            cnt += (c.x < ki) + (c.y < ki) + (c.z < ki) + (c.w < ki);
+        }
+        if (cnt < b) {
+            idx[cnt] = base + i;
+            if (val) val[cnt] = l.val[i];
+        }
+    }
+}
+
+// the sort: an ascending bitonic network over sort[0 .. n2), n2 the power of two >= k, the surplus holding all ones (above
+// every entry); the integers are distinct, so the outcome is the one sorted sequence
+__device__ __forceinline__ void topb_sort_store(TopbLds &l, const int k, const int b, const int64_t base, int64_t *idx,
+                                                float *val)
+{
+    const int n2 = topb_pow2(k);
+    for (int size = 2; size <= n2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < n2 / 2; t += kSelThreads) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;      // the pair t of this stage
+                const unsigned long long x = l.sort[lo], y = l.sort[hi];
+                if ((x > y) == ((lo & size) == 0)) { l.sort[lo] = y; l.sort[hi] = x; }
+            }
+            __syncthreads();
+        }
+    for (int r = threadIdx.x; r < b; r += kSelThreads) {
+        const int i = (int)(unsigned)l.sort[r];
+        idx[r] = base + i;
+        if (val) val[r] = l.val[i];
+    }
+}
+
+// all threads, after every entry has been put: the surplus keys, the barrier, the select
+__device__ __forceinline__ void topb_select_store(TopbLds &l, const int k, const int b, const int64_t base, int64_t *idx,
+                                                  float *val)
+{
+    if (k > kTopbCountMax) {               // block-uniform
+        for (int j = k + threadIdx.x; j < topb_pow2(k); j += kSelThreads) l.sort[j] = ~0ull;
+        __syncthreads();
+        topb_sort_store(l, k, b, base, idx, val);
+    } else {
+        for (int j = k + threadIdx.x; j < ((k + 3) & ~3); j += kSelThreads) reinterpret_cast<uint32_t *>(l.sort)[j] = 0xffffffffu;
+        __syncthreads();
+        topb_count_store(l, k, b, base, idx, val);
+    }
+}
+
+// block m finishes the costs of segment m ([m k, (m + 1) k), k <= kTopbMaxK) exactly as k_finalize_select does and stores
+// its first b particles: best_idx[m b + r] (global index) / best_val[m b + r] for rank r
+__global__ __launch_bounds__(kSelThreads) void k_finalize_topb(Tail t, int k, int b)
+{
+    __shared__ __attribute__((aligned(16))) TopbLds l;
+    const int m = blockIdx.x, lo = m * k;
+    finalize_costs(t, true, lo, lo + k, [&](float v, int p) { topb_put(l, k, p - lo, v); });
+    topb_select_store(l, k, b, lo, t.best_idx + (int64_t)m * b, t.best_val ? t.best_val + (int64_t)m * b : nullptr);
+}
+
+// the same select over given values: v [segments, k] -> idx / val (nullable) [segments, b]
+__global__ __launch_bounds__(kSelThreads) void k_topk_seg(const float *__restrict__ v, int k, int b, int64_t *__restrict__ idx,
+                                                          float *__restrict__ val)
+{
+    __shared__ __attribute__((aligned(16))) TopbLds l;
+    const int64_t m = blockIdx.x, lo = m * k;
+    for (int j = threadIdx.x; j < k; j += kSelThreads) topb_put(l, k, j, v[lo + j]);
+    topb_select_store(l, k, b, lo, idx + m * b, val ? val + m * b : nullptr);
+}
+
+int finalize_topb(const Tail &t, int segments, int b, hipStream_t s)
+{
+    if (t.n == 0) return DPSX_OK;
+    k_finalize_topb<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments, b);
+    return check_launch();
+}
+
+int topk_seg_f32(const float *v, int64_t segments, int64_t k, int64_t b, int64_t *idx, float *val, hipStream_t s)
+{
+    k_topk_seg<<<(unsigned)segments, kSelThreads, 0, s>>>(v, (int)k, (int)b, idx, val);
     return check_launch();
 }
 

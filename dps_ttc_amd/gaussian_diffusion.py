@@ -687,6 +687,20 @@ class SearchDDPM(DDPM):
     #: noise draws, costs and winner indices are the same); False keeps N copies as the reference does.
     single_state = True
 
+    #: Beam search: B > 1 keeps the B best proposals of every image per step instead of one (dpsx_search_step_beam_f32).
+    #: The first step scores the N given particles; every later step runs from the [images * B] surviving states -- one
+    #: model evaluation per state, N / (images * B) proposals from each, the per-image top-B select on the device (the
+    #: step without noise: one proposal per state, the select ranks the B survivors).  1: the greedy loop below, untouched.
+    beam_width = 1
+
+    @property
+    def last_parents(self):
+        """[images * B] int64: the beam (0 .. B - 1, inside its image) whose proposal each survivor of the last beam step
+        was -- (last_best % per) // K with per = N / images proposals per image, K = per / B per beam (per = B, K = 1 at
+        the step without noise, where every state proposes once)"""
+        per, k = self._beam_geom
+        return (self.last_best % per) // k
+
     def _proposal_noise(self, like, n, idx, segments, noise):
         """the noise source of a step's n proposals -> (noise, rng): the caller's tensor; else the record of the in-launch
         draw (noise_draw = 'device'); else a torch draw [n, C, H, W] on like's device"""
@@ -723,8 +737,53 @@ class SearchDDPM(DDPM):
             winner = self.global_select(costs, sample, n_out=1)
         return winner, costs
 
+    def search_step_beam(self, model, states, n, idx, measurement, handle, noise=None, segments=None):
+        """One beam step from `states` [S,C,H,W] (S = n on the first step, images * beam_width after it): n proposals,
+        n / S per state -> (survivors [images * beam_width, C, H, W], costs [n], their costs [images * beam_width])."""
+        with torch.no_grad():
+            model_out = self._call_model(model, states, idx)
+        noise, rng = self._proposal_noise(states, n, idx, segments, noise)
+        winners, _, costs, best, val = handle.search_step_beam(states, model_out, noise, measurement, self.step_coefs[idx],
+                                                               n=n, beam=self.beam_width, segments=segments, rng=rng)
+        self.last_best = best
+        return winners, costs, val
+
+    def _beam_loop(self, model, x_start, measurement, operator, **kwargs):
+        """p_sample_loop with beam_width = B > 1"""
+        img, n = x_start.detach(), x_start.shape[0]
+        beam = int(self.beam_width)
+        segments = self._segments(measurement, n, kwargs.get('n_images', None), infer=False)
+        per = n // (segments or 1)
+        if beam < 1 or per % beam:
+            raise ValueError(f"beam_width = {beam} does not divide the {per} particles per image")
+        if self.global_select is not None:
+            raise NotImplementedError("beam_width > 1 with a global (multi-rank) select is not supported: the champion "
+                                      "exchange picks one winner, not the B best across ranks")
+        if not self.single_state:
+            raise ValueError("beam_width > 1 runs from the surviving states only: single_state = False does not apply")
+        kernels.require_cuda(img, "x_start")
+        if not self.hip_posterior:
+            raise NotImplementedError("search_ddpm runs the epsilon / learned_range / clip configuration")
+        mask = kwargs.get('mask', None)
+        handle = operator.hip_handle_for(mask) if operator.name == 'inpainting' else operator.hip_handle(img)
+        self.best_paths, self.best_costs = [], []
+        self._step_rng(0, n, segments)    # validates noise_draw before the first step
+        state = img                       # the first step: n states, one proposal each; then [images * beam]
+        for idx in range(self.num_timesteps - 1, -1, -1):
+            # the step that adds no noise (the last one): the proposals of one state would all be equal and fill the beam
+            # with copies of the best state's, so every state proposes once and the select only ranks the survivors
+            m = n if self.step_coefs[idx].add_noise & 1 else state.shape[0]
+            self._beam_geom = (m // (segments or 1), max(m // (segments or 1) // beam, 1))
+            state, costs, kept = self.search_step_beam(model, state, m, idx, measurement, handle, segments=segments)
+            if kwargs.get('trace', False):
+                self.best_costs.append(costs)
+        self.beam_states, self.beam_costs = state, kept
+        return state.repeat_interleave(per // beam, dim=0)     # image-major, then rank-major: the call's [N, ...] shape
+
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, operator,
                       potential_type='min', resample_every_steps=10, rs_temp=0.1, **kwargs):
+        if self.beam_width != 1:
+            return self._beam_loop(model, x_start, measurement, operator, **kwargs)
         img = x_start.detach()
         kernels.require_cuda(img, "x_start")
         if not self.hip_posterior:

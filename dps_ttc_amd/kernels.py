@@ -364,6 +364,39 @@ class OpHandle:
                              f"model_out {tuple(model_out_one.shape)}, {what}")
         return self._search(x_one, model_out_one, noise, rng, y, coefs, n, states if want_winner else 0, segments, one=True)
 
+    def search_step_beam(self, x_states, model_out_states, noise=None, y=None, coefs=None, *, n, beam, segments=None,
+                         rng=None, want_winners=True):
+        """The beam step (include/dpsx.h: dpsx_search_step_beam_f32): x_states [S, C, H, W] and model_out_states
+        [S, 2C, H, W] feed n proposals, n / S consecutive ones per state; every image (segments=M, default 1; M divides S)
+        keeps its `beam` best proposals under the select's order -> (winners [M * beam, C, H, W] or None, sample [n, ...],
+        costs [n], best [M * beam] global particle indices, rank-major inside an image, costs[best]).
+        S == n is a loop's first step, S == M * beam every later one; noise= [n, C, H, W] or rng=."""
+        _noise_or_rng(noise, rng)
+        x, mo, y = _nchw(f32c(x_states, "x_t")), f32c(model_out_states, "model_out"), f32c(y, "measurement")
+        noise = None if noise is None else _nchw(f32c(noise, "noise"))
+        n, beam, seg = int(n), int(beam), 1 if segments is None else int(segments)
+        states, (c, h, w) = x.shape[0], x.shape[1:]
+        if n < 1:
+            raise ValueError("beam search over an empty particle set")
+        if seg < 1 or states < 1 or n % states or states % seg or mo.shape[0] != states or \
+                mo[0].numel() != 2 * c * h * w or (noise is not None and noise.shape != (n, c, h, w)):
+            raise ValueError(f"{n} proposals from {states} state(s) of {seg} image(s) expected: x {tuple(x.shape)}, "
+                             f"model_out {tuple(mo.shape)}" + ("" if noise is None else f", noise {tuple(noise.shape)}"))
+        if not 1 <= beam <= n // seg:
+            raise ValueError(f"beam = {beam} does not lie in [1, {n // seg}], the proposals per image")
+        dev = x.device
+        sample = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+        winners = torch.empty((seg * beam, c, h, w), dtype=torch.float32, device=dev) if want_winners else None
+        costs = torch.empty(n, dtype=torch.float32, device=dev)
+        best = torch.empty(seg * beam, dtype=torch.int64, device=dev)
+        val = torch.empty(seg * beam, dtype=torch.float32, device=dev)
+        ws = self.workspace(n, c, h, w, dev)
+        check(lib().dpsx_search_step_beam_f32(self._h, ptr(x), ptr(mo), ptr(noise), None if rng is None else byref(rng.rec()),
+                                              ptr(y), y.shape[0], ptr(sample), ptr(costs), ptr(best), ptr(val), ptr(winners),
+                                              seg, states, beam, n, c, h, w, byref(coefs), ptr(ws), ws.numel(), stream_of(x)),
+              "dpsx_search_step_beam_f32")
+        return winners, sample, costs, best, val
+
     def cg_step(self, x0_hat, sample, y, rho, iters, coefs, want_d=False):
         """The CG data-consistency step (include/dpsx.h: dpsx_cg_step_f32): `iters` conjugate-gradient iterations per
         particle on (A^T A + rho I)(x0_hat + d) = A^T y + rho x0_hat from d = 0, then x_next = sample + kappa d with the
@@ -510,6 +543,21 @@ def argmin_seg(v, segments, want_value=False):
     val = torch.empty(segments, dtype=torch.float32, device=v.device) if want_value else None
     check(lib().dpsx_argmin_seg_f32(ptr(v), segments, v.numel() // segments, ptr(out), ptr(val), stream_of(v)),
           "dpsx_argmin_seg_f32")
+    return (out, val) if want_value else out
+
+
+def topk_seg(v, segments, b, want_value=False):
+    """v [segments * K] (or [segments, K]) -> [segments * b] int64 global indices: the first b entries of every segment
+    under argmin_seg's order (NaN first, then the lower value, ties by the lower index), in that order; b = 1 is argmin_seg.
+    On the device in one launch.  want_value: also the [segments * b] values."""
+    v = f32c(v.reshape(-1), "scores")
+    segments, b = int(segments), int(b)
+    if segments < 1 or v.numel() == 0 or v.numel() % segments:
+        raise ValueError(f"{v.numel()} scores do not split into {segments} non-empty segments")
+    out = torch.empty(segments * max(b, 0), dtype=torch.int64, device=v.device)
+    val = torch.empty(segments * max(b, 0), dtype=torch.float32, device=v.device) if want_value else None
+    check(lib().dpsx_topk_seg_f32(ptr(v), segments, v.numel() // segments, b, ptr(out), ptr(val), stream_of(v)),
+          "dpsx_topk_seg_f32")
     return (out, val) if want_value else out
 
 

@@ -301,6 +301,13 @@ int dpsx_argmin_f32(const float *v, int64_t n, int64_t *idx_out_dev, float *val_
  * val_out_dev[m] (nullable) its value -- the per-image best-of-N of a multi-image batch (best_of_n_simple.py:32-40). */
 int dpsx_argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx_out_dev, float *val_out_dev,
                         void *stream);
+/* The first b entries of every segment under the same order, in that order: NaN before every number (among NaNs the lower
+ * index first), then the lower value, equal values (-0.0 == +0.0) by the lower index.  v is [segments, k];
+ * idx_out_dev[m * b + r] is the global index of segment m's rank r, val_out_dev[m * b + r] (nullable) its value.  b = 1
+ * is dpsx_argmin_seg_f32.  A rank is a count of the entries before it, so the result does not depend on how the launch
+ * splits the work.  1 <= b <= k (DPSX_EINVAL); k <= 4096 (DPSX_EUNSUPPORTED above). */
+int dpsx_topk_seg_f32(const float *v, int64_t segments, int64_t k, int64_t b, int64_t *idx_out_dev, float *val_out_dev,
+                      void *stream);
 /* dst[p] = src[ids[p]]   (ids: device int64 [n_out]; an id outside [0, n_src) fills dst[p] with NaN) */
 int dpsx_gather_f32(const float *src, const int64_t *ids_dev, float *dst,
                     int64_t n_out, int64_t n_src, int64_t chw, void *stream);
@@ -376,6 +383,22 @@ int dpsx_search_step_one_seg_rng_f32(dpsx_op *op, const float *x_t, const float 
                                      int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments,
                                      int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
                                      void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The beam step: the search step that keeps the `beam` best proposals of every image instead of one.
+ * x_t [states, c, h, w], model_out [states, 2c, h, w]: proposal p of n reads state p / (n / states); n % states == 0 and
+ * states % segments == 0 (image m owns the states [m states / segments, ...) and the particles [m n / segments, ...)).
+ * states == n is a loop's first step (n distinct particles, one proposal each), states == segments * beam every later one.
+ * noise [n, c, h, w] or rng_host: exactly one of them when the step adds noise.  y_n is 1 or segments.
+ * S1 -> the scoring launch -> costs + the per-image top-`beam` select (the order of dpsx_topk_seg_f32) -> the winners'
+ * gather: best_idx_dev / best_val_dev (nullable) are [segments * beam] (global particle indices, rank-major inside an
+ * image), x_next (nullable) [segments * beam, c, h, w] with x_next[m * beam + r] = sample[best_idx_dev[m * beam + r]].
+ * x_next must not be x_t or sample.  beam = 1 with states = segments is dpsx_search_step_one_seg_f32 / _rng bit for bit.
+ * 1 <= beam <= n / segments (DPSX_EINVAL); n / segments <= 4096 (DPSX_EUNSUPPORTED above). */
+int dpsx_search_step_beam_f32(dpsx_op *op, const float *x_t, const float *model_out, const float *noise,
+                              const dpsx_rng *rng_host, const float *y, int64_t y_n, float *sample, float *costs,
+                              int64_t *best_idx_dev, float *best_val_dev, float *x_next, int64_t segments, int64_t states,
+                              int64_t beam, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
+                              void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator

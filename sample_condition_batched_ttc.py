@@ -115,6 +115,9 @@ def parse_args(argv=None):
                    help="the step noise and x_start: torch.randn over the whole batch (default) or the library's "
                         'counter-based draw keyed on (--seed, step, path id, element): a path then draws the same noise '
                         'whatever --batch_size, --particle_groups, --images_per_batch and the number of ranks are')
+    p.add_argument('--beam_width', type=int, default=1,
+                   help='search_ddpm: keep this many best proposals per image and step instead of one (beam search); '
+                        'must divide batch_size; one rank only')
     return p.parse_args(argv)
 
 
@@ -153,10 +156,28 @@ def check_images_per_batch(args, sampler_name, world):
                          "for all particles")
 
 
+def check_beam_width(args, sampler_name, world):
+    """--beam_width: reject what the beam loop does not support, before any GPU work (one-line message)"""
+    b = args.beam_width
+    if b < 1:
+        raise SystemExit(f"--beam_width must be at least 1 (got {b})")
+    if b == 1:
+        return
+    if sampler_name != 'search_ddpm':
+        raise SystemExit(f"--beam_width > 1 is an option of sampler search_ddpm (the diffusion config names {sampler_name})")
+    if args.batch_size % b:
+        raise SystemExit(f"--beam_width {b} does not divide --batch_size {args.batch_size}, the particles per image")
+    if world > 1:
+        raise SystemExit("--beam_width > 1 runs on one rank only: the multi-rank select exchanges one winner, not the "
+                         f"best {b} (WORLD_SIZE={world})")
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    if args.beam_width != 1:
+        check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
     if args.images_per_batch != 1:
         check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
     if world > 1:
@@ -209,6 +230,7 @@ def main(argv=None):
     sampler.particle_groups = max(1, args.particle_groups)
     sampler.resample_draw = args.resample_draw
     sampler.noise_draw = args.noise_draw
+    sampler.beam_width = args.beam_width
     sampler.noise_seed = args.seed or 0          # the same on every rank: the path id tells the ranks' particles apart
     groups = args.n_paths // args.batch_size
     if world > 1 and diffusion_config['sampler'] in ('search_ddpm', 'ttc_ddim'):
