@@ -102,12 +102,11 @@ int dpsx_posterior_fwd_rng_f32(const float *x_t, const float *model_out, const d
 }
 
 // ------------------------------------------------------------------ operator objects
-// arrival counters of the in-launch reductions (common.h: Tail); zero between launches
+// arrival counters of the in-launch norm (common.h: NormTail); zero between launches
 static int alloc_counters(dpsx_op *op)
 {
-    const size_t bytes = (size_t)(1 + kTailMaxParticles) * sizeof(unsigned);
-    DPSX_HIP_TRY(hipMalloc((void **)&op->d_counters, bytes));
-    DPSX_HIP_TRY(hipMemset(op->d_counters, 0, bytes));
+    DPSX_HIP_TRY(hipMalloc((void **)&op->d_counters, kNormCounterBytes));
+    DPSX_HIP_TRY(hipMemset(op->d_counters, 0, kNormCounterBytes));
     return DPSX_OK;
 }
 
@@ -589,15 +588,13 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
     a.rng = rk;
     int parts = (int)parts_per_particle(op, c, h, w);
     // norm != NULL: the launch itself finishes the per-particle reduction (each particle's last block re-sums its
-    // partials in the order of k_finalize_norm -- bit-identical, no extra launch)
+    // partials in the order of k_finalize_norm -- bit-identical, no extra launch; common.h: NormTail)
     bool tail_done = false;
     if (norm && op->d_counters && n <= kTailMaxParticles && op->kind != OP_PHASE) {
         a.tail.counters = op->d_counters;
         a.tail.partials = ws.partials;
         a.tail.parts = op->kind == OP_IDENT ? 64 : parts;
-        a.tail.mode = TAIL_L2;
         a.tail.out = norm;
-        a.tail.n = (int)n;
         tail_done = true;
     }
     switch (op->kind) {
@@ -617,7 +614,8 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
         rc = posterior_fwd(x_t, model_out, noise, a.use_rng, rk, x0_hat, sample, inside, n, chw, k, s);
         if (rc != DPSX_OK) return rc;
         parts = 64;
-        rc = residual_partials(y, y_n, x0_hat, static_cast<float *>(resid), ws.partials, n, chw, parts, s, 0, a.tail);
+        rc = residual_partials(y, y_n, x0_hat, static_cast<float *>(resid), ws.partials, n, chw, parts, s, 0, nullptr, 0, 1,
+                               a.tail);
         break;
     case OP_PHASE:
         rc = phase_step_fwd(op, a, static_cast<float *>(resid), s);      // S1 + staging + R2C + residual / cotangent
@@ -628,7 +626,7 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
         // a launch that failed part-way may leave arrival counters non-zero: clear them behind whatever did run, so that
         // the handle's next in-launch reduction does not start from a stale count
         if (tail_done)
-            (void)hipMemsetAsync(op->d_counters, 0, (size_t)(1 + kTailMaxParticles) * sizeof(unsigned), s);
+            (void)hipMemsetAsync(op->d_counters, 0, kNormCounterBytes, s);
         return rc;
     }
     // norm == NULL: the partial sums stay in `workspace` and dpsx_step_bwd_f32 finalises them in its prologue
@@ -832,23 +830,21 @@ static int score_launch(dpsx_op *op, const Ws &ws, const float *x, const float *
                         int64_t n, int64_t c, int64_t h, int64_t w, hipStream_t s)
 {
     const int64_t chw = c * h * w;
-    const Tail tail{};                     // no in-launch tail
     int rc;
     switch (op->kind) {
     case OP_SEP:
-    case OP_TAPS: return blur_score(op, x, y, y_n, ws.partials, n, c, h, w, l1, tail, s);
-    case OP_RESIZE: return resize_score(op, x, y, y_n, ws.partials, n, c, l1, tail, s);
-    case OP_IDENT: return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, tail);
+    case OP_TAPS: return blur_score(op, x, y, y_n, ws.partials, n, c, h, w, l1, s);
+    case OP_RESIZE: return resize_score(op, x, y, y_n, ws.partials, n, c, l1, s);
+    case OP_IDENT: return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1);
     case OP_MASK:      // y - mask * x in the reduction itself (one launch, no scratch)
-        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, tail, op->mask, h * w,
-                                 op->mask_n);
+        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, op->mask, h * w, op->mask_n);
     case OP_PHASE: {
         // A x into scratch, then the generic residual reduction
         const int64_t m = meas_elems(op, c, h, w);
         float *ax = ws.meas;
         rc = phase_forward(op, x, ax, nullptr, n * c, ws.priv, ws.priv_bytes, s);
         if (rc != DPSX_OK) return rc;
-        return residual_partials(y, y_n, ax, nullptr, ws.partials, n, m, parts, s, l1, tail);
+        return residual_partials(y, y_n, ax, nullptr, ws.partials, n, m, parts, s, l1);
     }
     default: return DPSX_EUNSUPPORTED;
     }
@@ -860,15 +856,15 @@ static int score_parts(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
     return (int)parts_per_particle(op, c, h, w);
 }
 
-static Tail score_tail(const Ws &ws, int parts, int l1, const float *prev, int potential, float *raw_out, float *costs,
-                       int64_t *best_idx, float *best_val, int64_t n, int64_t chw)
+static CostArgs cost_args(const Ws &ws, int parts, int l1, const float *prev, int potential, float *raw_out, float *costs,
+                          int64_t *best_idx, float *best_val, int64_t n, int64_t chw)
 {
     // the reduction is finished by one small follow-up launch (finalize_select), not inside the scoring launch: see
     // the measurement at k_finalize_select
-    Tail fin{};
+    CostArgs fin{};
     fin.partials = ws.partials;
     fin.parts = parts;
-    fin.mode = l1 ? TAIL_L1SQ : TAIL_L2;
+    fin.mode = l1 ? COST_L1SQ : COST_L2;
     fin.l1_scale = (float)(1.0 / (double)chw);
     fin.prev = prev;
     fin.potential = potential;
@@ -893,7 +889,7 @@ static int score_impl(dpsx_op *op, const float *x, const float *y, int64_t y_n, 
     hipStream_t s = (hipStream_t)stream;
     const int parts = score_parts(op, c, h, w);
     if ((rc = score_launch(op, ws, x, y, y_n, l1, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    return finalize_select(score_tail(ws, parts, l1, prev, potential, raw_out, costs, best_idx, best_val, n, c * h * w), 1, s);
+    return finalize_select(cost_args(ws, parts, l1, prev, potential, raw_out, costs, best_idx, best_val, n, c * h * w), 1, s);
 }
 
 // ------------------------------------------------------------------ the search_ddpm step
@@ -958,16 +954,16 @@ static int search_step_impl(dpsx_op *op, const float *x_t, const float *model_ou
                        one_state, beam ? states : images);
     if (rc != DPSX_OK) return rc;
     if ((rc = score_launch(op, ws, sample, y, y_n, 0, parts, n, c, h, w, s)) != DPSX_OK) return rc;
-    const Tail tail = score_tail(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
+    const CostArgs fin = cost_args(ws, parts, 0, nullptr, POT_NONE, nullptr, costs, best_idx_dev, best_val_dev, n, chw);
     if (beam) {       // costs + the top-`beam` select per image: one launch; the winners' copies: one more (DESIGN.md "beam search")
-        rc = finalize_topb(tail, (int)images, (int)beam, s);
+        rc = finalize_topb(fin, (int)images, (int)beam, s);
         if (rc != DPSX_OK || !x_next) return rc;
         return gather_f32(sample, best_idx_dev, x_next, images * beam, n, chw, s);
     }
     static const bool unfused = getenv("DPSX_SEARCH_ONE_UNFUSED") != nullptr;       // A/B switch for tools/kbench_search.py
     if (one_state && !unfused && x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))
-        return finalize_select_copy(tail, (int)images, sample, x_next, chw, s);   // costs + select + the winners' copies: one launch
-    rc = finalize_select(tail, (int)images, s);
+        return finalize_select_copy(fin, (int)images, sample, x_next, chw, s);   // costs + select + the winners' copies: one launch
+    rc = finalize_select(fin, (int)images, s);
     if (rc != DPSX_OK || !x_next) return rc;
     if (one_state) return gather_f32(sample, best_idx_dev, x_next, images, n, chw, s);
     return replicate_seg_f32(sample, best_idx_dev, x_next, n, n / images, n, chw, s);

@@ -61,9 +61,10 @@ struct BlurArgs {
     // zero-extended loads (adjoint): the source plane is src_h x src_w and sits at (src_off, src_off)
     // inside the h x w domain the kernel tiles (src_off = 0 and src = domain for everything else)
     int src_h, src_w, src_off;
-    // scoring variants of the residual epilogue (plain input only): sums of |r| instead of r^2; in-launch finalisation
+    // scoring variant of the residual epilogue (plain input only): sums of |r| instead of r^2
     int l1;
-    Tail tail;
+    // the fused forward half (POST) finishes the per-particle norm inside the launch (common.h)
+    NormTail tail;
     // in-kernel noise draw of the fused S1 prologue (RNG instantiations; `noise` is then unused).  Last, so that every
     // other field keeps its kernel-argument offset
     RngK rng;
@@ -675,8 +676,8 @@ __global__ __launch_bounds__(NT, 4) void k_blur_taps(BlurArgs a, TapGeom g)
     }
     if constexpr (RESID) {
         const float t = block_sum(ss, s_red);
-        if (threadIdx.x == 0) tail_publish(&a.partials[(int64_t)plane * (a.tiles_x * a.tiles_y) + ty * a.tiles_x + tx], t, a.tail.counters != nullptr);
-        tail_arrive(a.tail, plane / a.c);
+        if (threadIdx.x == 0) tail_publish(&a.partials[(int64_t)plane * (a.tiles_x * a.tiles_y) + ty * a.tiles_x + tx], t, POST && a.tail.counters != nullptr);
+        if constexpr (POST) tail_arrive(a.tail, plane / a.c);
     }
 }
 
@@ -1601,7 +1602,7 @@ int blur_step_bwd(const dpsx_op *op, const StepBwdArgs &b, float *scratch, int64
 }
 
 int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials, int64_t n,
-               int64_t c, int64_t h, int64_t w, int l1, const Tail &tail, hipStream_t s)
+               int64_t c, int64_t h, int64_t w, int l1, hipStream_t s)
 {
     if (!geometry_ok(op, h, w)) return DPSX_EINVAL;
     if (n == 0) return DPSX_OK;
@@ -1609,8 +1610,6 @@ int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, f
     a.x = x; a.y = y; a.y_div = row_div(y_n, n); a.out = nullptr; a.partials = partials;
     fill_geometry(a, n * c, c, h, w);
     a.l1 = l1;
-    a.tail = tail;
-    a.tail.blocks_per_particle = a.c * a.tiles_x * a.tiles_y;
     const bool vec = vec_ok(h, w, {x, y});
     return op->kind == OP_SEP && vec ? dispatch_sep_fwd<false, true>(op, a, s) : launch_taps_fwd<false, true>(op, a, vec, s);
 }

@@ -9,8 +9,8 @@
 //
 // Reductions: grid (slots, n); block (q, p) owns a contiguous range of particle p and leaves ONE fp32 partial (the
 // fixed tree of block_sum) in slot q.  The slot count depends on the particle size only (cg_slots), so a particle's
-// sums do not depend on the batch it runs in.  The consumer launch's prologue adds a particle's slots in double, in
-// the order of particle_norm_to_lds (lane-strided, fixed shuffle tree); every block of a particle gets the same bits.
+// sums do not depend on the batch it runs in.  The consumer launch's prologue adds a particle's slots in double with
+// common.h's slots_sum (lane-strided, fixed shuffle tree); every block of a particle gets the same bits.
 // No atomics, no fences: launch boundaries order the partials.  Everything a particle reads is its own, so a
 // non-finite value stays inside its particle.
 //
@@ -50,23 +50,13 @@ template <class T> __device__ __forceinline__ T cg_ld_last(const float *p)
 }
 template <class T> __device__ __forceinline__ void cg_st(float *p, T v) { *reinterpret_cast<T *>(p) = v; }
 
-// one particle's slots added in double: lane-strided sums, fixed shuffle tree (wave 0; valid in lane 0)
-__device__ __forceinline__ double cg_slots_sum(const float *part, int cnt)
-{
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < cnt; i += kWave) acc += (double)part[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-    return acc;
-}
-
 // alpha = rs / (||t||^2 + rho ||p||^2), formed in double, rounded once.  out[0] = alpha, out[1] = rs, out[2] = pq;
 // called by all threads, valid after the next __syncthreads()
 __device__ __forceinline__ void cg_alpha_to_lds(const float *rs, const float *tt, const float *pp, int slots, int slots_m,
                                                 float rho, float *out)
 {
     if (threadIdx.x < kWave) {
-        const double a = cg_slots_sum(rs, slots), b = cg_slots_sum(tt, slots_m), c = cg_slots_sum(pp, slots);
+        const double a = slots_sum(rs, slots), b = slots_sum(tt, slots_m), c = slots_sum(pp, slots);
         if (threadIdx.x == 0) {
             const double pq = b + (double)rho * c;
             out[0] = (float)(pq > 0.0 ? a / pq : 0.0);
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(kCgThreads) void k_cg_pupdate(const float *__restri
         pv = cg_ld<T>(p + base + u * W);
     }
     if (threadIdx.x < kWave) {
-        const double a = cg_slots_sum(rs_old + q * slots, slots), b = cg_slots_sum(rs_new + q * slots, slots);
+        const double a = slots_sum(rs_old + q * slots, slots), b = slots_sum(rs_new + q * slots, slots);
         if (threadIdx.x == 0) sc[0] = (float)(a > 0.0 ? b / a : 0.0);
     }
     __syncthreads();

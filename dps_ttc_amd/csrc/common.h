@@ -216,24 +216,46 @@ __device__ __forceinline__ float block_sum(float v, float *scratch)
     return t;
 }
 
-// Per-particle norm from the per-block partial sums of squares the forward half left behind.  Same
-// order as k_finalize_norm (lane-strided sums, fixed shuffle tree, double), so every block of a particle
-// -- and the stand-alone finalisation -- get the bit-identical value.  Called by all threads; the result is
+// The shuffle tree that ends every fixed-order sum: 32 ... 1, result valid in lane 0.  In place, by reference: returning
+// the sum by value compiled the backward blur kernels to other register counts.
+__device__ __forceinline__ void wave_sum_f64(double &v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+}
+
+// THE fixed-order sum of one particle's partial slots, in double: lane i adds slots i, i + 64, ... in index order, then
+// wave_sum_f64.  The one definition: every finisher of a per-particle sum -- k_finalize_norm, the backward prologues, the
+// in-launch norm, the cost finalisation, the CG scalars -- goes through it or, where the loads are unrolled by hand, adds
+// in this order and ends in wave_sum_f64, so they all produce the same bits.
+// Called by wave 0 (threadIdx.x < kWave); the result is valid in lane 0.  ld: how a slot is read (plain by default).
+template <class Ld>
+__device__ __forceinline__ double slots_sum(const float *slots, int cnt, Ld &&ld)
+{
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < cnt; i += kWave) acc += (double)ld(slots + i);
+    wave_sum_f64(acc);
+    return acc;
+}
+__device__ __forceinline__ double slots_sum(const float *slots, int cnt)
+{
+    return slots_sum(slots, cnt, [](const float *p) { return *p; });
+}
+
+// Per-particle norm from the per-block partial sums of squares the forward half left behind (slots_sum: every block of a
+// particle -- and the stand-alone finalisation -- get the bit-identical value).  Called by all threads; the result is
 // valid in *slot after the next __syncthreads().
 __device__ __forceinline__ void particle_norm_to_lds(const float *partials, int parts, int64_t n, float *slot)
 {
     if (threadIdx.x < kWave) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < parts; i += kWave) acc += (double)partials[n * parts + i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+        const double acc = slots_sum(partials + n * parts, parts);
         if (threadIdx.x == 0) *slot = (float)sqrt(acc);
     }
 }
 
 // The same value in two halves, so the partial loads fly together with the caller's tile loads instead of
 // costing a memory round trip at the top of every block: *_issue starts them (wave 0, <= 4 per lane, fixed
-// slots), *_reduce adds them in the order of the loop above (adding the +0.0 of an absent slot is exact).
+// slots), *_reduce adds them in the order of slots_sum (adding the +0.0 of an absent slot is exact).
 // Only for parts <= 4 * kWave (block-uniform test by the caller).
 struct NormPartials { float v[4]; };
 __device__ __forceinline__ NormPartials particle_norm_issue(const float *partials, int parts, int64_t n)
@@ -251,8 +273,7 @@ __device__ __forceinline__ void particle_norm_reduce(const NormPartials &p, int 
         double acc = 0.0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc += (int)threadIdx.x + j * kWave < parts ? (double)p.v[j] : 0.0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+        wave_sum_f64(acc);
         if (threadIdx.x == 0) *slot = (float)sqrt(acc);
     }
 }
@@ -275,24 +296,18 @@ __device__ __forceinline__ bool argmin_better(const ArgMin &a, const ArgMin &b) 
     return a.v < b.v || (a.v == b.v && a.i < b.i);
 }
 
-// -------------------------------------------------------------------- "last block done" tail
-// A launch whose blocks each leave one partial sum per (particle, slot) can finish the per-particle reduction
-// itself: every partial-writing block arrives at its particle's counter; the last one re-sums ALL of that particle's
-// partials in the fixed order of k_finalize_norm (so the value is bit-identical to the stand-alone finalisation and
-// independent of which block came last) and writes the per-particle value; optionally the last particle to finish
-// runs the argmin over all values.  Nothing waits on anything: a block that is not last just leaves.  Counters are
-// zero between launches (the last arriver resets its counter; the host wrapper clears them if a launch fails).  One launch
-// at a time per counter array (= per dpsx_op): an operator handle serves ONE stream at a time, as its workspace does.
-enum { TAIL_L2 = 0,      // value = sqrt(sum of squares)                      ||y - A x||_2
-       TAIL_L1SQ = 1 };  // value = (sum of |.|)^2 * l1_scale                 ||y - A x||_1^2 / (C H W)
+// -------------------------------------------------------------------- the cost finalisation's arguments
+// What the small finalisation launches (k_finalize_select, k_finalize_select_copy, k_finalize_topb) take: where a
+// scoring launch left its partial sums, how a particle's sum becomes its cost, and where costs and select go.  Built by
+// api.hip: cost_args(); the scoring launches themselves only leave partial sums.
+enum { COST_L2 = 0,      // value = sqrt(sum of squares)                      ||y - A x||_2
+       COST_L1SQ = 1 };  // value = (sum of |.|)^2 * l1_scale                 ||y - A x||_1^2 / (C H W)
 enum { POT_NONE = 0, POT_MEAN = 1, POT_MIN = 2, POT_DIFF = 3, POT_CURR = 4 };   // SearchDDPM.resample_update :565-585
 
-struct Tail {
-    unsigned *counters = nullptr;   // [1 + n]: [0] particles finished, [1 + p] blocks of particle p arrived; null: no tail
-    int blocks_per_particle = 0;
+struct CostArgs {
     const float *partials = nullptr;
     int parts = 0;
-    int mode = TAIL_L2;
+    int mode = COST_L2;
     float l1_scale = 0.0f;
     const float *prev = nullptr;    // [n] previous costs (nullable) and how to combine them with the new value
     int potential = POT_NONE;
@@ -303,7 +318,28 @@ struct Tail {
     int n = 0;
 };
 
-constexpr int kTailMaxParticles = 1 << 16;    // counters allocated per operator handle
+// -------------------------------------------------------------------- the in-launch norm ("last block done")
+// dpsx_step_fwd_f32(norm != NULL) finishes the per-particle norm inside its forward launch -- the only user of this
+// route: every block that wrote a partial sum of a particle arrives at that particle's counter; the last one re-sums ALL
+// of the particle's partials with slots_sum (so the value is bit-identical to k_finalize_norm's and independent of which
+// block came last) and writes the norm.  Nothing waits on anything: a block that is not last just leaves.  Counters are
+// zero between launches (the last arriver resets its counter; the host wrapper clears them if a launch fails).  One launch
+// at a time per counter array (= per dpsx_op): an operator handle serves ONE stream at a time, as its workspace does.
+// NormTail travels by value in the argument block of the forward kernels (resize.hip converts it into the older record its
+// fused forward kernels were left with: see LegacyTail there); the scoring instantiations of the blur and resize kernels
+// (POST == false) do not contain the route at all.  (The field order is chosen by compiling both: with the
+// pointers first an RNG instantiation of k_blur_sep_fwd took more scratch memory -- profiles/tail_split_kernel_stats.txt.)
+struct NormTail {
+    unsigned *counters = nullptr;   // [kTailMaxParticles]: blocks of particle p arrived; null: no in-launch norm
+    int blocks_per_particle = 0;
+    const float *partials = nullptr;
+    int parts = 0;
+    float *out = nullptr;           // [n] the norms
+};
+
+constexpr int kTailMaxParticles = 1 << 16;    // counters allocated per operator handle: one per particle
+constexpr size_t kNormCounterBytes = (size_t)kTailMaxParticles * sizeof(unsigned);
+__device__ __forceinline__ unsigned *norm_counter(const NormTail &t, int particle) { return t.counters + particle; }
 
 // Visibility across the 8 XCDs (one L2 each) WITHOUT a device-scope release fence: on gfx950 that fence is a write-back
 // of the whole L2 (`buffer_wbl2`), and with megabytes of freshly written x0_hat / sample lines dirty in it, one fence per
@@ -335,82 +371,25 @@ __device__ __forceinline__ void tail_drain_stores()
 }
 
 // Called by ALL threads of every block that wrote a partial of `particle`, after the write (block-uniform call site).
-__device__ __forceinline__ void tail_arrive(const Tail &t, int particle)
+__device__ __forceinline__ void tail_arrive(const NormTail &t, int particle)
 {
     if (!t.counters) return;                                    // launch-uniform
-    __shared__ __attribute__((aligned(16))) int s_tail[52];     // flag + 16 x (value, index lo, index hi); 16-byte multiple (G17)
-    int *s_flag = s_tail;
+    __shared__ __attribute__((aligned(16))) int s_last[4];      // one flag, padded: dynamic LDS behind it stays 16-byte aligned
     if (threadIdx.x == 0) {                                     // the thread that published the partial
         tail_drain_stores();                                    // ... whose write-through store has completed
-        const unsigned prev = __hip_atomic_fetch_add(&t.counters[1 + particle], 1u, __ATOMIC_RELAXED,
+        const unsigned prev = __hip_atomic_fetch_add(norm_counter(t, particle), 1u, __ATOMIC_RELAXED,
                                                      __HIP_MEMORY_SCOPE_AGENT);
         const int last = prev == (unsigned)t.blocks_per_particle - 1u;
-        if (last) __hip_atomic_store(&t.counters[1 + particle], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *s_flag = last;
+        if (last) __hip_atomic_store(norm_counter(t, particle), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last[0] = last;
     }
     __syncthreads();
-    if (!*s_flag) return;                                       // block-uniform
+    if (!s_last[0]) return;                                     // block-uniform
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // invalidate, no write-back; N blocks per launch
     if (threadIdx.x < kWave) {
-        double acc = 0.0;
-        const float *pp = t.partials + (int64_t)particle * t.parts;
-        for (int i = threadIdx.x; i < t.parts; i += kWave) acc += (double)tail_ld(pp + i);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-        if (threadIdx.x == 0) {
-            float v = t.mode == TAIL_L1SQ ? (float)(acc * acc * (double)t.l1_scale) : (float)sqrt(acc);
-            if (t.raw_out) t.raw_out[particle] = v;
-            if (t.prev) {
-                const float q = t.prev[particle];
-                if (t.potential == POT_MEAN) v = v + q;
-                else if (t.potential == POT_MIN) v = (v != v || q != q) ? __builtin_nanf("") : fminf(v, q);   // torch.min propagates NaN
-                else if (t.potential == POT_DIFF) v = v - q;
-            }
-            __hip_atomic_store(t.out + particle, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (!t.best_idx) return;                                    // launch-uniform
-    __syncthreads();
-    if (threadIdx.x == 0) {                                     // the thread that stored out[particle]
-        tail_drain_stores();
-        const unsigned prev = __hip_atomic_fetch_add(&t.counters[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = prev == (unsigned)t.n - 1u;
-        if (last) __hip_atomic_store(&t.counters[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *s_flag = last;
-    }
-    __syncthreads();
-    if (!*s_flag) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // argmin over out[0..n): per-lane scan, wave shuffles, then thread 0 over the waves' winners (one LDS hop)
-    ArgMin best{0.0f, -1};
-    for (int64_t i = threadIdx.x; i < t.n; i += blockDim.x) {
-        const ArgMin c{tail_ld(t.out + i), i};
-        if (argmin_better(c, best)) best = c;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        ArgMin c;
-        c.v = __shfl_down(best.v, o, kWave);
-        c.i = __shfl_down(best.i, o, kWave);
-        if (argmin_better(c, best)) best = c;
-    }
-    float *s_v = reinterpret_cast<float *>(s_flag + 1);
-    int *s_lo = s_flag + 17, *s_hi = s_flag + 33;
-    const int wave = threadIdx.x / kWave, nw = (blockDim.x + kWave - 1) / kWave;
-    __syncthreads();
-    if (threadIdx.x % kWave == 0) {
-        s_v[wave] = best.v;
-        s_lo[wave] = (int)(best.i & 0xffffffff);
-        s_hi[wave] = (int)(best.i >> 32);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < nw; ++w) {
-            const ArgMin c{s_v[w], ((int64_t)s_hi[w] << 32) | (uint32_t)s_lo[w]};
-            if (argmin_better(c, best)) best = c;
-        }
-        *t.best_idx = best.i < 0 ? 0 : best.i;
-        if (t.best_val) *t.best_val = best.v;
+        const double acc = slots_sum(t.partials + (int64_t)particle * t.parts, t.parts, tail_ld);
+        if (threadIdx.x == 0)
+            __hip_atomic_store(t.out + particle, (float)sqrt(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -479,7 +458,7 @@ struct dpsx_op {
     // ---- mask: [mask_n, h, w], particle p of n uses mask p / (n / mask_n)
     const float *mask = nullptr;
     int64_t mask_n = 1;
-    // ---- "last block done" arrival counters (see Tail): [1 + kTailMaxParticles], zero between launches
+    // ---- "last block done" arrival counters (see NormTail): kNormCounterBytes, zero between launches
     unsigned *d_counters = nullptr;
     // ---- phase
     int64_t pr_h = 0, pr_pad = 0, pr_planes = 0;
@@ -499,7 +478,7 @@ struct StepFwdArgs {
     float *partials;  // [n * parts_per_particle] sums of squares, finalized into norm by the caller
     int64_t n, c, h, w;
     Coefs k;
-    Tail tail{};      // per-particle finalisation inside the launch (tail.counters == nullptr: not requested / not supported)
+    NormTail tail{};  // the norm finished inside the launch (tail.counters == nullptr: not requested / not supported)
     unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
     bool use_rng = false;               // draw the noise in the kernel from `rng` (noise is then null)
     RngK rng{};
@@ -530,9 +509,9 @@ int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h,
 int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &a, hipStream_t s);
 bool blur_step_draws_in_kernel(const dpsx_op *op, int64_t h, int64_t w);   // blur_step_fwd takes StepFwdArgs::use_rng
 int blur_step_bwd(const dpsx_op *op, const StepBwdArgs &a, float *scratch, int64_t scratch_bytes, hipStream_t s);
-// l1: partials are sums of |r| instead of r^2;  tail: finish the reduction inside the launch (see Tail)
+// l1: partials are sums of |r| instead of r^2
 int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials,
-               int64_t n, int64_t c, int64_t h, int64_t w, int l1, const Tail &tail, hipStream_t s);
+               int64_t n, int64_t c, int64_t h, int64_t w, int l1, hipStream_t s);
 int64_t blur_parts_per_particle(const dpsx_op *op, int64_t c, int64_t h, int64_t w);
 
 
@@ -546,7 +525,7 @@ int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &a, hipStream_t s);
 bool resize_step_draws_in_kernel(const dpsx_op *op);                        // resize_step_fwd takes StepFwdArgs::use_rng
 int resize_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s);
 int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials,
-                 int64_t n, int64_t c, int l1, const Tail &tail, hipStream_t s);
+                 int64_t n, int64_t c, int l1, hipStream_t s);
 
 // elementwise.hip
 // one_state: x [states, chw] and mo [states, 2 chw] feed all n particles, n / states consecutive particles per state
@@ -563,21 +542,22 @@ int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const flo
 // mask [mask_n, hw]: plane q (of n * c) uses mask meas_row(q / c, mask_div), mask_div = row_div(mask_n, n)
 int mask_mul(const float *x, const float *mask, float *y, int64_t planes, int64_t hw, hipStream_t s, int64_t c = 1,
              unsigned mask_div = 0);
-// sums of squares of (y - ax) per particle in `parts` chunks -> partials[n*parts]; r optional
+// sums of squares of (y - ax) per particle in `parts` chunks -> partials[n*parts]; r optional.  tail: the identity
+// operator's fused forward step finishes the norm inside the launch (see NormTail); scoring passes none
 int residual_partials(const float *y, int64_t y_n, const float *ax, float *r, float *partials,
-                      int64_t n, int64_t m, int parts, hipStream_t s, int l1 = 0, const Tail &tail = Tail{},
-                      const float *mask = nullptr, int64_t hw = 0, int64_t mask_n = 1);
+                      int64_t n, int64_t m, int parts, hipStream_t s, int l1 = 0, const float *mask = nullptr,
+                      int64_t hw = 0, int64_t mask_n = 1, const NormTail &tail = NormTail{});
 int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipStream_t s);
 // one small launch: per-particle values from the partials (t.partials / parts / mode / prev / potential -> raw_out, out)
-// and, if t.best_idx, the torch.argmin-order select over them (t.counters is not used).  The select runs per segment:
+// and, if t.best_idx, the torch.argmin-order select over them.  The select runs per segment:
 // `segments` consecutive groups of t.n / segments particles (1: the whole set); t.best_idx / t.best_val are [segments]
 // and receive each segment's winner as a global particle index.  _copy: dst[m] = src[best[m]] (chw % 4 == 0, aligned)
-int finalize_select(const Tail &t, int segments, hipStream_t s);
-int finalize_select_copy(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
+int finalize_select(const CostArgs &t, int segments, hipStream_t s);
+int finalize_select_copy(const CostArgs &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s);
 // costs + the first b particles of every segment (of t.n / segments <= kTopbMaxK particles) under the select's order:
 // t.best_idx / t.best_val (nullable) are [segments, b]
 constexpr int kTopbMaxK = 4096;          // a segment's keys and costs live in 12 k bytes of LDS (48 KB at the cap)
-int finalize_topb(const Tail &t, int segments, int b, hipStream_t s);
+int finalize_topb(const CostArgs &t, int segments, int b, hipStream_t s);
 // segmented argmin over v [segments, k] -> idx[m] = m * k + argmin (torch.argmin order), val[m] (nullable)
 int argmin_seg_f32(const float *v, int64_t segments, int64_t k, int64_t *idx, float *val, hipStream_t s);
 int topk_seg_f32(const float *v, int64_t segments, int64_t k, int64_t b, int64_t *idx, float *val, hipStream_t s);

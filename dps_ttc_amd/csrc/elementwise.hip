@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void k_residual_partials(const float *__r
                                                                 const float *__restrict__ ax,
                                                                 float *__restrict__ r,
                                                                 float *__restrict__ partials, int64_t m,
-                                                                int64_t chunk, int l1, Tail tail,
+                                                                int64_t chunk, int l1, NormTail tail,
                                                                 const float *__restrict__ mask, int hw, unsigned mask_div)
 {
     __shared__ float scratch[kThreads / kWave];
@@ -263,28 +263,25 @@ __global__ __launch_bounds__(kThreads) void k_residual_partials(const float *__r
 }
 
 int residual_partials(const float *y, int64_t y_n, const float *ax, float *r, float *partials, int64_t n,
-                      int64_t m, int parts, hipStream_t s, int l1, const Tail &tail, const float *mask, int64_t hw,
-                      int64_t mask_n)
+                      int64_t m, int parts, hipStream_t s, int l1, const float *mask, int64_t hw, int64_t mask_n,
+                      const NormTail &tail)
 {
     if (n == 0) return DPSX_OK;
     if (mask && (hw < 1 || hw > (1 << 30))) return DPSX_EINVAL;
     const int64_t chunk = (m + parts - 1) / parts;
-    Tail t = tail;
+    NormTail t = tail;
     t.blocks_per_particle = parts;
     k_residual_partials<<<dim3(parts, (unsigned)n), kThreads, 0, s>>>(y, row_div(y_n, n), ax, r, partials, m, chunk, l1, t,
                                                                      mask, (int)hw, row_div(mask_n, n));
     return check_launch();
 }
 
-// one wave per particle; partial sums added in index order within a lane, then a fixed tree
+// one wave per particle: common.h's slots_sum
 __global__ __launch_bounds__(kWave) void k_finalize_norm(const float *__restrict__ partials, int parts,
                                                          float *__restrict__ norm)
 {
     const int64_t p = blockIdx.x;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < parts; i += kWave) acc += (double)partials[p * parts + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+    const double acc = slots_sum(partials + p * parts, parts);
     if (threadIdx.x == 0) norm[p] = (float)sqrt(acc);
 }
 
@@ -298,17 +295,19 @@ int finalize_norm(const float *partials, int parts, float *norm, int64_t n, hipS
 // Finalisation + select in ONE small launch (replaces k_finalize_norm + k_argmin after a scoring launch, and does the
 // cost combine of SearchDDPM.resample_update): wave w finishes particles w, w + nw, ... in the order of k_finalize_norm
 // (bit-identical values), then the block runs the torch.argmin-order select over them.
-// Measured alternative (r02): finishing inside the scoring launch ("last block done", common.h: Tail) costs every short
-// scoring block two dependent memory round trips while it holds its LDS -- 42 us instead of ~25 us at N = 64.
+// Measured and removed (r02): finishing inside the scoring launch (a "last block done" arrival, as common.h's NormTail
+// still does for the fused forward step's norm) cost every short scoring block two dependent memory round trips while it
+// held its LDS -- 42 us instead of ~25 us at N = 64.  The scoring launches leave partial sums only.
 constexpr int kSelThreads = 1024;
 // the cost-finishing loop of the finalisation launches (k_finalize_select*, k_finalize_topb): one copy, so a particle's
 // cost is the same bits whichever of them finishes it.  `writer`: this block stores the costs.  [lo, hi): the particles this
 // block finishes.  each(v, p): called by lane 0 of the wave that finished particle p, with its (combined) cost.
 template <class Each>
-__device__ __forceinline__ void finalize_costs(const Tail &t, const bool writer, const int lo, const int hi, Each &&each)
+__device__ __forceinline__ void finalize_costs(const CostArgs &t, const bool writer, const int lo, const int hi, Each &&each)
 {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nw = kSelThreads / kWave;
-    constexpr int B = 4;          // particles per wave in flight: their partial loads are issued together (one latency)
+    constexpr int B = 4;          // particles per wave in flight: their partial loads are issued together (one latency);
+                                  // each particle's adds are in the order of common.h's slots_sum
     for (int p0 = lo + wave; p0 < hi; p0 += nw * B) {
         double acc[B];
 #pragma unroll
@@ -328,9 +327,8 @@ __device__ __forceinline__ void finalize_costs(const Tail &t, const bool writer,
             const int p = p0 + b * nw;
             if (p >= hi) break;                                       // wave-uniform
             double a = acc[b];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, kWave);
-            float v = t.mode == TAIL_L1SQ ? (float)(a * a * (double)t.l1_scale) : (float)sqrt(a);
+            wave_sum_f64(a);
+            float v = t.mode == COST_L1SQ ? (float)(a * a * (double)t.l1_scale) : (float)sqrt(a);
             if (lane == 0) {
                 if (t.raw_out && writer) t.raw_out[p] = v;
                 if (t.prev) {
@@ -352,7 +350,7 @@ __device__ __forceinline__ void finalize_costs(const Tail &t, const bool writer,
 // [lo, hi): the particles this block finishes and selects over (a segment of a multi-image batch; 0, t.n otherwise) -- each
 // particle's value comes out of the same loads and adds whatever the range, so segmented and whole launches agree bit for
 // bit; the winner (a global particle index) goes to best_idx[slot] / best_val[slot].
-__device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const bool writer, const int lo, const int hi,
+__device__ __forceinline__ int64_t finalize_select_body(const CostArgs &t, const bool writer, const int lo, const int hi,
                                                         const int slot)
 {
     __shared__ float s_v[kSelThreads / kWave];
@@ -383,7 +381,7 @@ __device__ __forceinline__ int64_t finalize_select_body(const Tail &t, const boo
 }
 
 // block m finishes and selects over the particles [m k, (m + 1) k) of segment m (one block and k = t.n: the whole set)
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t, int k)
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select(CostArgs t, int k)
 {
     const int m = blockIdx.x;
     (void)finalize_select_body(t, true, m * k, (m + 1) * k, m);
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(kSelThreads) void k_finalize_select(Tail t, int k)
 // the same + ONE copy of each segment's winner (the single-state search step): block (x, m) finishes segment m's costs
 // and select for itself (k * parts floats from the L2 -- 12 KB at N = 64) and copies slice x of its winner to dst[m];
 // one launch and one launch boundary less than finalisation + dpsx_replicate_f32(n_out = 1)
-__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(Tail t, int k, const float *__restrict__ src,
+__global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(CostArgs t, int k, const float *__restrict__ src,
                                                                       float *__restrict__ dst, int64_t chw4)
 {
     const int m = blockIdx.y;
@@ -402,14 +400,14 @@ __global__ __launch_bounds__(kSelThreads) void k_finalize_select_copy(Tail t, in
         (reinterpret_cast<float4 *>(dst) + (int64_t)m * chw4)[i] = (reinterpret_cast<const float4 *>(src) + b * chw4)[i];
 }
 
-int finalize_select(const Tail &t, int segments, hipStream_t s)
+int finalize_select(const CostArgs &t, int segments, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
     k_finalize_select<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments);
     return check_launch();
 }
 
-int finalize_select_copy(const Tail &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s)
+int finalize_select_copy(const CostArgs &t, int segments, const float *src, float *dst, int64_t chw, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
     const int64_t chw4 = chw / 4;
@@ -534,7 +532,7 @@ __device__ __forceinline__ void topb_select_store(TopbLds &l, const int k, const
 
 // block m finishes the costs of segment m ([m k, (m + 1) k), k <= kTopbMaxK) exactly as k_finalize_select does and stores
 // its first b particles: best_idx[m b + r] (global index) / best_val[m b + r] for rank r
-__global__ __launch_bounds__(kSelThreads) void k_finalize_topb(Tail t, int k, int b)
+__global__ __launch_bounds__(kSelThreads) void k_finalize_topb(CostArgs t, int k, int b)
 {
     __shared__ __attribute__((aligned(16))) TopbLds l;
     const int m = blockIdx.x, lo = m * k;
@@ -552,7 +550,7 @@ __global__ __launch_bounds__(kSelThreads) void k_topk_seg(const float *__restric
     topb_select_store(l, k, b, lo, idx + m * b, val ? val + m * b : nullptr);
 }
 
-int finalize_topb(const Tail &t, int segments, int b, hipStream_t s)
+int finalize_topb(const CostArgs &t, int segments, int b, hipStream_t s)
 {
     if (t.n == 0) return DPSX_OK;
     k_finalize_topb<<<(unsigned)segments, kSelThreads, 0, s>>>(t, t.n / segments, b);

@@ -59,6 +59,115 @@ struct ResizeDev {
     const int *blk_lo2, *blk_cnt2, *own_lo2;
 };
 
+// -------------------------------------------------------------------- the fused forward kernels' in-launch norm
+// LEFT OUT of the split of common.h's Tail record into NormTail + CostArgs: these kernels keep the old 13-field record and
+// its whole arrival routine, of which only the first stage can run (the launch sets counters, blocks_per_particle,
+// partials, parts, out and n: best_idx stays null, so the combine and the second stage -- which would take counters[0],
+// now particle 0's counter, for its own -- are never entered).  Reason, measured on MI355X in one session against the
+// parent (profiles/tail_split_ab.txt, "four libraries"; x4 at 256 x 256, us): with NormTail / tail_arrive the fused
+// forward launch read 24.93 at N = 16 (parent 23.90, this form 23.90) and 59.90 with the in-kernel draw at N = 64 (parent
+// 58.30, this form 58.00); with this routine cut down to its first stage 25.30 and 60.20.  Compiled, the lean forms have
+// the parent's VGPRs and more SGPR spills (k_resize_fwd_rows<true,true,16,4,false> 17 -> 29 / 37), and neither the
+// record's position or size in ResizeArgs, nor the static LDS, nor the shape of the re-sum changed that
+// (profiles/tail_split_kernel_stats.txt); this form compiles to the parent's figures in every column.  The scoring
+// instantiations (POST == false) do not contain the route.  The protocol is common.h's (tail_publish / tail_drain_stores /
+// tail_ld).  Open: an arrival routine that is lean AND leaves the tile code's register allocation alone.
+struct LegacyTail {
+    unsigned *counters = nullptr;   // NormTail::counters ([p] blocks of particle p arrived); null: no in-launch norm
+    int blocks_per_particle = 0;
+    const float *partials = nullptr;
+    int parts = 0;
+    int mode = COST_L2;
+    float l1_scale = 0.0f;
+    const float *prev = nullptr;    // [n] previous costs (nullable) and how to combine them with the new value
+    int potential = POT_NONE;
+    float *raw_out = nullptr;       // [n] the uncombined value (nullable)
+    float *out = nullptr;           // [n]
+    int64_t *best_idx = nullptr;    // argmin over out[0..n) (nullable)
+    float *best_val = nullptr;      // out[argmin] (nullable)
+    int n = 0;
+};
+
+// Called by ALL threads of every block that wrote a partial of `particle`, after the write (block-uniform call site).
+__device__ __forceinline__ void legacy_tail_arrive(const LegacyTail &t, int particle)
+{
+    if (!t.counters) return;                                    // launch-uniform
+    __shared__ __attribute__((aligned(16))) int s_tail[52];     // flag + 16 x (value, index lo, index hi); 16-byte multiple (G17)
+    int *s_flag = s_tail;
+    if (threadIdx.x == 0) {                                     // the thread that published the partial
+        tail_drain_stores();                                    // ... whose write-through store has completed
+        const unsigned prev = __hip_atomic_fetch_add(&t.counters[particle], 1u, __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT);
+        const int last = prev == (unsigned)t.blocks_per_particle - 1u;
+        if (last) __hip_atomic_store(&t.counters[particle], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_flag = last;
+    }
+    __syncthreads();
+    if (!*s_flag) return;                                       // block-uniform
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // invalidate, no write-back; N blocks per launch
+    if (threadIdx.x < kWave) {
+        double acc = 0.0;
+        const float *pp = t.partials + (int64_t)particle * t.parts;
+        for (int i = threadIdx.x; i < t.parts; i += kWave) acc += (double)tail_ld(pp + i);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+        if (threadIdx.x == 0) {
+            float v = t.mode == COST_L1SQ ? (float)(acc * acc * (double)t.l1_scale) : (float)sqrt(acc);
+            if (t.raw_out) t.raw_out[particle] = v;
+            if (t.prev) {
+                const float q = t.prev[particle];
+                if (t.potential == POT_MEAN) v = v + q;
+                else if (t.potential == POT_MIN) v = (v != v || q != q) ? __builtin_nanf("") : fminf(v, q);   // torch.min propagates NaN
+                else if (t.potential == POT_DIFF) v = v - q;
+            }
+            __hip_atomic_store(t.out + particle, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (!t.best_idx) return;                                    // launch-uniform
+    __syncthreads();
+    if (threadIdx.x == 0) {                                     // the thread that stored out[particle]
+        tail_drain_stores();
+        const unsigned prev = __hip_atomic_fetch_add(&t.counters[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = prev == (unsigned)t.n - 1u;
+        if (last) __hip_atomic_store(&t.counters[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_flag = last;
+    }
+    __syncthreads();
+    if (!*s_flag) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // argmin over out[0..n): per-lane scan, wave shuffles, then thread 0 over the waves' winners (one LDS hop)
+    ArgMin best{0.0f, -1};
+    for (int64_t i = threadIdx.x; i < t.n; i += blockDim.x) {
+        const ArgMin c{tail_ld(t.out + i), i};
+        if (argmin_better(c, best)) best = c;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        ArgMin c;
+        c.v = __shfl_down(best.v, o, kWave);
+        c.i = __shfl_down(best.i, o, kWave);
+        if (argmin_better(c, best)) best = c;
+    }
+    float *s_v = reinterpret_cast<float *>(s_flag + 1);
+    int *s_lo = s_flag + 17, *s_hi = s_flag + 33;
+    const int wave = threadIdx.x / kWave, nw = (blockDim.x + kWave - 1) / kWave;
+    __syncthreads();
+    if (threadIdx.x % kWave == 0) {
+        s_v[wave] = best.v;
+        s_lo[wave] = (int)(best.i & 0xffffffff);
+        s_hi[wave] = (int)(best.i >> 32);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < nw; ++w) {
+            const ArgMin c{s_v[w], ((int64_t)s_hi[w] << 32) | (uint32_t)s_lo[w]};
+            if (argmin_better(c, best)) best = c;
+        }
+        *t.best_idx = best.i < 0 ? 0 : best.i;
+        if (t.best_val) *t.best_val = best.v;
+    }
+}
+
 struct ResizeArgs {
     const float *x;           // plain input [planes, in_h, in_w] / adjoint input u [planes, out_h, out_w]
     float *out;               // fwd: A x or residual (nullable when RESID); adj: g
@@ -79,7 +188,7 @@ struct ResizeArgs {
     int c, planes;
     Coefs k;
     int l1;                   // scoring (plain input): partials are sums of |r|
-    Tail tail;                // in-launch finalisation of the per-particle reduction (common.h)
+    LegacyTail tail;          // the fused forward half (POST) finishes the per-particle norm in the launch (see above)
     RngK rng;                 // in-kernel noise draw of the fused S1 (RNG instantiation; `noise` is then unused).  Last, so
                               // that every other field keeps its kernel-argument offset
 };
@@ -115,7 +224,7 @@ __device__ __forceinline__ void block_sum4(float (&v)[4], float *scratch)
 // The H pass of one block and its partial sums.  gparts == 1: one partial per block (every trip of the loop accumulates
 // into one value per thread).  gparts > 1 (the block covers exactly gparts * RT outputs): trip j keeps its own value --
 // partial j of the block is what a block of the fine blocking, whose only trip it is, publishes as its one partial.
-template <bool RESID, typename F>
+template <bool POST, bool RESID, typename F>
 __device__ __forceinline__ void resize_h_pass(const ResizeArgs &a, const ResizeDev &d, F &h_out, int total, int plane,
                                               int nblk, int blk, float *s_red)
 {
@@ -130,9 +239,9 @@ __device__ __forceinline__ void resize_h_pass(const ResizeArgs &a, const ResizeD
                 float *dst = &a.partials[((int64_t)plane * nblk + blk) * d.gparts];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (j < d.gparts) tail_publish(dst + j, sg[j], a.tail.counters != nullptr);
+                    if (j < d.gparts) tail_publish(dst + j, sg[j], POST && a.tail.counters != nullptr);
             }
-            tail_arrive(a.tail, plane / a.c);
+            if constexpr (POST) legacy_tail_arrive(a.tail, plane / a.c);
         }
         return;
     }
@@ -140,8 +249,8 @@ __device__ __forceinline__ void resize_h_pass(const ResizeArgs &a, const ResizeD
     for (int it = threadIdx.x; it < total; it += RT) ss = h_out(it, ss);
     if constexpr (RESID) {
         const float t = block_sum(ss, s_red);
-        if (threadIdx.x == 0) tail_publish(&a.partials[(int64_t)plane * nblk + blk], t, a.tail.counters != nullptr);
-        tail_arrive(a.tail, plane / a.c);
+        if (threadIdx.x == 0) tail_publish(&a.partials[(int64_t)plane * nblk + blk], t, POST && a.tail.counters != nullptr);
+        if constexpr (POST) legacy_tail_arrive(a.tail, plane / a.c);
     }
 }
 
@@ -292,7 +401,7 @@ __global__ __launch_bounds__(RT) void k_resize_fwd(ResizeArgs a, ResizeDev d)
             return 0.0f;
         }
     };
-    resize_h_pass<RESID>(a, d, h_out, (p1 - p0) * d.out_w, plane, nblk, blk, s_red);
+    resize_h_pass<POST, RESID>(a, d, h_out, (p1 - p0) * d.out_w, plane, nblk, blk, s_red);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -447,7 +556,7 @@ __global__ __launch_bounds__(RT, 3) void k_resize_fwd_rows(ResizeArgs a, ResizeD
             return 0.0f;
         }
     };
-    resize_h_pass<RESID>(a, d, h_out, (p1 - p0) * d.out_w, plane, nblk, blk, s_red);
+    resize_h_pass<POST, RESID>(a, d, h_out, (p1 - p0) * d.out_w, plane, nblk, blk, s_red);
 }
 
 // LDS: s_u[adj_rows][out_w] | s_t[ti][out_w]
@@ -1016,7 +1125,8 @@ int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     a.x_t = f.x_t; a.model_out = f.model_out; a.noise = f.noise; a.x0_hat = f.x0_hat; a.sample = f.sample;
     a.inside_w = f.inside; a.y = f.y; a.y_div = f.y_div; a.out = f.resid; a.partials = f.partials;
     a.c = (int)f.c; a.planes = (int)(f.n * f.c); a.k = f.k;
-    a.tail = f.tail;
+    a.tail.counters = f.tail.counters; a.tail.partials = f.tail.partials; a.tail.parts = f.tail.parts;
+    a.tail.out = f.tail.out; a.tail.n = (int)f.n;
     a.tail.blocks_per_particle = (int)resize_fwd_blocks_per_particle(op, f.c, f.n * f.c);
     const bool vec = rz_vec(op, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) &&
                      (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
@@ -1040,15 +1150,13 @@ int resize_step_bwd(const dpsx_op *op, const StepBwdArgs &b, hipStream_t s)
 }
 
 int resize_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials, int64_t n,
-                 int64_t c, int l1, const Tail &tail, hipStream_t s)
+                 int64_t c, int l1, hipStream_t s)
 {
     if (n == 0) return DPSX_OK;
     ResizeArgs a{};
     a.x = x; a.y = y; a.y_div = row_div(y_n, n); a.out = nullptr; a.partials = partials; a.c = (int)c;
     a.planes = (int)(n * c);
     a.l1 = l1;
-    a.tail = tail;
-    a.tail.blocks_per_particle = (int)resize_fwd_blocks_per_particle(op, c, n * c);
     return launch_fwd<false, true>(op, a, rz_vec(op, {x}), s);
 }
 

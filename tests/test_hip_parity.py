@@ -998,25 +998,26 @@ def test_score_argmin_fused(K, name, hw, n):
     assert int(best) == n - 1 and bool(torch.isnan(val).all())
 
 
-@pytest.mark.parametrize("name,hw", [("gauss", 256), ("motion", 128), ("sr4", 256), ("inpaint", 256), ("gauss", 46),
-                                     ("denoise", 17)])
-def test_step_fwd_norm_modes_bit_identical(K, name, hw):
-    """K1 finishing the norm itself (last block of each particle) == the stand-alone finalisation kernel of r01 ==
-    K2's prologue finalisation: the same bits, and repeatable over launches (self-resetting counters)"""
+def _norm_modes_bit_identical(K, name, hw, n, draw=None):
+    """the body of test_step_fwd_norm_modes_bit_identical*.  draw: a kernels.Rng record -- the noise is drawn inside K1
+    (the handle must have that form) instead of read from a tensor"""
     rng = np.random.RandomState(hw)
-    n = 5
     mask = (np.random.RandomState(7).rand(1, 1, hw, hw) < 0.5).astype(np.float32)
     op, fkw = make_product_op(name, hw=hw, kernel=synthetic_motion_kernel(61, 5), mask=mask)
     x, mo, z = dev(rng.randn(n, 3, hw, hw).astype(np.float32)), dev(rng.randn(n, 6, hw, hw).astype(np.float32) * 0.4), \
         dev(rng.randn(n, 3, hw, hw).astype(np.float32))
     y = op.forward(dev(rng.uniform(-1, 1, (1, 3, hw, hw)).astype(np.float32)), **fkw).detach().contiguous()
     handle = op.hip_handle_for(fkw["mask"]) if name == "inpaint" else op.hip_handle(x)
+    noise = dict(noise=z)
+    if draw is not None:
+        assert handle.draws_in_kernel(3, hw, hw)
+        noise = dict(rng=draw)
     ck = _sampler("ddpm", "").step_coefs[400]
     outs = []
     for finalize in (True, False, True, True):
         buf = K.StepBuffers(handle, n, 3, hw, hw, DEV)
         buf.norm.fill_(-1.0)
-        K.step_fwd(handle, buf, x, mo, z, y, ck, finalize_norm=finalize)
+        K.step_fwd(handle, buf, x, mo, y=y, coefs=ck, finalize_norm=finalize, **noise)
         if finalize:
             first = buf.norm.clone()
             assert float(first.min()) > 0
@@ -1028,6 +1029,27 @@ def test_step_fwd_norm_modes_bit_identical(K, name, hw):
         assert torch.equal(a, outs[0][0]) and torch.equal(b, outs[0][1])
     r = (y - op.forward(buf.x0_hat, **fkw)).reshape(n, -1)
     assert rel_l2(host(outs[0][0]), host(r.norm(dim=1))) < TOL
+
+
+@pytest.mark.parametrize("name,hw", [("gauss", 256), ("motion", 128), ("sr4", 256), ("inpaint", 256), ("gauss", 46),
+                                     ("denoise", 17)])
+def test_step_fwd_norm_modes_bit_identical(K, name, hw):
+    """K1 finishing the norm itself (last block of each particle) == the stand-alone finalisation kernel of r01 ==
+    K2's prologue finalisation: the same bits, and repeatable over launches (self-resetting counters)"""
+    _norm_modes_bit_identical(K, name, hw, 5)
+
+
+@pytest.mark.parametrize("name,hw", [("gauss", 128), ("motion", 128), ("sr4", 256), ("inpaint", 64)])
+def test_step_fwd_norm_modes_bit_identical_in_kernel_draw(K, name, hw):
+    """the same with the noise drawn inside K1 (the RNG instantiations carry the in-launch norm too): the smallest
+    whole-tile shapes with several arriving blocks per particle (128^2: 4 tiles x 3 planes)"""
+    _norm_modes_bit_identical(K, name, hw, 3, draw=K.Rng(29, 400))
+
+
+def test_step_fwd_norm_modes_bit_identical_coarse_blocking(K):
+    """the same under the resize kernel's coarse blocking, where one block publishes several partials and arrives once:
+    96 planes x out_h / tp workgroups is past the threshold up to which the launch takes the fine blocking (n = 5 above)"""
+    _norm_modes_bit_identical(K, "sr4", 256, 32)
 
 
 @pytest.mark.parametrize("name,hw,n", [("gauss", 256, 64), ("sr4", 256, 64), ("inpaint", 256, 64), ("motion", 128, 16),
