@@ -94,6 +94,9 @@ SIGNATURES = {
     "dpsx_replicate_f32": (c_int, [_f, _p, _f, _i64, _i64, _i64, _p]),
     "dpsx_resample_draw_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _p, _p, _p]),
     "dpsx_resample_seg_f32": (c_int, [_f, _f, _i64, _i64, c_float, _f, _f, _f, _p, _p, _i64, _i64, _p]),
+    "dpsx_resample_draw_seg_ex_f32": (c_int, [_f, _f, _i64, _i64, c_float, _p, _p, c_int, c_int32, _p, _f, _p]),
+    "dpsx_resample_seg_ex_f32": (c_int, [_f, _f, _i64, _i64, c_float, _f, _f, _f, _p, _p, _i64, _i64, c_int, c_int32,
+                                         _p, _f, _p]),
     "dpsx_randn_f32": (c_int, [_f, _p, _i64, _i64, POINTER(RngRec), _p]),
     "dpsx_posterior_fwd_rng_f32": (c_int, [_f, _f, POINTER(RngRec), _f, _f, _p, _i64, _i64, POINTER(Coefs), _p]),
     "dpsx_step_draws_in_kernel": (c_int, [c_void_p, _i64, _i64, _i64]),

@@ -1126,12 +1126,10 @@ int dpsx_resample_draw_seg_f32(const float *d, const float *u, int64_t segments,
     return resample_draw_seg_f32(d, u, segments, k, inv_scale, ids_out, q_out, (hipStream_t)stream);
 }
 
-int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
-                          const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
-                          int64_t n, int64_t chw, void *stream)
+// ... and of the fused form's gathers
+static int resample_seg_args(const float *d, int64_t segments, int64_t k, const float *src, const float *dst,
+                             const float *d_out, int64_t n, int64_t chw)
 {
-    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
-    if (rc != DPSX_OK) return rc;
     if (!src || !dst || !d_out || n != segments * k || chw < 1) return DPSX_EINVAL;
     // the gather reads whole particles of src while other blocks write dst: no overlap of the two ranges, and the
     // distances are read by every block while one of them writes d_out
@@ -1140,7 +1138,46 @@ int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int6
     if (sb < db + bytes && db < sb + bytes) return DPSX_EINVAL;
     if (d_out < d + n && d < d_out + n) return DPSX_EINVAL;
     if (n > 65535) return DPSX_EUNSUPPORTED;                              // one grid row per destination particle
+    return DPSX_OK;
+}
+
+int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                          const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
+                          int64_t n, int64_t chw, void *stream)
+{
+    int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
+    if (rc == DPSX_OK) rc = resample_seg_args(d, segments, k, src, dst, d_out, n, chw);
+    if (rc != DPSX_OK) return rc;
     return resample_seg_f32(d, u, segments, k, inv_scale, src, dst, d_out, ids_out, q_out, chw, (hipStream_t)stream);
+}
+
+static bool resample_scheme_ok(int scheme, int32_t ess_q16)
+{
+    return scheme >= DPSX_RESAMPLE_MULTINOMIAL && scheme <= DPSX_RESAMPLE_SYSTEMATIC && ess_q16 >= 0 && ess_q16 <= 65536;
+}
+
+int dpsx_resample_draw_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                                  int64_t *ids_out, int32_t *q_out, int scheme, int32_t ess_q16,
+                                  uint8_t *resampled_out, float *ess_out, void *stream)
+{
+    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
+    if (rc != DPSX_OK) return rc;
+    if (!resample_scheme_ok(scheme, ess_q16)) return DPSX_EINVAL;
+    return resample_draw_seg_ex_f32(d, u, segments, k, inv_scale, ids_out, q_out, scheme, ess_q16, resampled_out, ess_out,
+                                    (hipStream_t)stream);
+}
+
+int dpsx_resample_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                             const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
+                             int64_t n, int64_t chw, int scheme, int32_t ess_q16, uint8_t *resampled_out,
+                             float *ess_out, void *stream)
+{
+    int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
+    if (rc == DPSX_OK) rc = resample_seg_args(d, segments, k, src, dst, d_out, n, chw);
+    if (rc != DPSX_OK) return rc;
+    if (!resample_scheme_ok(scheme, ess_q16)) return DPSX_EINVAL;
+    return resample_seg_ex_f32(d, u, segments, k, inv_scale, src, dst, d_out, ids_out, q_out, chw, scheme, ess_q16,
+                               resampled_out, ess_out, (hipStream_t)stream);
 }
 
 int dpsx_pack_champion_f32(const float *particles, const float *costs, const int64_t *best_idx_dev,

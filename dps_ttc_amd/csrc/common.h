@@ -584,6 +584,13 @@ int resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int6
                           int32_t *q_out, hipStream_t s);
 int resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
                      float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, hipStream_t s);
+// the same two launches with a scheme (DPSX_RESAMPLE_*), the ESS trigger ess_q16 in [0, 65536] and the per-segment
+// diagnostics flag_out / ess_out [segments] (nullable); the caller checked scheme and ess_q16
+int resample_draw_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, int64_t *ids,
+                             int32_t *q_out, int scheme, int ess_q16, uint8_t *flag_out, float *ess_out, hipStream_t s);
+int resample_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
+                        float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, int scheme, int ess_q16,
+                        uint8_t *flag_out, float *ess_out, hipStream_t s);
 int pack_champion(const float *particles, const float *costs, const int64_t *best, const float *val, float *out, int64_t n,
                   int64_t chw, hipStream_t s);
 int select_champion(const float *table, int world, int64_t chw, float *dst, int64_t n_out, int64_t *win_rank,

@@ -22,6 +22,7 @@ Deliberate differences from the reference snapshot:
 import functools
 import math
 import os
+from operator import index as _index
 
 import numpy as np
 import torch
@@ -151,6 +152,14 @@ class GaussianDiffusion:
         #: reference's draw) or "device" (kernels.resample: a pure function of the distances and one torch.rand per slot,
         #: computed per image on the device and fused with the particle gather -- the draw multi-image batches need)
         self.resample_draw = "multinomial"
+        #: the device draw's scheme ("multinomial", "stratified", "systematic") and ESS trigger (tau in [0, 1]: an image
+        #: resamples only while its effective sample size is below tau K; None = 1.0: whenever its weights differ) --
+        #: include/dpsx.h "resampling schemes and the ESS trigger".  Anything but the defaults needs resample_draw = "device".
+        self.resample_scheme = "multinomial"
+        self.resample_ess = None
+        #: after a resampling step with a non-default scheme / ESS: [images] uint8 (1: the image resampled) and its ESS
+        self.last_resample_flags = None
+        self.last_resample_ess = None
         #: the step noise: "torch" (torch.randn, one stream over the whole batch) or "device" (kernels.Rng: a counter-based
         #: draw keyed on (noise_seed, loop index, path id, element), drawn inside the fused launches where the operator has
         #: that form -- a path's noise then does not depend on the batch it runs in, the particle groups, the images per
@@ -198,6 +207,21 @@ class GaussianDiffusion:
         if value not in ("multinomial", "device"):
             raise ValueError(f"resample_draw must be 'multinomial' or 'device' (got {value!r})")
         return value
+
+    def _check_resample_scheme(self, draw, scheme=None, ess=None):
+        """(scheme, ess) for kernels.resample / resample_draw, or None for the defaults (the plain entry points)"""
+        scheme = self.resample_scheme if scheme is None else scheme
+        ess = self.resample_ess if ess is None else ess
+        kernels.resample_scheme_args(scheme, ess)                      # ValueError on an unknown scheme / tau outside [0, 1]
+        if scheme == "multinomial" and ess is None:
+            return None
+        if getattr(self, "global_resample", False):
+            raise NotImplementedError(f"resample_scheme = {scheme!r} / resample_ess = {ess!r} with global (multi-rank) "
+                                      "resampling is not supported: the exchange keeps its own multinomial draw")
+        if draw != "device":
+            raise ValueError(f"resample_scheme = {scheme!r} / resample_ess = {ess!r} need resample_draw = 'device' "
+                             f"(got {draw!r}): the schemes and the ESS trigger are the device draw's")
+        return scheme, ess
 
     @staticmethod
     def _check_noise_draw(value):
@@ -829,12 +853,18 @@ class SearchDDPM(DDPM):
         segments = self._segments(measurement, n, kwargs.get('n_images', None), refuse_multi=None if draw == "device" else (
             "resample_update over a multi-image batch is not supported: the multinomial draw would mix particles of "
             "different images (it needs a per-image RNG stream policy; resample_draw='device' draws per image)"))
+        opts = self._check_resample_scheme(draw, kwargs.get('resample_scheme', None), kwargs.get('resample_ess', None))
         if draw == "device":
             if resample and prev_costs is not None:
                 # one uniform per slot whatever the weights turn out to be (a flat segment keeps its particles: the
                 # draw's identity rule), so the stream position does not depend on data and nothing is read back
                 inv = rs_temp / steps_done if potential_type == 'mean' else rs_temp
-                ids = kernels.resample_draw(prev_costs, self._rand(n, prev_costs), segments, inv)
+                if opts is None:
+                    ids = kernels.resample_draw(prev_costs, self._rand(n, prev_costs), segments, inv)
+                    self.last_resample_flags = self.last_resample_ess = None
+                else:
+                    ids, self.last_resample_flags, self.last_resample_ess = kernels.resample_draw(
+                        prev_costs, self._rand(n, prev_costs), segments, inv, scheme=opts[0], ess=opts[1], want_flags=True)
                 self.last_resample_ids = ids
                 candidates = kernels.gather(candidates, ids, validate=False)      # ids inside [0, n) by construction
                 denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
@@ -870,14 +900,23 @@ class TTC_DDIM(DDIM):
     launch (kernels.resample).  It is defined per image, so a measurement with one row per image (or `n_images = M`)
     is accepted in that mode: image m's particles are resampled among themselves, and fed the same uniforms they are
     what a single-image run draws, bit for bit.  The default stays torch.multinomial over all N weights, and
-    `global_resample` (several ranks) keeps its own multinomial draw whatever this option says."""
+    `global_resample` (several ranks) keeps its own multinomial draw whatever this option says.
+
+    `resample_scheme` ("stratified", "systematic") and `resample_ess` (tau: an image resamples only while its effective
+    sample size is below tau K, decided inside the launch) are options of the device draw; `resample_every` is the
+    loop's resampling period.  After a resampling step with a non-default scheme or tau, `last_resample_flags` /
+    `last_resample_ess` hold the per-image diagnostics."""
 
     global_resample = False
     resample_generator = None
     #: how the drawn particles travel between ranks: "selected" (one all-to-all of the drawn ones, each once per
     #: destination), "all" (all-gather of every state, no host read of device ids) or "auto" (distributed.resample_particles)
     resample_fetch = "auto"
+    #: the loop resamples after every step whose index is a multiple of this (the reference's hard-coded 10);
+    #: resample_every = 1 with resample_ess = 0.5 is adaptive SMC: look at every step, shuffle only degenerate images
+    resample_every = 10
     _resample_segments = 1
+    _resample_opts = None
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
@@ -885,9 +924,10 @@ class TTC_DDIM(DDIM):
         draw = self._check_resample_draw(self.resample_draw)
         n = img.shape[0]
         segments = self._segments(measurement, n, kwargs.get('n_images', None))
-        resample_every_steps, resample_scale = 10, 100
+        resample_every_steps, resample_scale = self._check_resample_every(self.resample_every), 100
+        self._resample_opts = self._check_resample_scheme(draw)
         distance = None
-        self.last_resample_ids = None
+        self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
         # 'ps'-type methods run the three fused launches with the DDIM variant of S1; the rest (e.g. 'mcg', the
         # method whose two return values fit the reference loop's unpacking at :672) go through the per-op path
         plan = self._fusion_plan(measurement_cond_fn, img)
@@ -934,6 +974,18 @@ class TTC_DDIM(DDIM):
                 img, distance = self._resample(img, distance, resample_scale)
         return img.clone(), distance.clone()
 
+    @staticmethod
+    def _check_resample_every(value):
+        try:
+            if isinstance(value, bool):
+                raise TypeError
+            every = _index(value)
+        except TypeError:
+            every = 0
+        if every < 1:
+            raise ValueError(f"resample_every must be a positive integer (got {value!r})")
+        return every
+
     def _resample(self, img, distance, resample_scale):
         """the resampling block (:685-698): w = exp(-d / 100), multinomial with replacement, skipped when all
         weights are equal.  The draw is torch.multinomial (RNG parity), the particle gather is HIP."""
@@ -947,8 +999,13 @@ class TTC_DDIM(DDIM):
         if self.resample_draw == "device":
             # one launch: per-image draw + both gathers.  img / distance are views of the persistent step buffers on the
             # fused route (the launch's src / d), the results are fresh tensors
-            img, distance, ids = kernels.resample(img, distance, self._rand(n, distance),
-                                                  self._resample_segments, 1.0 / resample_scale)
+            if self._resample_opts is None:
+                img, distance, ids = kernels.resample(img, distance, self._rand(n, distance),
+                                                      self._resample_segments, 1.0 / resample_scale)
+            else:
+                img, distance, ids, self.last_resample_flags, self.last_resample_ess = kernels.resample(
+                    img, distance, self._rand(n, distance), self._resample_segments, 1.0 / resample_scale,
+                    scheme=self._resample_opts[0], ess=self._resample_opts[1], want_flags=True)
             self.last_resample_ids = ids
             return img, distance
         if n <= 1:

@@ -602,21 +602,47 @@ def _resample_args(d, u, segments):
     return d, u, segments, n
 
 
-def resample_draw(d, u, segments, inv_scale, want_weights=False):
+RESAMPLE_SCHEMES = {"multinomial": 0, "stratified": 1, "systematic": 2}     # DPSX_RESAMPLE_* of include/dpsx.h
+
+
+def resample_scheme_args(scheme, ess):
+    """(scheme id, ess_q16) of include/dpsx.h "resampling schemes and the ESS trigger": ess is tau in [0, 1] (None: 1.0,
+    every segment whose weights are not all equal resamples) -> tau * 65536 rounded to nearest"""
+    if scheme not in RESAMPLE_SCHEMES:
+        raise ValueError(f"resample scheme must be one of {sorted(RESAMPLE_SCHEMES)} (got {scheme!r})")
+    tau = 1.0 if ess is None else float(ess)
+    if not 0.0 <= tau <= 1.0:                                       # NaN fails both comparisons
+        raise ValueError(f"the ESS threshold is a fraction of the particle count in [0, 1] (got {ess!r})")
+    return RESAMPLE_SCHEMES[scheme], int(tau * 65536.0 + 0.5)
+
+
+def resample_draw(d, u, segments, inv_scale, want_weights=False, scheme="multinomial", ess=None, want_flags=False):
     """The resampling draw of include/dpsx.h per segment of K = N / segments particles: d [N] distances, u [N] uniforms in
     [0, 1) (one per output slot, e.g. torch.rand) -> ids [N] int64 global particle indices, each inside its own segment;
-    a pure function of (d, u), one launch, nothing read back.  want_weights: also the integer weights q [N] int32."""
+    a pure function of (d, u), one launch, nothing read back.  want_weights: also the integer weights q [N] int32.
+    scheme "stratified" / "systematic", ess (tau in [0, 1]: a segment resamples only while its effective sample size is
+    below tau K, else it keeps its particles) or want_flags (also flags [segments] uint8, 1 where the segment resampled,
+    and its ESS [segments] fp32) take the scheme / ESS entry point; the defaults take the plain one."""
     d, u, segments, n = _resample_args(d, u, segments)
     ids = torch.empty(n, dtype=torch.int64, device=d.device)
     q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
-    check(lib().dpsx_resample_draw_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
-                                           stream_of(d)), "dpsx_resample_draw_seg_f32")
-    return (ids, q) if want_weights else ids
+    if scheme == "multinomial" and ess is None and not want_flags:
+        check(lib().dpsx_resample_draw_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
+                                               stream_of(d)), "dpsx_resample_draw_seg_f32")
+        return (ids, q) if want_weights else ids
+    sid, ess_q16 = resample_scheme_args(scheme, ess)
+    flags = torch.empty(segments, dtype=torch.uint8, device=d.device) if want_flags else None
+    ess_out = torch.empty(segments, dtype=torch.float32, device=d.device) if want_flags else None
+    check(lib().dpsx_resample_draw_seg_ex_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
+                                              sid, ess_q16, ptr(flags), ptr(ess_out), stream_of(d)),
+          "dpsx_resample_draw_seg_ex_f32")
+    out = (ids,) + ((q,) if want_weights else ()) + ((flags, ess_out) if want_flags else ())
+    return out if len(out) > 1 else ids
 
 
-def resample(src, d, u, segments, inv_scale, want_weights=False):
-    """resample_draw fused with the gathers, ONE launch: -> (src[ids], d[ids], ids[, q]) for src [N, ...] fp32.
-    The results are fresh tensors (the launch does not work in place)."""
+def resample(src, d, u, segments, inv_scale, want_weights=False, scheme="multinomial", ess=None, want_flags=False):
+    """resample_draw fused with the gathers, ONE launch: -> (src[ids], d[ids], ids[, q][, flags, ess]) for src [N, ...]
+    fp32.  The results are fresh tensors (the launch does not work in place); a segment that does not resample is copied."""
     src = f32c(src, "particles")
     d, u, segments, n = _resample_args(d, u, segments)
     if src.dim() < 1 or src.shape[0] != n or src.device != d.device:
@@ -626,10 +652,18 @@ def resample(src, d, u, segments, inv_scale, want_weights=False):
     dst, d_out = torch.empty_like(src), torch.empty_like(d)
     ids = torch.empty(n, dtype=torch.int64, device=d.device)
     q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
-    check(lib().dpsx_resample_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
-                                      ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), stream_of(src)),
-          "dpsx_resample_seg_f32")
-    return (dst, d_out, ids, q) if want_weights else (dst, d_out, ids)
+    if scheme == "multinomial" and ess is None and not want_flags:
+        check(lib().dpsx_resample_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
+                                          ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), stream_of(src)),
+              "dpsx_resample_seg_f32")
+        return (dst, d_out, ids, q) if want_weights else (dst, d_out, ids)
+    sid, ess_q16 = resample_scheme_args(scheme, ess)
+    flags = torch.empty(segments, dtype=torch.uint8, device=d.device) if want_flags else None
+    ess_out = torch.empty(segments, dtype=torch.float32, device=d.device) if want_flags else None
+    check(lib().dpsx_resample_seg_ex_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
+                                         ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), sid, ess_q16, ptr(flags),
+                                         ptr(ess_out), stream_of(src)), "dpsx_resample_seg_ex_f32")
+    return (dst, d_out, ids) + ((q,) if want_weights else ()) + ((flags, ess_out) if want_flags else ())
 
 
 def pack_champion(particles, costs=None, best=None, best_val=None, out=None):

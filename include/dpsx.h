@@ -337,6 +337,39 @@ int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int6
                           const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
                           int64_t n, int64_t chw, void *stream);
 
+/* ---- resampling schemes and the ESS trigger: the two entry points above with a scheme, a per-segment trigger and two
+ * per-segment diagnostics.  Steps 1-3 are the draw's; with T = sum q_i, cdf_i = q_0 + ... + q_i, S2 = sum q_i^2 (exact
+ * integers: T <= 2^36, S2 < 2^60 at k = 4096):
+ *   trigger   ess_q16 in [0, 65536] is tau * 65536 rounded to nearest.  A segment resamples iff
+ *             T^2 * 65536 < ess_q16 * k * S2   (both sides up to 2^88, compared in 128 bits), i.e. iff its effective
+ *             sample size (sum w)^2 / sum w^2 is below tau * k; a segment that does not gets the identity.  By
+ *             Cauchy-Schwarz T^2 <= k S2 with equality iff all q_i are equal, so ess_q16 = 65536 is exactly step 4's
+ *             flat rule ("always, as above"; the all-zero segment gives 0 < 0), and ess_q16 = 0 means never.
+ *   position  of slot j (the local index inside its segment), ui as in step 5:
+ *             DPSX_RESAMPLE_MULTINOMIAL  target_j = (T * ui_j) >> 24                         (step 5)
+ *             DPSX_RESAMPLE_STRATIFIED   target_j = ((T * (j * 2^24 + ui_j)) >> 24) / k      (product in 128 bits)
+ *             DPSX_RESAMPLE_SYSTEMATIC   the same with ui_0, the uniform of the segment's first slot, for every j; the
+ *                                        other k - 1 uniforms are ignored (the caller still supplies k of them, so its
+ *                                        RNG stream position does not depend on the scheme)
+ *             slot j takes the smallest i with cdf_i > target_j, clamped to [0, k - 1].
+ * target_j < T always: a particle with q_i = 0 is never drawn and ids stay inside their segment whatever d and u hold.
+ * With L_i = floor(k q_i / T) and n_i the number of slots that drew particle i: systematic L_i <= n_i <= L_i + 1,
+ * stratified max(0, L_i - 1) <= n_i <= L_i + 2; both give ids that are non-decreasing in j.  The best particle of a
+ * segment has q_i = 2^24 >= T / k, so the systematic scheme never loses it.
+ *   resampled_out [segments] uint8 (nullable): 1 where the segment resampled, exactly the trigger above.
+ *   ess_out       [segments] fp32  (nullable): (double) T * (double) T / (double) S2 rounded to fp32; 0 when S2 = 0.
+ * Everything is integer arithmetic from q on, so these ids too are a property of the segment and not of the launch.
+ * Refusals as above; an unknown scheme or ess_q16 outside [0, 65536] is DPSX_EINVAL.  With scheme 0 and ess_q16 = 65536
+ * every output equals the entry points above. */
+enum { DPSX_RESAMPLE_MULTINOMIAL = 0, DPSX_RESAMPLE_STRATIFIED = 1, DPSX_RESAMPLE_SYSTEMATIC = 2 };
+int dpsx_resample_draw_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                                  int64_t *ids_out, int32_t *q_out, int scheme, int32_t ess_q16,
+                                  uint8_t *resampled_out, float *ess_out, void *stream);
+int dpsx_resample_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
+                             const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
+                             int64_t n, int64_t chw, int scheme, int32_t ess_q16, uint8_t *resampled_out,
+                             float *ess_out, void *stream);
+
 /* ---- counter-based normals: the step noise as a pure function of (seed, step, tag, particle id, element), so a path's
  * noise does not depend on the batch, the particle groups, the images per batch or the ranks it is computed with.
  * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), one call per float4 unit:

@@ -111,6 +111,15 @@ def parse_args(argv=None):
                    help='the resampling draw of ttc_ddim: torch.multinomial over all particles (default, the '
                         "reference's draw) or the library's per-image draw fused with the particle gather "
                         '(one launch; required for --images_per_batch > 1 with ttc_ddim)')
+    p.add_argument('--resample_scheme', type=str, default='multinomial', choices=('multinomial', 'stratified', 'systematic'),
+                   help='the scheme of the device draw: independent uniforms (default), one uniform per stratum, or one '
+                        'uniform per image (systematic: never loses the best particle); needs --resample_draw device')
+    p.add_argument('--resample_ess', type=float, default=None,
+                   help='resample an image only while its effective sample size is below this fraction of its particles '
+                        '(in [0, 1]; default: whenever its weights differ); decided on the device; needs --resample_draw device')
+    p.add_argument('--ttc_resample_every', type=int, default=10,
+                   help='ttc_ddim resamples after every step whose index is a multiple of this (1 with --resample_ess 0.5: '
+                        'adaptive SMC)')
     p.add_argument('--noise_draw', type=str, default='torch', choices=('torch', 'device'),
                    help="the step noise and x_start: torch.randn over the whole batch (default) or the library's "
                         'counter-based draw keyed on (--seed, step, path id, element): a path then draws the same noise '
@@ -156,6 +165,27 @@ def check_images_per_batch(args, sampler_name, world):
                          "for all particles")
 
 
+def check_resample_scheme(args, sampler_name=None):
+    """--resample_scheme / --resample_ess / --ttc_resample_every: reject bad combinations before any GPU work (one-line
+    message); sampler_name: also reject them for a sampler whose loop never resamples, instead of ignoring them"""
+    if args.ttc_resample_every < 1:
+        raise SystemExit(f"--ttc_resample_every must be at least 1 (got {args.ttc_resample_every})")
+    if args.resample_ess is not None and not 0.0 <= args.resample_ess <= 1.0:
+        raise SystemExit(f"--resample_ess is a fraction of the particle count in [0, 1] (got {args.resample_ess})")
+    for flag, value, default in (("--resample_scheme", args.resample_scheme, "multinomial"),
+                                 ("--resample_ess", args.resample_ess, None)):
+        if value != default and args.resample_draw != 'device':
+            raise SystemExit(f"{flag} {value} needs --resample_draw device: the schemes and the ESS trigger are options "
+                             "of the library's per-image draw")
+    if sampler_name is not None and sampler_name != 'ttc_ddim':
+        for flag, value, default in (("--resample_scheme", args.resample_scheme, "multinomial"),
+                                     ("--resample_ess", args.resample_ess, None),
+                                     ("--ttc_resample_every", args.ttc_resample_every, 10)):
+            if value != default:
+                raise SystemExit(f"{flag} {value} is an option of sampler ttc_ddim, the loop that resamples (the diffusion "
+                                 f"config names {sampler_name})")
+
+
 def check_beam_width(args, sampler_name, world):
     """--beam_width: reject what the beam loop does not support, before any GPU work (one-line message)"""
     b = args.beam_width
@@ -176,6 +206,9 @@ def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    check_resample_scheme(args)
+    if (args.resample_scheme, args.resample_ess, args.ttc_resample_every) != ('multinomial', None, 10):
+        check_resample_scheme(args, load_yaml(args.diffusion_config)['sampler'])
     if args.beam_width != 1:
         check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
     if args.images_per_batch != 1:
@@ -229,6 +262,8 @@ def main(argv=None):
     sampler = create_sampler(**diffusion_config)
     sampler.particle_groups = max(1, args.particle_groups)
     sampler.resample_draw = args.resample_draw
+    sampler.resample_scheme, sampler.resample_ess = args.resample_scheme, args.resample_ess
+    sampler.resample_every = args.ttc_resample_every
     sampler.noise_draw = args.noise_draw
     sampler.beam_width = args.beam_width
     sampler.noise_seed = args.seed or 0          # the same on every rank: the path id tells the ranks' particles apart

@@ -10,10 +10,11 @@ Prints one line per launch: avg / min microseconds and achieved GB/s against the
 --images M: the step's three launches (fwd, bwd, upd) for a multi-image batch of M images x --particles K with one
 measurement (and inpainting mask) per image, as ONE sequence of N = M K particles, against M sequential K-particle
 sequences with y[m] (and mask[m]) in the same process: us per step and particle-steps per second of both.
---resample: the resampling step of ttc_ddim on [N, 3, 256, 256] particles, three forms alternated in one process:
+--resample: the resampling step of ttc_ddim on [N, 3, 256, 256] particles, its forms alternated in one process:
 (a) torch.multinomial + its [N]-sized glue + two gathers (resample_draw = "multinomial", the non-parity branch),
-(b) kernels.resample_draw + two gathers, (c) the fused kernels.resample; single image at K = 16 / 64 / 512 and
-M (default 4) images x K = 16, there also against M single-image calls of each form.
+(b) kernels.resample_draw + two gathers, (c) the fused kernels.resample, (d-f) the fused scheme / ESS launch
+(dpsx_resample_seg_ex_f32: multinomial tau = 1, systematic tau = 1, systematic tau = 0.5); single image at
+K = 16 / 64 / 512 and M (default 4) images x K = 16, there also against M single-image calls of each form.
     python tools/kbench.py --noise-draw                                               (the step noise, 256^2, N = --particles)
 --noise-draw: K1 of every operator and the single-state search step with the step noise drawn three ways, alternated in
 one process: (a) torch.randn + the pointer launch (noise_draw = "torch"), (b) kernels.randn (dpsx_randn_f32) + the pointer
@@ -280,6 +281,9 @@ def resample_step(args):
     def fused(img, distance, u, segments):
         return kernels.resample(img, distance, u, segments, 1.0 / scale)
 
+    def fused_ex(img, distance, u, segments, scheme, ess):       # dpsx_resample_seg_ex_f32; the same outputs as c
+        return kernels.resample(img, distance, u, segments, 1.0 / scale, scheme=scheme, ess=ess)
+
     def timed(fn):
         for _ in range(3):
             fn()
@@ -303,7 +307,10 @@ def resample_step(args):
         if M == 1:
             forms.append(("a multinomial + 2 gathers", lambda: multinomial(img, distance, u, 1)))
         forms += [("b draw + 2 gathers", lambda: draw_gather(img, distance, u, M)),
-                  ("c fused", lambda: fused(img, distance, u, M))]
+                  ("c fused", lambda: fused(img, distance, u, M)),
+                  ("d fused ex, multinomial tau 1", lambda: fused_ex(img, distance, u, M, "multinomial", 1.0)),
+                  ("e fused ex, systematic tau 1", lambda: fused_ex(img, distance, u, M, "systematic", 1.0)),
+                  ("f fused ex, systematic tau 0.5", lambda: fused_ex(img, distance, u, M, "systematic", 0.5))]
         if M > 1:
             forms += [(f"a multinomial + 2 gathers, {M} calls", lambda: [multinomial(*p, 1) for p in parts]),
                       (f"b draw + 2 gathers, {M} calls", lambda: [draw_gather(*p, 1) for p in parts]),
