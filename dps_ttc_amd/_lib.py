@@ -109,6 +109,9 @@ SIGNATURES = {
     "dpsx_topk_seg_f32": (c_int, [_f, _i64, _i64, _i64, _p, _f, _p]),
     "dpsx_search_step_beam_f32": (c_int, [c_void_p, _f, _f, _f, POINTER(RngRec), _f, _i64, _f, _f, _p, _f, _f, _i64, _i64,
                                           _i64, _i64, _i64, _i64, _i64, POINTER(Coefs), _p, _i64, _p]),
+    "dpsx_corr_slots": (c_int, [_i64]),
+    "dpsx_step_update_corr_f32": (c_int, [_f, _f, _f, _f, _f, POINTER(RngRec), _f, _f, _i64, _i64, POINTER(Coefs), _p]),
+    "dpsx_smc_accum_f32": (c_int, [_f, _f, _f, _f, c_int, _p, _i64, _i64, c_float, c_int, c_float, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

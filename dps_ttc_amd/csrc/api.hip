@@ -723,6 +723,42 @@ int dpsx_step_update_f32(const float *sample, const float *g_model_out, const fl
     return step_update(sample, g_model_out, g_unet, x_next, n, chw, to_coefs(coefs_host), (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ particle weights (smc.hip)
+int dpsx_corr_slots(int64_t chw) { return chw < 0 ? DPSX_EINVAL : cg_slots(chw); }
+
+int dpsx_step_update_corr_f32(const float *sample, const float *g_model_out, const float *g_unet, const float *model_out,
+                              const float *noise, const dpsx_rng *rng_host, float *x_next, float *corr_partials, int64_t n,
+                              int64_t chw, const dpsx_coefs *coefs_host, void *stream)
+{
+    if (!sample || !g_model_out || !x_next || !corr_partials || !coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
+    if ((noise != nullptr) == (rng_host != nullptr)) return DPSX_EINVAL;         // exactly one noise source, whatever the step
+    if (coefs_host->b == 0.0f) return DPSX_EINVAL;
+    const int mode = coefs_host->add_noise;
+    if ((mode & 1) && (mode & 2) && !(coefs_host->min_log > 0.0f)) return DPSX_EINVAL;      // eta = 0: no density to weigh
+    if ((mode & 1) && !(mode & 2) && !model_out) return DPSX_EINVAL;                       // sd comes from its variance half
+    RngK r{};
+    if (rng_host) {
+        int rc = to_rngk(rng_host, n, r);
+        if (rc != DPSX_OK) return rc;
+    }
+    if (n > 65535) return DPSX_EUNSUPPORTED;                       // particles are the grid's y dimension
+    return step_update_corr(sample, g_model_out, g_unet, model_out, noise, rng_host != nullptr, r, x_next, corr_partials, n,
+                            chw, to_coefs(coefs_host), (hipStream_t)stream);
+}
+
+int dpsx_smc_accum_f32(float *E, float *d_prev, const float *d_cur, const float *corr_partials, int slots,
+                       const uint8_t *reset, int64_t segments, int64_t n, float twist_scale, int power,
+                       float proposal_weight, void *stream)
+{
+    if (!E || !d_prev || !d_cur || n < 0 || segments < 1 || n % segments) return DPSX_EINVAL;
+    if (power != 1 && power != 2) return DPSX_EINVAL;
+    if (corr_partials && slots < 1) return DPSX_EINVAL;
+    if (!std::isfinite(twist_scale) || !std::isfinite(proposal_weight)) return DPSX_EINVAL;
+    if (n > 65535) return DPSX_EUNSUPPORTED;
+    return smc_accum(E, d_prev, d_cur, corr_partials, slots, reset, segments, n, twist_scale, power, proposal_weight,
+                     (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

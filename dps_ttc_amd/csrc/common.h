@@ -614,6 +614,15 @@ int cg_final(const float *sample, const float *d, const float *p, float *x_next,
              const float *tt, const float *pp, float *scal, float rho, float kappa, bool first, int64_t n, int64_t e,
              int64_t m, hipStream_t s);
 
+// smc.hip: the particle weights' two launches (the recurrence is stated in include/dpsx.h)
+// K3 + the proposal correction's partials [n, cg_slots(chw)]; the noise is z, or with use_rng the counters of r
+int step_update_corr(const float *sample, const float *g_mo, const float *g_unet, const float *mo, const float *z,
+                     bool use_rng, const RngK &r, float *x_next, float *partials, int64_t n, int64_t chw, const Coefs &k,
+                     hipStream_t s);
+// E += twist_scale (d_cur^power - d_prev^power) - proposal_weight sum(partials); d_prev = d_cur; reset [segments] (nullable)
+int smc_accum(float *e, float *d_prev, const float *d_cur, const float *partials, int slots, const uint8_t *reset,
+              int64_t segments, int64_t n, float twist_scale, int power, float proposal_weight, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op);
 void phase_destroy(dpsx_op *op);

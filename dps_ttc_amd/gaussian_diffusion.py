@@ -32,22 +32,26 @@ from .condition_methods import ConditioningMethod, ConjugateGradientConsistency
 from .diffstategrad_utils import apply_diffstategrad, compute_svd_and_adaptive_rank
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
-__SAMPLER__ = {}
+__SAMPLER__ = {}                  # the reference's samplers, under the reference's names
+__EXTENSION_SAMPLER__ = {}        # samplers the reference does not have ('smc_ddpm'): same lookup, their own table
 
 
-def register_sampler(name: str):
+def register_sampler(name: str, extension: bool = False):
+    """extension=True: a sampler that is not in the reference; it is found by get_sampler like the others and kept out of
+    the table that mirrors the reference's"""
     def wrapper(cls):
-        if __SAMPLER__.get(name, None):
+        if __SAMPLER__.get(name, None) or __EXTENSION_SAMPLER__.get(name, None):
             raise NameError(f"Name {name} is already registered!")
-        __SAMPLER__[name] = cls
+        (__EXTENSION_SAMPLER__ if extension else __SAMPLER__)[name] = cls
         return cls
     return wrapper
 
 
 def get_sampler(name: str):
-    if __SAMPLER__.get(name, None) is None:
+    cls = __SAMPLER__.get(name, None) or __EXTENSION_SAMPLER__.get(name, None)
+    if cls is None:
         raise NameError(f"Name {name} is not defined!")
-    return __SAMPLER__[name]
+    return cls
 
 
 def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_type, dynamic_threshold,
@@ -327,11 +331,13 @@ class GaussianDiffusion:
         return self._bufs[1]
 
     def dps_step(self, model, x_prev, idx, measurement, method, cond_kw, handle, noise=None, loop_kw=None,
-                 want_x0=False, rng=None):
+                 want_x0=False, rng=None, corr_state=None):
         """One fused DPS step at loop index idx.  Returns (x_next, norm[N]) -- device tensors that live in the
         sampler's persistent step buffers (valid until the next step; the loops clone what they hand out).
         loop_kw: the keyword arguments the calling loop passes to measurement_cond_fn besides the tensors
-        (base loop: beta_scale, t -- reference :230-236; ttc_ddim: none -- :678-682)."""
+        (base loop: beta_scale, t -- reference :230-236; ttc_ddim: none -- :678-682).
+        corr_state (a kernels.SmcState; smc_ddpm): K3 is kernels.step_update_corr, which also leaves the step's proposal
+        correction in corr_state.corr_partials."""
         x_prev = x_prev.detach().requires_grad_()
         with torch.enable_grad():
             model_out = self._call_model(model, x_prev, idx)
@@ -358,7 +364,10 @@ class GaussianDiffusion:
         if model_out.requires_grad:
             (g_unet,) = torch.autograd.grad(model_out, x_prev, grad_outputs=buf.g_model_out.to(model_out.dtype))
             g_unet = kernels.f32c(g_unet, "UNet VJP")
-        x_next = kernels.step_update(buf, g_unet, coefs)
+        if corr_state is None:
+            x_next = kernels.step_update(buf, g_unet, coefs)
+        else:
+            x_next, _ = kernels.step_update_corr(buf, g_unet, coefs, mo, noise=noise, rng=rng, state=corr_state)
         return x_next, buf.norm
 
     def _particle_group_set(self, method, cond_kw, x, images=None):
@@ -1023,3 +1032,92 @@ class TTC_DDIM(DDIM):
             ids = torch.where(flat, torch.arange(n, device=img.device), drawn)
         self.last_resample_ids = ids
         return kernels.gather(img, ids, validate=False), kernels.gather(distance.reshape(n, 1), ids, validate=False).reshape(n)
+
+
+@register_sampler(name='smc_ddpm', extension=True)
+class SMC_DDPM(DDPM):
+    """The DDPM DPS loop as a sequential Monte Carlo sampler: every particle carries the twisted-SMC log-weight of the
+    guided step (include/dpsx.h "particle weights"; Wu et al. 2023) and the particles of an image are resampled from
+    those weights.  Per step the negative log-weight E gains
+
+        twist_scale (d^p - d_prev^p)  -  proposal_weight (log p_model(x_{t-1} | x_t) - log q_guided(x_{t-1} | x_t))
+
+    with d = ||y - A(x0_hat)|| the step's distance.  The second term is summed inside the update launch
+    (kernels.step_update_corr in K3's place), the recurrence is one small launch (kernels.smc_accum), and after every step
+    whose index is a positive multiple of `resample_every` the device draw (kernels.resample, inv_scale = 1 on E) resamples
+    each image's particles; an image that resampled restarts from E = 0.  The DDPM noise keeps resampled copies apart.
+
+    Options: twist_scale (0.01: ttc_ddim's 1 / 100), twist_power (1 or 2), proposal_weight (1: the exact weight; 0: the
+    Feynman-Kac "difference" potential alone), and ttc_ddim's resample_scheme / resample_ess / resample_every.  The draw
+    is always the device draw.  After a loop: last_neg_log_weights (E after the last step, not reset), last_resample_ids /
+    last_resample_flags / last_resample_ess (the last resampling).  Returns (particles, distances) like ttc_ddim.
+    Needs a fused plan; refuses particle_groups > 1, rng_parity and global (multi-rank) resampling before any launch."""
+
+    twist_scale = 0.01
+    twist_power = 1
+    proposal_weight = 1.0
+    resample_every = 10
+    last_neg_log_weights = None
+    last_resample_ids = None
+
+    def _smc_options(self):
+        """the validated options -> (twist_scale, twist_power, proposal_weight, resample_every, scheme, ess)"""
+        scale, weight = float(self.twist_scale), float(self.proposal_weight)
+        if not (math.isfinite(scale) and math.isfinite(weight)):
+            raise ValueError(f"twist_scale and proposal_weight must be finite (got {self.twist_scale!r}, "
+                             f"{self.proposal_weight!r})")
+        if isinstance(self.twist_power, bool) or self.twist_power not in (1, 2):
+            raise ValueError(f"twist_power must be 1 or 2 (got {self.twist_power!r})")
+        every = TTC_DDIM._check_resample_every(self.resample_every)
+        if self.particle_groups > 1:
+            raise ValueError("smc_ddpm with particle_groups > 1 is not supported: the weights and the resampling are over "
+                             "the whole particle set")
+        if self.rng_parity:
+            raise ValueError("smc_ddpm has no reference loop whose host RNG stream rng_parity could replay")
+        if getattr(self, "global_resample", False):
+            raise NotImplementedError("smc_ddpm with global (multi-rank) resampling is not supported: the weights live on "
+                                      "one rank")
+        kernels.resample_scheme_args(self.resample_scheme, self.resample_ess)       # ValueError: unknown scheme / tau
+        return scale, int(self.twist_power), weight, every, self.resample_scheme, self.resample_ess
+
+    def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
+        scale, power, weight, every, scheme, ess = self._smc_options()
+        img = x_start.detach()
+        n = img.shape[0]
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if not self.hip_posterior or method is None or method.fused_spec(**kw) is None:
+            name = type(method).__name__ if method is not None else "this conditioning function"
+            raise NotImplementedError(f"smc_ddpm needs the fused ps / ps_anneal / ps_semantic step under the epsilon / "
+                                      f"learned_range / clip_denoised posterior: {name} has no fused plan")
+        segments = self._segments(measurement, n, kwargs.get('n_images', None))
+        kernels.require_cuda(img, "x_start")
+        plan = self._fusion_plan(measurement_cond_fn, img)
+        if plan is None:
+            raise NotImplementedError(f"smc_ddpm: {type(method).__name__} on {tuple(img.shape)} particles has no fused plan "
+                                      "(the per-op path computes no proposal correction)")
+        if segments > 1:
+            try:
+                self._check_multi_image(plan, method, False, segments, n)
+            except NotImplementedError as e:
+                raise NotImplementedError(f"smc_ddpm: {e}") from None
+        self._step_rng(0, n, segments)    # validates noise_draw before the first step
+        state = kernels.SmcState(n, img.shape[1:], img.device)
+        reset, distance = None, None
+        self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
+        for idx in range(self.num_timesteps - 1, -1, -1):
+            rng = self._step_rng(idx, n, segments)
+            noise = self._randn(img) if rng is None else None
+            img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise, rng=rng,
+                                          corr_state=state)
+            kernels.smc_accum(state, distance, reset, segments, scale, power, weight)
+            reset = None
+            if idx % every == 0 and idx > 0:
+                # one launch: per-image draw on E + the particle gather; the flags reset the resampled images' weights in
+                # the next smc_accum, which also brings the increment still missing through the gathered d_prev
+                img, _, ids, reset, self.last_resample_ess = kernels.resample(
+                    img, state.E, self._rand(n, img), segments, 1.0, scheme=scheme, ess=ess, want_flags=True)
+                state.d_prev = kernels.gather(state.d_prev.reshape(n, 1), ids, validate=False).reshape(n)
+                self.last_resample_ids, self.last_resample_flags = ids, reset
+        self.last_neg_log_weights = state.E
+        self.last_measurement_distance = distance.clone()
+        return img.clone(), distance.clone()

@@ -851,6 +851,66 @@ def step_update(buf, g_unet, coefs, stream=None):
     return out
 
 
+# ------------------------------------------------------------------ particle weights (include/dpsx.h: "particle weights")
+def corr_slots(chw):
+    """partial slots per particle of step_update_corr: a function of the particle size only (dpsx_corr_slots)"""
+    slots = lib().dpsx_corr_slots(int(chw))
+    if slots < 0:
+        check(int(slots), "dpsx_corr_slots")
+    return int(slots)
+
+
+class SmcState:
+    """The weights of one particle set [N, *shape]: E [N] the negative log-weights, d_prev [N] the last step's distances
+    (both start at 0) and corr_partials [N, corr_slots] that step_update_corr fills and smc_accum consumes."""
+
+    def __init__(self, n, shape, device):
+        self.n, self.shape = int(n), tuple(int(v) for v in shape)
+        self.slots = corr_slots(int(np.prod(self.shape, dtype=np.int64)))
+        f = dict(dtype=torch.float32, device=device)
+        self.E, self.d_prev = torch.zeros(self.n, **f), torch.zeros(self.n, **f)
+        self.corr_partials = torch.empty((self.n, self.slots), **f)
+
+
+def step_update_corr(buf, g_unet, coefs, model_out, noise=None, rng=None, state=None, stream=None):
+    """K3 with the proposal correction's partial sums, one launch (dpsx_step_update_corr_f32): -> (x_next, corr_partials).
+    x_next has step_update's bits; corr_partials [N, corr_slots] (state.corr_partials, or a fresh tensor) holds
+    sum q (z - q / 2), q = s / sd, per block.  model_out is the UNet output K1 read (its variance half gives sd); the noise
+    is K1's: noise= or the same rng=, exactly one of them."""
+    _noise_or_rng(noise, rng)
+    n, c, h, w = buf.shape
+    part = state.corr_partials if state is not None else \
+        torch.empty((n, corr_slots(c * h * w)), dtype=torch.float32, device=buf.sample.device)
+    if tuple(part.shape) != (n, corr_slots(c * h * w)):
+        raise ValueError(f"SmcState of {tuple(part.shape)} partials for step buffers of shape {buf.shape}")
+    if model_out is not None and (model_out.shape[0] != n or (n and model_out[0].numel() != 2 * c * h * w)):
+        raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of {buf.shape}")
+    out = buf.x_next[buf.flip]
+    buf.flip ^= 1
+    check(lib().dpsx_step_update_corr_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise),
+                                          None if rng is None else byref(rng.rec()), ptr(out), ptr(part), n, c * h * w,
+                                          byref(coefs), _stream_arg(stream, buf.sample)), "dpsx_step_update_corr_f32")
+    return out, part
+
+
+def smc_accum(state, d_cur, reset=None, segments=1, twist_scale=0.01, power=1, proposal_weight=1.0, stream=None):
+    """state.E += twist_scale (d_cur^power - d_prev^power) - proposal_weight corr; state.d_prev = d_cur, in place, one small
+    launch (dpsx_smc_accum_f32).  corr is the fixed-order double sum of state.corr_partials; proposal_weight = 0 drops the
+    term (the partials are then not read).  reset [segments] uint8 (the flags of the last resampling, or None): a flagged
+    segment's particles restart from E = 0."""
+    d_cur = f32c(d_cur.reshape(-1), "distances")
+    if d_cur.numel() != state.n or d_cur.device != state.E.device:
+        raise ValueError(f"{d_cur.numel()} distances on {d_cur.device} for the weights of {state.n} particles")
+    segments = int(segments)
+    if reset is not None and (reset.dtype != torch.uint8 or reset.numel() != segments or not reset.is_contiguous()):
+        raise ValueError(f"reset must be a contiguous uint8 tensor with one flag per segment ({segments})")
+    part = state.corr_partials if float(proposal_weight) != 0.0 else None
+    check(lib().dpsx_smc_accum_f32(ptr(state.E), ptr(state.d_prev), ptr(d_cur), ptr(part), state.slots, ptr(reset), segments,
+                                   state.n, float(twist_scale), int(power), float(proposal_weight),
+                                   _stream_arg(stream, state.E)), "dpsx_smc_accum_f32")
+    return state.E
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,

@@ -433,6 +433,47 @@ int dpsx_search_step_beam_f32(dpsx_op *op, const float *x_t, const float *model_
                               int64_t beam, int64_t n, int64_t c, int64_t h, int64_t w, const dpsx_coefs *coefs_host,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- particle weights for sequential Monte Carlo over the guided step (twisted SMC: Wu et al. 2023, "Practical and
+ * asymptotically exact conditional sampling in diffusion models"; proposal_weight = 0 leaves the Feynman-Kac "difference"
+ * potential).  K1 built sample = mean_u + sd z (z the step noise; sd per element: exp(0.5 logvar(v)) for a DDPM record,
+ * sigma for a DDIM record) and K3 forms x_next = sample - s, s = (-a/b) g_eps + g_unet.  The guided proposal is
+ * N(mean_u - s, sd^2), the model's own transition N(mean_u, sd^2), so
+ *   corr = log p_u(x_next) - log q(x_next) = sum_e q_e (z_e - q_e / 2),   q_e = s_e / sd_e
+ * and corr = 0 by definition on a step that adds no noise (bit 0 of add_noise clear: the proposal is deterministic).
+ * Each particle carries its NEGATIVE log-weight E (the sign the resampling draw takes as its d, with inv_scale = 1):
+ *   E      <- E + twist_scale (d_cur^p - d_prev^p) - proposal_weight corr        p in {1, 2}, d_cur = ||y - A(x0_hat)||
+ *   d_prev <- d_cur                                                             (d_prev starts at 0: the twist at x_T)
+ * A segment that resampled restarts from E = 0 (`reset`); the increment still missing arrives at the next step through the
+ * gathered d_prev.
+ *
+ * dpsx_step_update_corr_f32: dpsx_step_update_f32 (x_next has its bits: the same expression, the same roundings) plus
+ * the correction's partial sums, one launch.  model_out [n, 2c, h, w] (its variance half gives sd; not read for a DDIM
+ * record); the noise is `noise` [n, chw] or the counters of rng_host (tag 0 and the particle-id rule of the _rng entry
+ * points: the same bits as the pointer form fed dpsx_randn_f32) -- exactly one of the two, whatever the step.  Per element
+ * q = s / sd and q (z - 0.5 q), one rounding per operation; sd comes from the device functions S1 uses.
+ * corr_partials [n, slots], slots = dpsx_corr_slots of chw: grid (slots, n), one fp32 partial per block in a fixed tree;
+ * the slot count depends on the particle size only, so a particle's partials do not depend on the batch it runs in; no
+ * atomics.  On a step without noise the partials are written as 0 and model_out / noise are not read.
+ * DPSX_EINVAL: a null pointer, both or neither of noise / rng_host, b = 0, a DDIM record with sigma <= 0 and bit 0 set, a
+ * bad rng record; DPSX_EUNSUPPORTED: n > 65535.  All of them return before anything is launched.
+ *
+ * dpsx_smc_accum_f32: the recurrence above, one wave per particle.  corr (corr_partials == NULL: no correction term) is
+ * the particle's `slots` partials added in double in a fixed order; base = reset[segment of p] ? 0 : E[p] (reset
+ * [segments] uint8, nullable; the n particles are `segments` images of n / segments each, image-major); the sum is formed
+ * in double from the fp32 inputs and rounded to fp32 once; d_prev[p] = d_cur[p].  A non-finite input reaches its own
+ * particle's E only (the draw gives a NaN or infinite d weight 0).
+ * DPSX_EINVAL: a null E / d_prev / d_cur, power not 1 or 2, segments < 1 or not dividing n, slots < 1 with partials given,
+ * a non-finite twist_scale or proposal_weight; DPSX_EUNSUPPORTED: n > 65535.  Nothing is launched then.
+ * Both calls are one launch on `stream`: no allocation, no host read (graph-capturable). */
+int dpsx_corr_slots(int64_t chw);       /* partial slots per particle: ceil(chw / 1024), at least 1, at most 256 */
+int dpsx_step_update_corr_f32(const float *sample, const float *g_model_out, const float *g_unet /* nullable */,
+                              const float *model_out, const float *noise, const dpsx_rng *rng_host,
+                              float *x_next, float *corr_partials, int64_t n, int64_t chw,
+                              const dpsx_coefs *coefs_host, void *stream);
+int dpsx_smc_accum_f32(float *E, float *d_prev, const float *d_cur, const float *corr_partials, int slots,
+                       const uint8_t *reset, int64_t segments, int64_t n,
+                       float twist_scale, int power, float proposal_weight, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

@@ -124,6 +124,13 @@ def parse_args(argv=None):
                    help="the step noise and x_start: torch.randn over the whole batch (default) or the library's "
                         'counter-based draw keyed on (--seed, step, path id, element): a path then draws the same noise '
                         'whatever --batch_size, --particle_groups, --images_per_batch and the number of ranks are')
+    p.add_argument('--smc_twist_scale', type=float, default=None,
+                   help='smc_ddpm: the weight of the distance difference in the particle log-weights (default 0.01)')
+    p.add_argument('--smc_twist_power', type=int, default=None, choices=(1, 2),
+                   help='smc_ddpm: the power of the distance in the twist (default 1)')
+    p.add_argument('--smc_proposal_weight', type=float, default=None,
+                   help='smc_ddpm: the weight of the proposal correction log p_model - log q_guided (default 1: the exact '
+                        'twisted-SMC weight; 0: the difference potential alone)')
     p.add_argument('--beam_width', type=int, default=1,
                    help='search_ddpm: keep this many best proposals per image and step instead of one (beam search); '
                         'must divide batch_size; one rank only')
@@ -167,23 +174,47 @@ def check_images_per_batch(args, sampler_name, world):
 
 def check_resample_scheme(args, sampler_name=None):
     """--resample_scheme / --resample_ess / --ttc_resample_every: reject bad combinations before any GPU work (one-line
-    message); sampler_name: also reject them for a sampler whose loop never resamples, instead of ignoring them"""
+    message); sampler_name: also reject them for a sampler whose loop never resamples, instead of ignoring them.
+    smc_ddpm takes the three flags too and always draws on the device: --resample_draw need not be given for it"""
     if args.ttc_resample_every < 1:
         raise SystemExit(f"--ttc_resample_every must be at least 1 (got {args.ttc_resample_every})")
     if args.resample_ess is not None and not 0.0 <= args.resample_ess <= 1.0:
         raise SystemExit(f"--resample_ess is a fraction of the particle count in [0, 1] (got {args.resample_ess})")
     for flag, value, default in (("--resample_scheme", args.resample_scheme, "multinomial"),
                                  ("--resample_ess", args.resample_ess, None)):
-        if value != default and args.resample_draw != 'device':
+        if value != default and args.resample_draw != 'device' and sampler_name != 'smc_ddpm':
             raise SystemExit(f"{flag} {value} needs --resample_draw device: the schemes and the ESS trigger are options "
                              "of the library's per-image draw")
-    if sampler_name is not None and sampler_name != 'ttc_ddim':
+    if sampler_name is not None and sampler_name not in ('ttc_ddim', 'smc_ddpm'):
         for flag, value, default in (("--resample_scheme", args.resample_scheme, "multinomial"),
                                      ("--resample_ess", args.resample_ess, None),
                                      ("--ttc_resample_every", args.ttc_resample_every, 10)):
             if value != default:
                 raise SystemExit(f"{flag} {value} is an option of sampler ttc_ddim, the loop that resamples (the diffusion "
                                  f"config names {sampler_name})")
+
+
+def smc_flags(args):
+    """the --smc_* flags that were given, as (flag, value) pairs"""
+    return [(f"--smc_{k}", getattr(args, f"smc_{k}")) for k in ("twist_scale", "twist_power", "proposal_weight")
+            if getattr(args, f"smc_{k}") is not None]
+
+
+def check_smc(args, sampler_name, world=1):
+    """--smc_*: options of sampler smc_ddpm; reject them for another sampler, and what that loop does not support, before any
+    GPU work (one-line message)"""
+    for flag, value in smc_flags(args):
+        if sampler_name != 'smc_ddpm':
+            raise SystemExit(f"{flag} {value} is an option of sampler smc_ddpm (the diffusion config names {sampler_name})")
+        if value != value or value in (float("inf"), float("-inf")):
+            raise SystemExit(f"{flag} must be finite (got {value})")
+    if sampler_name == 'smc_ddpm':
+        if world > 1:
+            raise SystemExit(f"sampler smc_ddpm runs on one rank only: its weights and resampling are not exchanged between "
+                             f"ranks (WORLD_SIZE={world})")
+        if args.particle_groups > 1:
+            raise SystemExit("sampler smc_ddpm does not run with --particle_groups > 1: the weights and the resampling are "
+                             "over the whole particle set")
 
 
 def check_beam_width(args, sampler_name, world):
@@ -206,9 +237,12 @@ def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    check_resample_scheme(args)
-    if (args.resample_scheme, args.resample_ess, args.ttc_resample_every) != ('multinomial', None, 10):
-        check_resample_scheme(args, load_yaml(args.diffusion_config)['sampler'])
+    # the sampler's name decides what the resampling flags mean; without a config the checks that need no name still run
+    sampler_name = load_yaml(args.diffusion_config)['sampler'] if args.diffusion_config else None
+    resampling = (args.resample_scheme, args.resample_ess, args.ttc_resample_every) != ('multinomial', None, 10)
+    check_resample_scheme(args, sampler_name if resampling else None)
+    if smc_flags(args) or sampler_name == 'smc_ddpm':
+        check_smc(args, sampler_name, world)
     if args.beam_width != 1:
         check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
     if args.images_per_batch != 1:
@@ -266,6 +300,8 @@ def main(argv=None):
     sampler.resample_every = args.ttc_resample_every
     sampler.noise_draw = args.noise_draw
     sampler.beam_width = args.beam_width
+    for flag, value in smc_flags(args):          # check_smc: the sampler is smc_ddpm
+        setattr(sampler, flag[len("--smc_"):], value)
     sampler.noise_seed = args.seed or 0          # the same on every rank: the path id tells the ranks' particles apart
     groups = args.n_paths // args.batch_size
     if world > 1 and diffusion_config['sampler'] in ('search_ddpm', 'ttc_ddim'):

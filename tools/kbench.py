@@ -25,6 +25,11 @@ marked and its (c) is the front end's fallback, which is (b).
 N = 64 and 16, Gaussian / motion / SR x4 / inpainting, 3 x --reps repetitions alternated in one process.  Per launch: the
 step's time over its enqueued launches (5 + 5 iters - 1).  The vector side of one middle iteration (||t||^2, the d / r
 update, the p update: (9 + m / e) P by shape arithmetic) is priced as (t(5) - t(1)) / 4 - t(A) - t(A^T), beside K3's rate.
+    python tools/kbench.py --smc                                                      (the particle weights' launches, 256^2)
+--smc: K3 beside the launch that also sums the proposal correction, N = 64 and 16, Gaussian sigma = 3, 3 x --reps repetitions
+alternated in one process: (a) K3 alone (4 P by shape arithmetic), (b) kernels.step_update_corr with a noise pointer (6 P),
+(c) the same with rng= (5 P), (d) K3 + the correction as torch ops + a torch sum, and kernels.smc_accum alone.  Rates are
+against the bytes by shape arithmetic; (b) and (c) also as a fraction of K3's rate in the same run.
 """
 import argparse
 import os
@@ -50,7 +55,10 @@ def main():
     ap.add_argument("--resample", action="store_true", help="time the resampling step (multinomial / draw + gathers / fused)")
     ap.add_argument("--noise-draw", action="store_true", help="time the step noise: torch.randn / device fill / in-kernel draw")
     ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
+    ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
     args = ap.parse_args()
+    if args.smc:
+        return smc_step(args)
     if args.cg:
         return cg_step(args)
     if args.noise_draw:
@@ -256,6 +264,74 @@ def cg_step(args):
                   f"   vector side of one iteration {vec_us:7.1f} us = {vec_bytes / max(vec_us, 1e-3) / 1e3:7.1f} GB/s "
                   f"({9 + m_over_e:.2f} P/particle) = {vec_bytes / max(vec_us, 1e-3) / (k3_bytes / t['K3']):4.2f} x K3's rate",
                   flush=True)
+
+
+def smc_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    P = bench.P_BYTES
+    ratio, lo_log, hi_log = -float(ck.a) / float(ck.b), float(ck.min_log), float(ck.max_log)
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for n in (64, 16):
+        op, fkw = bench.build_operator("gaussian_blur", dev, sigma=args.sigma)
+        x_t, ring, truth, meas_noise = bench.synth_inputs(n, 2, dev, 1234)
+        yy = op.forward(truth.to(dev), **fkw).detach()
+        y = (yy + meas_noise.to(dev)[..., :yy.shape[-2], :yy.shape[-1]]).contiguous()
+        handle = op.hip_handle(x_t)
+        buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+        st = kernels.SmcState(n, (3, 256, 256), dev)
+        r0 = ring[0]
+        kernels.step_fwd(handle, buf, x_t, r0["model_out"], r0["noise"], y, ck, want_x0=False)     # sample, g_model_out
+        kernels.step_bwd(handle, buf, y, 0.3, 1, ck)
+        rng = kernels.Rng(7, 500)
+
+        def torch_ops(i):
+            r = ring[i % 2]
+            kernels.step_update(buf, r["g_unet"], ck)
+            s = ratio * buf.g_model_out[:, :3] + r["g_unet"]
+            frac = (r["model_out"][:, 3:] + 1.0) * 0.5
+            q = s / torch.exp(0.5 * (frac * hi_log + (1.0 - frac) * lo_log))
+            return (q * (r["noise"] - 0.5 * q)).flatten(1).sum(dim=1)
+
+        forms = {"a K3": lambda i: kernels.step_update(buf, ring[i % 2]["g_unet"], ck),
+                 "b update_corr, noise pointer": lambda i: kernels.step_update_corr(
+                     buf, ring[i % 2]["g_unet"], ck, ring[i % 2]["model_out"], noise=ring[i % 2]["noise"], state=st),
+                 "c update_corr, rng": lambda i: kernels.step_update_corr(
+                     buf, ring[i % 2]["g_unet"], ck, ring[i % 2]["model_out"], rng=rng, state=st),
+                 "d K3 + torch ops + torch sum": torch_ops,
+                 "smc_accum": lambda i: kernels.smc_accum(st, buf.norm)}
+        nbytes = {"a K3": 4 * P * n, "b update_corr, noise pointer": 6 * P * n, "c update_corr, rng": 5 * P * n}
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for key, fn in forms.items():
+                res.setdefault(key, []).append(timed(fn))
+        k3 = nbytes["a K3"] / float(np.concatenate(res["a K3"]).mean())
+        for key in forms:
+            ts = np.concatenate(res[key])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[key])
+            rate = ""
+            if key in nbytes:
+                bps = nbytes[key] / ts.mean()
+                rate = f"  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = {bps / k3:4.2f} x K3's rate"
+            print(f"smc 256^2 N={n:2d} {key:30s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs}){rate}", flush=True)
+        del buf, st, handle, op
 
 
 def resample_step(args):
