@@ -6,6 +6,7 @@
         'ps' / 'ps_anneal' / 'mcg' / 'ps+'  -> (x_t_updated, norm, ...)  (:85-106, 206-232)
         'ps_semantic'                       -> (norm_grad, measurement_err, semantic_err)   (:190-195)
         'cg' (not in the reference)         -> (x_{t-1}, dist): needs coefs= from the loop, no autograd graph
+        'dsg' (not in the reference)        -> raises: it runs inside the fused step only (kernels.step_update_dsg)
 
 Called on tensors that came out of this package's p_sample (PosteriorStepFn) and
 operator.forward (OperatorFn), `torch.autograd.grad` walks:  UNet  <-  [HIP S1 VJP]
@@ -23,21 +24,29 @@ from .measurements import LinearOperator
 
 __CONDITIONING_METHOD__ = {}      # the reference's methods, under the reference's names
 __EXTENSION_METHOD__ = {}         # methods the reference does not have ('cg'): same lookup, their own table
+__FUSED_ONLY_METHOD__ = {}        # extensions that exist inside the fused step only ('dsg'): conditioning() raises
 
 
-def register_conditioning_method(name: str, extension: bool = False):
+def register_conditioning_method(name: str, extension: bool = False, fused_only: bool = False):
     """extension=True: a method that is not in the reference; it is found by get_conditioning_method like the others
-    and kept out of the table that mirrors the reference's registry"""
+    and kept out of the table that mirrors the reference's registry.
+    fused_only=True (extensions only): a method with no per-op form -- its conditioning() cannot be called, the sampling
+    loops run it through its fused_spec() -- listed apart from the extensions whose conditioning() a loop calls"""
+    if fused_only and not extension:
+        raise ValueError("fused_only is an option of extension methods: every method of the reference has a per-op form")
+
     def wrapper(cls):
-        if __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None):
+        if any(t.get(name, None) for t in (__CONDITIONING_METHOD__, __EXTENSION_METHOD__, __FUSED_ONLY_METHOD__)):
             raise NameError(f"Name {name} is already registered!")
-        (__EXTENSION_METHOD__ if extension else __CONDITIONING_METHOD__)[name] = cls
+        table = __FUSED_ONLY_METHOD__ if fused_only else (__EXTENSION_METHOD__ if extension else __CONDITIONING_METHOD__)
+        table[name] = cls
         return cls
     return wrapper
 
 
 def get_conditioning_method(name: str, operator, noiser, **kwargs):
-    cls = __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None)
+    cls = __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None) or \
+        __FUSED_ONLY_METHOD__.get(name, None)
     if cls is None:
         raise NameError(f"Name {name} is not defined!")
     return cls(operator=operator, noiser=noiser, **kwargs)
@@ -297,3 +306,30 @@ class ConjugateGradientConsistency(ConditioningMethod):
         else:
             handle = op.hip_handle(x_0_hat)
         return handle.cg_step(x_0_hat, x_t, measurement, self.rho(coefs.b), self.iters, coefs)
+
+
+@register_conditioning_method(name='dsg', extension=True, fused_only=True)
+class SphericalGaussianGuidance(ConditioningMethod):
+    """Spherical-Gaussian guidance (not in the reference; Yang et al. 2024, "Guidance with Spherical Gaussian Constraint
+    for Conditional Diffusion"): the DPS gradient's direction only.  x_{t-1} is put on the sphere of radius ||sigma_t||
+    around the model's mean, `guidance_rate` in [0, 1] of the way from the drawn noise direction to the steepest-descent
+    direction, so there is no step size to tune and DDIM at 50-100 steps with eta = 1 stays on the shell the model expects.
+    The same K1 / K2 / UNet-VJP launches as `ps`; kernels.step_update_dsg runs in K3's place."""
+    returns_gradient = False
+
+    def __init__(self, operator, noiser, **kwargs):
+        super().__init__(operator, noiser)
+        self.guidance_rate = float(kwargs.get('guidance_rate', 0.1))
+        if not 0.0 <= self.guidance_rate <= 1.0:          # NaN fails both comparisons
+            raise ValueError(f"dsg: guidance_rate must be in [0, 1] (got {kwargs.get('guidance_rate')!r})")
+        self.operator_name = operator.name
+
+    def fused_spec(self, **kwargs):
+        if self.noiser.__name__ != 'gaussian':
+            return None
+        # only the direction of the gradient is used: unit scale, first power
+        return {"scale": 1.0, "power": 1, "dsg": self.guidance_rate}
+
+    def conditioning(self, x_t, measurement, noisy_measurement=None, **kwargs):
+        raise NotImplementedError("dsg needs the step's sd and noise, which only the fused step has: it runs inside the "
+                                  "sampling loops (kernels.step_update_dsg), not through conditioning()")

@@ -759,6 +759,28 @@ int dpsx_smc_accum_f32(float *E, float *d_prev, const float *d_cur, const float 
                      (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ spherical-Gaussian guidance (dsg.hip)
+int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, const float *g_unet, const float *model_out,
+                             const float *noise, const dpsx_rng *rng_host, float guidance_rate, float *x_next, float *stats,
+                             int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream)
+{
+    if (!sample || !g_model_out || !x_next || !stats || !coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
+    if ((noise != nullptr) == (rng_host != nullptr)) return DPSX_EINVAL;         // exactly one noise source, whatever the step
+    if (coefs_host->b == 0.0f) return DPSX_EINVAL;
+    if (!(guidance_rate >= 0.0f && guidance_rate <= 1.0f)) return DPSX_EINVAL;   // NaN included
+    const int mode = coefs_host->add_noise;
+    if ((mode & 1) && (mode & 2) && !(coefs_host->min_log > 0.0f)) return DPSX_EINVAL;      // eta = 0: a sphere of radius 0
+    if ((mode & 1) && !(mode & 2) && !model_out) return DPSX_EINVAL;                       // sd comes from its variance half
+    RngK r{};
+    if (rng_host) {
+        int rc = to_rngk(rng_host, n, r);
+        if (rc != DPSX_OK) return rc;
+    }
+    if (n > 65535) return DPSX_EUNSUPPORTED;                       // particles are the grid's y dimension
+    return step_update_dsg(sample, g_model_out, g_unet, model_out, noise, rng_host != nullptr, r, guidance_rate, x_next,
+                           stats, n, chw, to_coefs(coefs_host), (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

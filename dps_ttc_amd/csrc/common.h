@@ -623,6 +623,12 @@ int step_update_corr(const float *sample, const float *g_mo, const float *g_unet
 int smc_accum(float *e, float *d_prev, const float *d_cur, const float *partials, int slots, const uint8_t *reset,
               int64_t segments, int64_t n, float twist_scale, int power, float proposal_weight, hipStream_t s);
 
+// dsg.hip: spherical-Gaussian guidance in K3's place, two launches (the expression is stated in dsg.hip's header)
+// stats [n, cg_slots(chw), 4]: the per-block partials of (S, Nn, C, R); the noise is z, or with use_rng the counters of r
+int step_update_dsg(const float *sample, const float *g_mo, const float *g_unet, const float *mo, const float *z,
+                    bool use_rng, const RngK &r, float rate, float *x_next, float *stats, int64_t n, int64_t chw,
+                    const Coefs &k, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op);
 void phase_destroy(dpsx_op *op);

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import kernels
-from .condition_methods import ConditioningMethod, ConjugateGradientConsistency
+from .condition_methods import ConditioningMethod, ConjugateGradientConsistency, SphericalGaussianGuidance
 from .diffstategrad_utils import apply_diffstategrad, compute_svd_and_adaptive_rank
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
@@ -55,15 +55,24 @@ def get_sampler(name: str):
 
 
 def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_type, dynamic_threshold,
-                   clip_denoised, rescale_timesteps, timestep_respacing=""):
+                   clip_denoised, rescale_timesteps, timestep_respacing="", eta=None):
+    """eta (not in the reference, whose DDIM loops never pass it): the DDIM samplers' `eta` attribute -- sigma's scale,
+    0 the deterministic sampler, 1 the DDPM-like one the `dsg` method wants; a sampler without that attribute refuses it"""
     cls = get_sampler(name=sampler)
     betas = get_named_beta_schedule(noise_schedule, steps)
     if not timestep_respacing:
         timestep_respacing = [steps]
-    return cls(use_timesteps=space_timesteps(steps, timestep_respacing), betas=betas,
-               model_mean_type=model_mean_type, model_var_type=model_var_type,
-               dynamic_threshold=dynamic_threshold, clip_denoised=clip_denoised,
-               rescale_timesteps=rescale_timesteps)
+    smp = cls(use_timesteps=space_timesteps(steps, timestep_respacing), betas=betas,
+              model_mean_type=model_mean_type, model_var_type=model_var_type,
+              dynamic_threshold=dynamic_threshold, clip_denoised=clip_denoised,
+              rescale_timesteps=rescale_timesteps)
+    if eta is not None:
+        if not isinstance(smp, DDIM):
+            raise ValueError(f"eta is an option of the ddim samplers (got sampler {sampler!r})")
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1] (got {eta!r})")
+        smp.eta = float(eta)
+    return smp
 
 
 # ------------------------------------------------------------------ schedules
@@ -323,6 +332,38 @@ class GaussianDiffusion:
             return None
         return method, kw, handle
 
+    def _check_dsg(self, measurement_cond_fn, x_start, plan=False):
+        """The `dsg` method runs only where every step of a loop is the fused step and adds noise: anything else is refused
+        here, from the host's knowledge alone, before the first step (and before the model or the device is asked for
+        anything).  plan: the loop's fusion plan once it has one (None: refused whatever the reason).
+        rng_parity needs no refusal: the fused step takes that path's host-drawn noise tensor, and the update reads the
+        same tensor."""
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if not isinstance(method, SphericalGaussianGuidance):
+            return
+        if isinstance(self, SMC_DDPM):
+            raise NotImplementedError("dsg under smc_ddpm is not supported: the weights' proposal correction assumes the "
+                                      "Gaussian-shift proposal x_next = sample - s, and dsg's x_next is a point on a sphere")
+        why = None
+        if not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
+            why = ("it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised posterior (a "
+                   "fixed-variance model has no fused step)")
+        elif method.fused_spec(**kw) is None:
+            why = f"it needs a Gaussian noiser (got {getattr(method.noiser, '__name__', method.noiser)!r})"
+        elif method.operator.name == 'inpainting' and kw.get('mask', None) is None:
+            why = "inpainting needs its mask bound to the conditioning function"
+        elif method.operator.name == 'inpainting' and (x_start.shape[-2] * x_start.shape[-1]) % 4:
+            why = (f"the fused inpainting step exists on the float4 grid only, H * W a multiple of 4 (got "
+                   f"{x_start.shape[-2]} x {x_start.shape[-1]})")
+        elif plan is None:
+            why = f"{type(method.operator).__name__} has no fused step at {tuple(x_start.shape)}"
+        if why is not None:
+            raise NotImplementedError("dsg has no fused plan here and runs nowhere else (the update needs the step's sd and "
+                                      f"noise, which only the fused step has): {why}")
+        if isinstance(self, DDIM) and not float(self.eta) > 0.0:
+            raise ValueError(f"dsg under {type(self).__name__} with eta = {self.eta}: the step adds no noise, the sphere "
+                             "has radius 0 and no guidance is possible (set eta > 0; eta = 1 is the method's setting)")
+
     def _buffers(self, handle, x):
         n, c, h, w = x.shape
         b = self._bufs
@@ -364,7 +405,10 @@ class GaussianDiffusion:
         if model_out.requires_grad:
             (g_unet,) = torch.autograd.grad(model_out, x_prev, grad_outputs=buf.g_model_out.to(model_out.dtype))
             g_unet = kernels.f32c(g_unet, "UNet VJP")
-        if corr_state is None:
+        if "dsg" in spec:                 # the point on the sphere in K3's place (refused with corr_state: _check_dsg)
+            x_next, _ = kernels.step_update_dsg(buf, g_unet, coefs, mo, spec["dsg"], noise=noise, rng=rng,
+                                                stats=buf.dsg_stats())
+        elif corr_state is None:
             x_next = kernels.step_update(buf, g_unet, coefs)
         else:
             x_next, _ = kernels.step_update_corr(buf, g_unet, coefs, mo, noise=noise, rng=rng, state=corr_state)
@@ -468,7 +512,10 @@ class GaussianDiffusion:
                     (g_unet,) = torch.autograd.grad(model_out, x_prev,
                                                     grad_outputs=pg.bufs[j].g_model_out.to(model_out.dtype))
                     g_unet = kernels.f32c(g_unet, "UNet VJP")
-                pg.step_update(j, g_unet, coefs)
+                if "dsg" in spec:
+                    pg.step_update_dsg(j, g_unet, coefs, mo, spec["dsg"], noise=noise, rng=rng)
+                else:
+                    pg.step_update(j, g_unet, coefs)
         self._step_semantic = sems if sems else None
         return pg.x_next(), pg.full.norm
 
@@ -502,9 +549,11 @@ class GaussianDiffusion:
     # -- the base loop (reference :175-303) -------------------------------------
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
+        self._check_dsg(measurement_cond_fn, img)
         kernels.require_cuda(img, "x_start")
         ttc_driver_call = 'operator' in kwargs      # sample_condition_batched_ttc.py:91-100
         plan = self._fusion_plan(measurement_cond_fn, img)
+        self._check_dsg(measurement_cond_fn, img, plan)
         cg = self._cg_plan(measurement_cond_fn)
         method, _ = self._unwrap_cond_fn(measurement_cond_fn)
         returns_gradient = True if method is None else method.returns_gradient
@@ -929,6 +978,7 @@ class TTC_DDIM(DDIM):
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
+        self._check_dsg(measurement_cond_fn, img)
         kernels.require_cuda(img, "x_start")
         draw = self._check_resample_draw(self.resample_draw)
         n = img.shape[0]
@@ -940,6 +990,7 @@ class TTC_DDIM(DDIM):
         # 'ps'-type methods run the three fused launches with the DDIM variant of S1; the rest (e.g. 'mcg', the
         # method whose two return values fit the reference loop's unpacking at :672) go through the per-op path
         plan = self._fusion_plan(measurement_cond_fn, img)
+        self._check_dsg(measurement_cond_fn, img, plan)
         cg = self._cg_plan(measurement_cond_fn)
         if segments > 1:
             if draw != "device":
@@ -1082,6 +1133,7 @@ class SMC_DDPM(DDPM):
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         scale, power, weight, every, scheme, ess = self._smc_options()
+        self._check_dsg(measurement_cond_fn, x_start)
         img = x_start.detach()
         n = img.shape[0]
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)

@@ -732,6 +732,14 @@ class StepBuffers:
         self.resid = torch.empty(max(int(rb), 256), dtype=torch.uint8, device=device)
         self.flip = 0
         self._noise = None
+        self._dsg_stats = None
+
+    def dsg_stats(self):
+        """[n, corr_slots, 4] partial sums of step_update_dsg, the buffers' own (allocated on first use)"""
+        if self._dsg_stats is None:
+            n, c, h, w = self.shape
+            self._dsg_stats = torch.empty((n, corr_slots(c * h * w), 4), dtype=torch.float32, device=self.sample.device)
+        return self._dsg_stats
 
     def noise_buffer(self):
         """[n, c, h, w] scratch that step_fwd(rng=) fills for operators without an in-kernel draw (allocated on first use)"""
@@ -911,6 +919,33 @@ def smc_accum(state, d_cur, reset=None, segments=1, twist_scale=0.01, power=1, p
     return state.E
 
 
+# ------------------------------------------------------------------ spherical-Gaussian guidance (include/dpsx.h)
+def step_update_dsg(buf, g_unet, coefs, model_out, guidance_rate, noise=None, rng=None, stats=None, stream=None):
+    """DSG in K3's place, two launches (dpsx_step_update_dsg_f32): -> (x_next, stats).  x_next lies on the sphere of radius
+    ||sd|| around the model's mean, between the drawn noise direction (guidance_rate = 0) and the steepest-descent direction
+    of s = (-a/b) g_eps + g_unet (guidance_rate = 1); stats [N, corr_slots, 4] (the given tensor, or a fresh one) holds the
+    per-block partials of (sum s^2, sum n^2, sum s n, sum sd^2).  model_out is the UNet output K1 read (its variance half
+    gives sd); the noise is K1's: noise= or the same rng=, exactly one of them."""
+    _noise_or_rng(noise, rng)
+    n, c, h, w = buf.shape
+    want = (n, corr_slots(c * h * w), 4)
+    if stats is None:
+        stats = torch.empty(want, dtype=torch.float32, device=buf.sample.device)
+    if tuple(stats.shape) != want or stats.dtype != torch.float32 or not stats.is_contiguous() or \
+            stats.device != buf.sample.device:
+        raise ValueError(f"stats must be a contiguous float32 {want} tensor on {buf.sample.device} for step buffers of "
+                         f"shape {buf.shape}")
+    if model_out is not None and (model_out.shape[0] != n or (n and model_out[0].numel() != 2 * c * h * w)):
+        raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of {buf.shape}")
+    out = buf.x_next[buf.flip]
+    buf.flip ^= 1
+    check(lib().dpsx_step_update_dsg_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise),
+                                         None if rng is None else byref(rng.rec()), float(guidance_rate), ptr(out),
+                                         ptr(stats), n, c * h * w, byref(coefs), _stream_arg(stream, buf.sample)),
+          "dpsx_step_update_dsg_f32")
+    return out, stats
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,
@@ -1019,6 +1054,14 @@ class ParticleGroups:
 
     def step_update(self, j, g_unet, coefs):
         return step_update(self.bufs[j], self._slice(j, g_unet), coefs, stream=self.streams[j])
+
+    def step_update_dsg(self, j, g_unet, coefs, model_out, guidance_rate, noise=None, rng=None):
+        """step_update_dsg for group j with the group's own stats buffer (bufs[j].dsg_stats()); noise / rng as in
+        step_fwd: the full batch's tensor or record"""
+        _noise_or_rng(noise, rng)
+        return step_update_dsg(self.bufs[j], self._slice(j, g_unet), coefs, self._slice(j, model_out), guidance_rate,
+                               noise=self._slice(j, noise), rng=None if rng is None else rng.offset(self.starts[j]),
+                               stats=self.bufs[j].dsg_stats(), stream=self.streams[j])
 
     def x_next(self):
         """[N, C, H, W]: the state the groups' last step_update calls wrote (all groups flip together)"""

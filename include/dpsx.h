@@ -474,6 +474,33 @@ int dpsx_smc_accum_f32(float *E, float *d_prev, const float *d_cur, const float 
                        const uint8_t *reset, int64_t segments, int64_t n,
                        float twist_scale, int power, float proposal_weight, void *stream);
 
+/* ---- spherical-Gaussian guidance (DSG: Yang et al. 2024, "Guidance with Spherical Gaussian Constraint for Conditional
+ * Diffusion"; not in the reference): K3's place -- the update of gaussian_diffusion.py:255 -- without a step size.  K1 built
+ * sample = mean + n, n = sd z (sd and z as in "particle weights" above), and s = (-a/b) g_eps + g_unet is the gradient K3
+ * would subtract (dpsx_step_update_f32's expression and roundings).  Only the direction of s is used: x_next is put on the
+ * sphere of radius r = ||sd|| around the mean, at m = n + g (d* - n) scaled back to the sphere, d* = -r s / ||s|| the
+ * steepest-descent point and g = guidance_rate in [0, 1].  Per particle, S = sum s^2, Nn = sum n^2, C = sum s n, R = sum sd^2:
+ *   r = sqrt(R) ;  mm = (1 - g)^2 Nn + g^2 R - 2 g (1 - g) r C / sqrt(S)                  (= ||m||^2)
+ *   alpha = r (1 - g) / sqrt(mm) ;  beta = r^2 g / (sqrt(mm) sqrt(S))
+ *   x_next = sample + (alpha - 1) n - beta s                                              (= mean + r m / ||m||)
+ * Two launches on `stream`, grid (slots, n) with slots = dpsx_corr_slots(chw): the first leaves the four sums as fp32
+ * per-block partials in stats [n, slots, 4] (order S, Nn, C, R; a fixed tree, no atomics, a slot count that depends on
+ * the particle size only); in the second every block adds its particle's partials in double in a fixed order, forms alpha
+ * and beta in double, rounds each to fp32 once and writes its range of x_next.  Every per-element operation is one fp32
+ * rounding; the exact expression is the header of csrc/dsg.hip.  g = 0 is the unconditional sample renormalised to r.
+ * A step without noise (bit 0 of add_noise clear: r = 0), a particle with S not > 0 (a zero gradient) or mm not > 0, NaN
+ * sums included: x_next = sample bit for bit.  A step without noise writes stats as zeros and reads neither model_out,
+ * noise nor the gradients.  A non-finite input reaches its own particle only.  x_next must not overlap an input.
+ * The noise is `noise` [n, chw] or the counters of rng_host exactly as dpsx_step_update_corr_f32 draws them -- exactly one
+ * of the two, whatever the step.
+ * DPSX_EINVAL: a null pointer, both or neither of noise / rng_host, b = 0, guidance_rate outside [0, 1] or not finite, a
+ * DDIM record with sigma <= 0 and bit 0 set, a bad rng record; DPSX_EUNSUPPORTED: n > 65535.  All of them return before
+ * anything is launched.  No allocation, no host read (graph-capturable). */
+int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, const float *g_unet /* nullable */,
+                             const float *model_out, const float *noise, const dpsx_rng *rng_host,
+                             float guidance_rate, float *x_next, float *stats /* [n, slots, 4] */,
+                             int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

@@ -131,6 +131,9 @@ def parse_args(argv=None):
     p.add_argument('--smc_proposal_weight', type=float, default=None,
                    help='smc_ddpm: the weight of the proposal correction log p_model - log q_guided (default 1: the exact '
                         'twisted-SMC weight; 0: the difference potential alone)')
+    p.add_argument('--dsg_guidance_rate', type=float, default=None,
+                   help='dsg: overrides the task config\'s guidance_rate in [0, 1] (0: the drawn noise direction, 1: the '
+                        'steepest-descent direction)')
     p.add_argument('--beam_width', type=int, default=1,
                    help='search_ddpm: keep this many best proposals per image and step instead of one (beam search); '
                         'must divide batch_size; one rank only')
@@ -217,6 +220,19 @@ def check_smc(args, sampler_name, world=1):
                              "over the whole particle set")
 
 
+def check_dsg(args, method_name):
+    """--dsg_guidance_rate: an option of conditioning method dsg; reject it for another method, and a value outside [0, 1],
+    before any GPU work (one-line message)"""
+    g = args.dsg_guidance_rate
+    if g is None:
+        return
+    if method_name != 'dsg':
+        raise SystemExit(f"--dsg_guidance_rate {g} is an option of conditioning method dsg (the task config names "
+                         f"{method_name})")
+    if not 0.0 <= g <= 1.0:
+        raise SystemExit(f"--dsg_guidance_rate must be in [0, 1] (got {g})")
+
+
 def check_beam_width(args, sampler_name, world):
     """--beam_width: reject what the beam loop does not support, before any GPU work (one-line message)"""
     b = args.beam_width
@@ -243,6 +259,8 @@ def main(argv=None):
     check_resample_scheme(args, sampler_name if resampling else None)
     if smc_flags(args) or sampler_name == 'smc_ddpm':
         check_smc(args, sampler_name, world)
+    if args.dsg_guidance_rate is not None:
+        check_dsg(args, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None)
     if args.beam_width != 1:
         check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
     if args.images_per_batch != 1:
@@ -282,6 +300,8 @@ def main(argv=None):
 
     cond_config = task_config['conditioning']
     cond_params = dict(cond_config['params'])
+    if args.dsg_guidance_rate is not None:       # check_dsg: the method is dsg
+        cond_params['guidance_rate'] = args.dsg_guidance_rate
     embedder = None
     if args.embedder is not None:
         import importlib
@@ -325,6 +345,8 @@ def main(argv=None):
         dir_name = f"{op_name}_noise_sigma_{sigma}_dps_anneal_amp_{args.anneal_amp}"
     elif cond_config['method'] == 'cg':
         dir_name = (f"{op_name}_noise_sigma_{sigma}_cg_rho_scale_{cond_method.rho_scale}_iters_{cond_method.iters}")
+    elif cond_config['method'] == 'dsg':
+        dir_name = f"{op_name}_noise_sigma_{sigma}_dsg_guidance_rate_{cond_method.guidance_rate}"
     else:
         dir_name = f"{op_name}_noise_sigma_{sigma}_dps_scale_{cond_config['params']['scale']}"
     out_path = os.path.join(args.save_dir, dir_name)

@@ -30,6 +30,11 @@ update, the p update: (9 + m / e) P by shape arithmetic) is priced as (t(5) - t(
 alternated in one process: (a) K3 alone (4 P by shape arithmetic), (b) kernels.step_update_corr with a noise pointer (6 P),
 (c) the same with rng= (5 P), (d) K3 + the correction as torch ops + a torch sum, and kernels.smc_accum alone.  Rates are
 against the bytes by shape arithmetic; (b) and (c) also as a fraction of K3's rate in the same run.
+    python tools/kbench.py --dsg                                                      (spherical-Gaussian guidance, 256^2)
+--dsg: K3 beside kernels.step_update_dsg's two launches, N = 64 and 16, Gaussian sigma = 3, 3 x --reps repetitions alternated
+in one process: (a) K3 alone (4 P), (b) step_update_corr with a noise pointer (6 P), (c) step_update_dsg with a noise pointer
+(stats 4 P + apply 6 P), (d) the same with rng= (3 P + 5 P).  Per form: the time as a multiple of K3's and the rate against
+the bytes by shape arithmetic as a fraction of K3's rate, all from the same run.
 """
 import argparse
 import os
@@ -56,7 +61,10 @@ def main():
     ap.add_argument("--noise-draw", action="store_true", help="time the step noise: torch.randn / device fill / in-kernel draw")
     ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
     ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
+    ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
     args = ap.parse_args()
+    if args.dsg:
+        return dsg_step(args)
     if args.smc:
         return smc_step(args)
     if args.cg:
@@ -331,6 +339,67 @@ def smc_step(args):
                 bps = nbytes[key] / ts.mean()
                 rate = f"  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = {bps / k3:4.2f} x K3's rate"
             print(f"smc 256^2 N={n:2d} {key:30s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs}){rate}", flush=True)
+        del buf, st, handle, op
+
+
+def dsg_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    P = bench.P_BYTES
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for n in (64, 16):
+        op, fkw = bench.build_operator("gaussian_blur", dev, sigma=args.sigma)
+        x_t, ring, truth, meas_noise = bench.synth_inputs(n, 2, dev, 1234)
+        yy = op.forward(truth.to(dev), **fkw).detach()
+        y = (yy + meas_noise.to(dev)[..., :yy.shape[-2], :yy.shape[-1]]).contiguous()
+        handle = op.hip_handle(x_t)
+        buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+        st = kernels.SmcState(n, (3, 256, 256), dev)
+        stats = buf.dsg_stats()
+        r0 = ring[0]
+        kernels.step_fwd(handle, buf, x_t, r0["model_out"], r0["noise"], y, ck, want_x0=False)     # sample, g_model_out
+        kernels.step_bwd(handle, buf, y, 1.0, 1, ck)
+        rng = kernels.Rng(7, 500)
+        forms = {"a K3": lambda i: kernels.step_update(buf, ring[i % 2]["g_unet"], ck),
+                 "b update_corr, noise pointer": lambda i: kernels.step_update_corr(
+                     buf, ring[i % 2]["g_unet"], ck, ring[i % 2]["model_out"], noise=ring[i % 2]["noise"], state=st),
+                 "c update_dsg, noise pointer": lambda i: kernels.step_update_dsg(
+                     buf, ring[i % 2]["g_unet"], ck, ring[i % 2]["model_out"], 0.1, noise=ring[i % 2]["noise"], stats=stats),
+                 "d update_dsg, rng": lambda i: kernels.step_update_dsg(
+                     buf, ring[i % 2]["g_unet"], ck, ring[i % 2]["model_out"], 0.1, rng=rng, stats=stats)}
+        # bytes by shape arithmetic: stats reads 4 P (3 P with rng), apply reads 5 P (4 P) and writes 1 P
+        nbytes = {"a K3": 4 * P * n, "b update_corr, noise pointer": 6 * P * n, "c update_dsg, noise pointer": 10 * P * n,
+                  "d update_dsg, rng": 8 * P * n}
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for key, fn in forms.items():
+                res.setdefault(key, []).append(timed(fn))
+        t_k3 = float(np.concatenate(res["a K3"]).mean())
+        k3 = nbytes["a K3"] / t_k3
+        for key in forms:
+            ts = np.concatenate(res[key])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[key])
+            bps = nbytes[key] / ts.mean()
+            print(f"dsg 256^2 N={n:2d} {key:30s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs})  "
+                  f"{ts.mean() / t_k3:4.2f} x K3's time  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = "
+                  f"{bps / k3:4.2f} x K3's rate", flush=True)
         del buf, st, handle, op
 
 
