@@ -726,22 +726,33 @@ int dpsx_step_update_f32(const float *sample, const float *g_model_out, const fl
 // ------------------------------------------------------------------ particle weights (smc.hip)
 int dpsx_corr_slots(int64_t chw) { return chw < 0 ? DPSX_EINVAL : cg_slots(chw); }
 
-int dpsx_step_update_corr_f32(const float *sample, const float *g_model_out, const float *g_unet, const float *model_out,
-                              const float *noise, const dpsx_rng *rng_host, float *x_next, float *corr_partials, int64_t n,
-                              int64_t chw, const dpsx_coefs *coefs_host, void *stream)
+// what the entry points in K3's place share: the argument checks and the launch form of the noise counters
+static int update_place_args(const float *sample, const float *g_model_out, const float *model_out, const float *noise,
+                             const dpsx_rng *rng_host, const float *x_next, int64_t n, int64_t chw,
+                             const dpsx_coefs *coefs_host, RngK &r)
 {
-    if (!sample || !g_model_out || !x_next || !corr_partials || !coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
+    if (!sample || !g_model_out || !x_next || !coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
     if ((noise != nullptr) == (rng_host != nullptr)) return DPSX_EINVAL;         // exactly one noise source, whatever the step
     if (coefs_host->b == 0.0f) return DPSX_EINVAL;
     const int mode = coefs_host->add_noise;
-    if ((mode & 1) && (mode & 2) && !(coefs_host->min_log > 0.0f)) return DPSX_EINVAL;      // eta = 0: no density to weigh
+    if ((mode & 1) && (mode & 2) && !(coefs_host->min_log > 0.0f)) return DPSX_EINVAL;      // eta = 0: sd = 0, no density, no sphere
     if ((mode & 1) && !(mode & 2) && !model_out) return DPSX_EINVAL;                       // sd comes from its variance half
-    RngK r{};
+    r = RngK{};
     if (rng_host) {
         int rc = to_rngk(rng_host, n, r);
         if (rc != DPSX_OK) return rc;
     }
-    if (n > 65535) return DPSX_EUNSUPPORTED;                       // particles are the grid's y dimension
+    return n > 65535 ? DPSX_EUNSUPPORTED : DPSX_OK;                // particles are the grid's y dimension
+}
+
+int dpsx_step_update_corr_f32(const float *sample, const float *g_model_out, const float *g_unet, const float *model_out,
+                              const float *noise, const dpsx_rng *rng_host, float *x_next, float *corr_partials, int64_t n,
+                              int64_t chw, const dpsx_coefs *coefs_host, void *stream)
+{
+    if (!corr_partials) return DPSX_EINVAL;
+    RngK r;
+    const int rc = update_place_args(sample, g_model_out, model_out, noise, rng_host, x_next, n, chw, coefs_host, r);
+    if (rc != DPSX_OK) return rc;
     return step_update_corr(sample, g_model_out, g_unet, model_out, noise, rng_host != nullptr, r, x_next, corr_partials, n,
                             chw, to_coefs(coefs_host), (hipStream_t)stream);
 }
@@ -764,19 +775,10 @@ int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, cons
                              const float *noise, const dpsx_rng *rng_host, float guidance_rate, float *x_next, float *stats,
                              int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream)
 {
-    if (!sample || !g_model_out || !x_next || !stats || !coefs_host || n < 0 || chw < 0) return DPSX_EINVAL;
-    if ((noise != nullptr) == (rng_host != nullptr)) return DPSX_EINVAL;         // exactly one noise source, whatever the step
-    if (coefs_host->b == 0.0f) return DPSX_EINVAL;
-    if (!(guidance_rate >= 0.0f && guidance_rate <= 1.0f)) return DPSX_EINVAL;   // NaN included
-    const int mode = coefs_host->add_noise;
-    if ((mode & 1) && (mode & 2) && !(coefs_host->min_log > 0.0f)) return DPSX_EINVAL;      // eta = 0: a sphere of radius 0
-    if ((mode & 1) && !(mode & 2) && !model_out) return DPSX_EINVAL;                       // sd comes from its variance half
-    RngK r{};
-    if (rng_host) {
-        int rc = to_rngk(rng_host, n, r);
-        if (rc != DPSX_OK) return rc;
-    }
-    if (n > 65535) return DPSX_EUNSUPPORTED;                       // particles are the grid's y dimension
+    if (!stats || !(guidance_rate >= 0.0f && guidance_rate <= 1.0f)) return DPSX_EINVAL;    // NaN included
+    RngK r;
+    const int rc = update_place_args(sample, g_model_out, model_out, noise, rng_host, x_next, n, chw, coefs_host, r);
+    if (rc != DPSX_OK) return rc;
     return step_update_dsg(sample, g_model_out, g_unet, model_out, noise, rng_host != nullptr, r, guidance_rate, x_next,
                            stats, n, chw, to_coefs(coefs_host), (hipStream_t)stream);
 }

@@ -7,104 +7,48 @@
 //                        or the same counter through rng_unit / rng_elem), so sample = mean + sd z is the sample K1 built.
 //   k_smc_accum          E += twist_scale (d_cur^p - d_prev^p) - proposal_weight corr;  d_prev = d_cur   (one wave per particle)
 //
-// The reduction is cg.hip's: grid (slots, n); block (q, p) owns a contiguous range of particle p and leaves ONE fp32 partial
-// (the fixed tree of block_sum) in slot q; slots = cg_slots(chw) depends on the particle size only, so a particle's partials
-// do not depend on the batch it runs in.  k_smc_accum adds a particle's slots in double with common.h's slots_sum.  No
-// atomics, no fences: the launch boundary orders the partials.  Everything a particle reads is its own, so a non-finite
-// value stays inside its particle.
-//
-// Units: 16 bytes per lane where the particle size is a multiple of 4 and the buffers are 16-byte aligned; otherwise the
-// scalar instantiation of the same body (chosen on the host).  A unit's loads are issued before its arithmetic (and before
+// The pass is particle_pass.h's: grid (slots, n), one fp32 partial per block (the fixed tree of block_sum) in slot q;
+// k_smc_accum adds a particle's slots in double with common.h's slots_sum.  The streams, their loader and s / sd are
+// particle_pass.h's update streams (dsg.hip reads the same).  A unit's loads are issued before its arithmetic (and before
 // the Philox rounds of the rng form); every input stream is read here for the last time of its step: non-temporal loads.
-#include "common.h"
+#include "particle_pass.h"
 
 namespace dpsx {
 
-namespace {
-
-constexpr int kSmcThreads = 256;
-
-typedef float smc_f4 __attribute__((ext_vector_type(4)));
-
-template <bool VEC> struct SmcUnit { typedef float T; static constexpr int W = 1; };
-template <> struct SmcUnit<true> { typedef smc_f4 T; static constexpr int W = 4; };
-
-template <class T> __device__ __forceinline__ T smc_ld_last(const float *p)
-{
-    return __builtin_nontemporal_load(reinterpret_cast<const T *>(p));
-}
-
-__device__ __forceinline__ float smc_lane(float v, int) { return v; }
-__device__ __forceinline__ float smc_lane(const smc_f4 &v, int j) { return v[j]; }
-__device__ __forceinline__ void smc_set(float &v, int, float x) { v = x; }
-__device__ __forceinline__ void smc_set(smc_f4 &v, int j, float x) { v[j] = x; }
-
-// the noise of unit u (VEC) / element u (scalar) of the particle with id pid: S1's draw (k_posterior_fwd and the fused K1s)
-template <bool VEC> __device__ __forceinline__ typename SmcUnit<VEC>::T smc_draw(const RngK &r, int64_t u, uint32_t pid)
-{
-    if constexpr (VEC) {
-        const float4 z = rng_unit(r, (uint32_t)u, pid);
-        return smc_f4{z.x, z.y, z.z, z.w};
-    } else {
-        return rng_elem(r, u, pid);
-    }
-}
-
-}  // namespace
-
-struct CorrArgs {
-    const float *sample, *g_mo, *gu, *mo, *z;
-    float *out, *part;
-    int64_t chw, per;       // per: work items (float4 units or elements) per block
-    float ratio;            // -a / b
-    Coefs k;
-    RngK rng;
-};
-
 template <bool VEC, bool RNG>
-__global__ __launch_bounds__(kSmcThreads) void k_step_update_corr(const CorrArgs a)
+__global__ __launch_bounds__(kPassThreads) void k_step_update_corr(const UpdateArgs a)
 {
-    using T = typename SmcUnit<VEC>::T;
-    constexpr int W = SmcUnit<VEC>::W;
-    __shared__ float red[kSmcThreads / kWave];
-    const int64_t p = blockIdx.y, base = p * a.chw, mbase = p * 2 * a.chw;
-    const int64_t units = a.chw / W, lo = (int64_t)blockIdx.x * a.per, hi = min(units, lo + a.per);
+    using T = typename Unit<VEC>::T;
+    constexpr int W = Unit<VEC>::W;
+    __shared__ float red[kPassThreads / kWave];
+    const int64_t p = blockIdx.y, base = p * a.chw;
+    const Range r = block_range(a.chw / W, a.per);
     const bool noisy = a.k.add_noise & 1, ddim = a.k.add_noise & 2;          // launch-uniform
-    const bool has_u = a.gu != nullptr, ld_v = noisy && !ddim, ld_z = noisy && !RNG;
     const uint32_t pid = RNG ? rng_particle(a.rng, (unsigned)p) : 0u;
-    int64_t u = lo + threadIdx.x;
-    T sv = T{}, gv = T{}, uv = T{}, vv = T{}, zv = T{};
-    auto load = [&](int64_t unit) {
-        const int64_t i = unit * W;
-        sv = smc_ld_last<T>(a.sample + base + i);
-        gv = smc_ld_last<T>(a.g_mo + mbase + i);
-        if (has_u) uv = smc_ld_last<T>(a.gu + base + i);
-        if (ld_v) vv = smc_ld_last<T>(a.mo + mbase + a.chw + i);
-        if (ld_z) zv = smc_ld_last<T>(a.z + base + i);
-    };
-    if (u < hi) load(u);
+    UpdateLoader<VEC, RNG, true, true> in(a, p, noisy, ddim);
+    int64_t u = r.lo + threadIdx.x;
+    if (u < r.hi) in.load(u);
     float acc = 0.0f;
-    while (u < hi) {
+    while (u < r.hi) {
         if constexpr (RNG)
-            if (noisy) zv = smc_draw<VEC>(a.rng, u, pid);
+            if (noisy) in.zv = draw<VEC>(a.rng, u, pid);
         T xn;
         float t[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) {
-            const float s = a.ratio * smc_lane(gv, j) + smc_lane(uv, j);       // k_step_update's expression
-            smc_set(xn, j, smc_lane(sv, j) - s);
+            const float s = update_s(lane(in.gv, j), lane(in.uv, j), a);
+            set(xn, j, lane(in.sv, j) - s);
             t[j] = 0.0f;
             if (noisy) {
-                const float sd = ddim ? a.k.min_log : __expf(__fmul_rn(0.5f, post_logvar(smc_lane(vv, j), a.k)));
-                const float q = __fdiv_rn(s, sd);
-                t[j] = __fmul_rn(q, __fsub_rn(smc_lane(zv, j), __fmul_rn(0.5f, q)));
+                const float q = __fdiv_rn(s, update_sd(lane(in.vv, j), ddim, a));
+                t[j] = __fmul_rn(q, __fsub_rn(lane(in.zv, j), __fmul_rn(0.5f, q)));
             }
         }
-        *reinterpret_cast<T *>(a.out + base + u * W) = xn;
+        st<T>(a.out + base + u * W, xn);
 #pragma unroll
         for (int j = 0; j < W; ++j) acc = __fadd_rn(acc, t[j]);
-        u += kSmcThreads;
-        if (u < hi) load(u);
+        u += kPassThreads;
+        if (u < r.hi) in.load(u);
     }
     const float sum = block_sum(acc, red);
     if (threadIdx.x == 0) a.part[p * gridDim.x + blockIdx.x] = noisy ? sum : 0.0f;
@@ -134,17 +78,11 @@ int step_update_corr(const float *sample, const float *g_mo, const float *g_unet
                      hipStream_t s)
 {
     if (n == 0 || chw == 0) return DPSX_OK;
-    const bool noisy = k.add_noise & 1;
-    const bool vec = chw % 4 == 0 && aligned16(sample) && aligned16(g_mo) && aligned16(g_unet) && aligned16(x_next) &&
-                     (!noisy || (aligned16(mo) && (use_rng || aligned16(z))));
-    const int64_t units = vec ? chw / 4 : chw, slots = cg_slots(chw);
-    CorrArgs a{sample, g_mo, g_unet, mo, z, x_next, partials, chw, (units + slots - 1) / slots, -k.a / k.b, k, r};
-    const dim3 grid((unsigned)slots, (unsigned)n);
-    if (vec && use_rng) k_step_update_corr<true, true><<<grid, kSmcThreads, 0, s>>>(a);
-    else if (vec) k_step_update_corr<true, false><<<grid, kSmcThreads, 0, s>>>(a);
-    else if (use_rng) k_step_update_corr<false, true><<<grid, kSmcThreads, 0, s>>>(a);
-    else k_step_update_corr<false, false><<<grid, kSmcThreads, 0, s>>>(a);
-    return check_launch();
+    const UpdatePass u = update_pass(sample, g_mo, g_unet, mo, z, use_rng, r, 0.0f, x_next, partials, n, chw, k);
+    return dispatch(u.vec, use_rng, [&](auto V, auto R) {
+        k_step_update_corr<V.value, R.value><<<u.grid, kPassThreads, 0, s>>>(u.a);
+        return check_launch();
+    });
 }
 
 int smc_accum(float *e, float *d_prev, const float *d_cur, const float *partials, int slots, const uint8_t *reset,

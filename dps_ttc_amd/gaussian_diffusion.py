@@ -371,14 +371,18 @@ class GaussianDiffusion:
             self._bufs = (handle, kernels.StepBuffers(handle, n, c, h, w, x.device))
         return self._bufs[1]
 
-    def dps_step(self, model, x_prev, idx, measurement, method, cond_kw, handle, noise=None, loop_kw=None,
-                 want_x0=False, rng=None, corr_state=None):
-        """One fused DPS step at loop index idx.  Returns (x_next, norm[N]) -- device tensors that live in the
-        sampler's persistent step buffers (valid until the next step; the loops clone what they hand out).
-        loop_kw: the keyword arguments the calling loop passes to measurement_cond_fn besides the tensors
-        (base loop: beta_scale, t -- reference :230-236; ttc_ddim: none -- :678-682).
-        corr_state (a kernels.SmcState; smc_ddpm): K3 is kernels.step_update_corr, which also leaves the step's proposal
-        correction in corr_state.corr_partials."""
+    def _step_spec(self, idx, method, cond_kw, loop_kw):
+        """the method's fused_spec at loop index idx.  loop_kw: the keyword arguments the calling loop passes to
+        measurement_cond_fn besides the tensors (base loop: beta_scale, t -- reference :230-236; ttc_ddim: none -- :678-682)"""
+        if loop_kw is None:
+            loop_kw = {'beta_scale': self.betas[idx], 't': idx / self.num_timesteps}
+        return method.fused_spec(**loop_kw, **cond_kw)
+
+    def _fused_step(self, model, x_prev, idx, y, spec, handle, buf, stream, noise, rng, want_x0, corr_state=None):
+        """The fused DPS step of one chain of particles -- model call, K1, [semantic term], K2, model VJP, K3 -- on `stream`
+        (None: torch's current stream).  x_prev, noise, y and rng are the chain's own (already sliced); -> (x_next, the
+        semantic term's distance or None).  K3 is kernels.step_update, step_update_dsg where the spec says "dsg" (refused
+        with corr_state: _check_dsg), or step_update_corr with corr_state."""
         x_prev = x_prev.detach().requires_grad_()
         with torch.enable_grad():
             model_out = self._call_model(model, x_prev, idx)
@@ -388,30 +392,38 @@ class GaussianDiffusion:
         coefs = self.sample_coefs(idx)
         if noise is None and rng is None:
             noise = self._randn(x_prev)
-        buf = self._buffers(handle, x_prev)
-        xp = kernels.f32c(x_prev.detach(), "x_t")
-        y = kernels.f32c(measurement, "measurement")
-        if loop_kw is None:
-            loop_kw = {'beta_scale': self.betas[idx], 't': idx / self.num_timesteps}
-        spec = method.fused_spec(**loop_kw, **cond_kw)
         # x0_hat is consumed inside K1 (A(x0_hat), the clamp gate): the image itself is written out only when something
         # reads it afterwards -- the semantic term's embedder, a progress snapshot (want_x0)
-        kernels.step_fwd(handle, buf, xp, mo, noise, y, coefs, want_x0=want_x0 or "semantic" in spec, rng=rng)
-        g_sem, self._step_semantic = None, None
+        kernels.step_fwd(handle, buf, kernels.f32c(x_prev.detach(), "x_t"), mo, noise, y, coefs,
+                         want_x0=want_x0 or "semantic" in spec, stream=stream, rng=rng)
+        g_sem = sem = None
         if "semantic" in spec:            # embedder forward + VJP on x0_hat (torch), between the two HIP halves
-            g_sem, self._step_semantic = spec["semantic"](buf.x0_hat)
-        kernels.step_bwd(handle, buf, y, spec["scale"], spec["power"], coefs, g_x0_extra=g_sem)
+            g_sem, sem = spec["semantic"](buf.x0_hat)
+        kernels.step_bwd(handle, buf, y, spec["scale"], spec["power"], coefs, g_x0_extra=g_sem, stream=stream)
         g_unet = None
         if model_out.requires_grad:
             (g_unet,) = torch.autograd.grad(model_out, x_prev, grad_outputs=buf.g_model_out.to(model_out.dtype))
             g_unet = kernels.f32c(g_unet, "UNet VJP")
-        if "dsg" in spec:                 # the point on the sphere in K3's place (refused with corr_state: _check_dsg)
+        if "dsg" in spec:                 # the point on the sphere in K3's place
             x_next, _ = kernels.step_update_dsg(buf, g_unet, coefs, mo, spec["dsg"], noise=noise, rng=rng,
-                                                stats=buf.dsg_stats())
+                                                stats=buf.dsg_stats(), stream=stream)
         elif corr_state is None:
-            x_next = kernels.step_update(buf, g_unet, coefs)
+            x_next = kernels.step_update(buf, g_unet, coefs, stream=stream)
         else:
-            x_next, _ = kernels.step_update_corr(buf, g_unet, coefs, mo, noise=noise, rng=rng, state=corr_state)
+            x_next, _ = kernels.step_update_corr(buf, g_unet, coefs, mo, noise=noise, rng=rng, state=corr_state,
+                                                 stream=stream)
+        return x_next, sem
+
+    def dps_step(self, model, x_prev, idx, measurement, method, cond_kw, handle, noise=None, loop_kw=None,
+                 want_x0=False, rng=None, corr_state=None):
+        """One fused DPS step at loop index idx.  Returns (x_next, norm[N]) -- device tensors that live in the
+        sampler's persistent step buffers (valid until the next step; the loops clone what they hand out).
+        loop_kw: see _step_spec.  corr_state (a kernels.SmcState; smc_ddpm): K3 is kernels.step_update_corr, which also
+        leaves the step's proposal correction in corr_state.corr_partials."""
+        buf = self._buffers(handle, x_prev)
+        x_next, self._step_semantic = self._fused_step(
+            model, x_prev, idx, kernels.f32c(measurement, "measurement"), self._step_spec(idx, method, cond_kw, loop_kw),
+            handle, buf, None, noise, rng, want_x0, corr_state)
         return x_next, buf.norm
 
     def _particle_group_set(self, method, cond_kw, x, images=None):
@@ -481,41 +493,25 @@ class GaussianDiffusion:
 
     def dps_step_grouped(self, model, img, idx, measurement, method, cond_kw, pg, noise, loop_kw=None, want_x0=False,
                          rng=None):
-        """dps_step over kernels.ParticleGroups: every group's whole step -- model call, K1, [semantic term], K2, model VJP,
-        K3 -- is enqueued on the group's own stream; nothing is joined between steps (group j's next step reads only what
-        group j wrote).  img, noise: full-batch tensors.  Returns (x_next [N, C, H, W], norm [N]) -- views of the group
-        set's full-batch buffers, valid on the CALLER's stream only after pg.join()."""
-        coefs = self.sample_coefs(idx)
+        """dps_step over kernels.ParticleGroups: every group's whole step (_fused_step) is enqueued on the group's own
+        stream; nothing is joined between steps (group j's next step reads only what group j wrote).  img, noise, rng: the
+        full batch's; measurement: contiguous fp32 and alive until pg.join() (the loops convert it once per trajectory).
+        Returns (x_next [N, C, H, W], norm [N]) -- views of the group set's full-batch buffers, valid on the CALLER's stream
+        only after pg.join()."""
         y = kernels.f32c(measurement, "measurement")
-        if loop_kw is None:
-            loop_kw = {'beta_scale': self.betas[idx], 't': idx / self.num_timesteps}
-        spec = method.fused_spec(**loop_kw, **cond_kw)
+        if y is not measurement and pg.record_streams:       # a direct caller's layout: the copy outlives the groups' work
+            for stream in pg.streams:
+                y.record_stream(stream)
+        spec = self._step_spec(idx, method, cond_kw, loop_kw)
         pg.fork()                 # the noise (and, on the first step, x_start) was produced on the caller's stream
         sems = []
         for j in range(len(pg)):
-            with torch.cuda.stream(pg.streams[j]):
-                x_prev = img[pg.slices[j]].detach().requires_grad_()
-                with torch.enable_grad():
-                    model_out = self._call_model(model, x_prev, idx)
-                mo = kernels.f32c(model_out.detach(), "model output")
-                if mo.shape[1] != 2 * x_prev.shape[1]:
-                    raise ValueError("the fused DPS step needs a learned-sigma model ([N, 2C, H, W] output)")
-                pg.step_fwd(j, kernels.f32c(x_prev.detach(), "x_t"), mo, noise, y, coefs,
-                            want_x0=want_x0 or "semantic" in spec, rng=rng)
-                g_sem = None
-                if "semantic" in spec:
-                    g_sem, sem = spec["semantic"](pg.bufs[j].x0_hat)
-                    sems.append(sem)
-                pg.step_bwd(j, y, spec["scale"], spec["power"], coefs, g_x0_extra=g_sem)
-                g_unet = None
-                if model_out.requires_grad:
-                    (g_unet,) = torch.autograd.grad(model_out, x_prev,
-                                                    grad_outputs=pg.bufs[j].g_model_out.to(model_out.dtype))
-                    g_unet = kernels.f32c(g_unet, "UNet VJP")
-                if "dsg" in spec:
-                    pg.step_update_dsg(j, g_unet, coefs, mo, spec["dsg"], noise=noise, rng=rng)
-                else:
-                    pg.step_update(j, g_unet, coefs)
+            handle, buf, stream, noise_j, y_j, rng_j = pg.group_args(j, noise, y, rng)
+            with torch.cuda.stream(stream):
+                _, sem = self._fused_step(model, img[pg.slices[j]], idx, y_j, spec, handle, buf, stream, noise_j, rng_j,
+                                          want_x0)
+            if sem is not None:
+                sems.append(sem)
         self._step_semantic = sems if sems else None
         return pg.x_next(), pg.full.norm
 
@@ -546,6 +542,20 @@ class GaussianDiffusion:
             return method.conditioning(x_t=sample, x_0_hat=x0_hat, measurement=kernels.f32c(measurement, "measurement"),
                                        coefs=coefs, **cond_kw)
 
+    def _loop_step(self, model, img, idx, y, images, plan, cg=None, pg=None, **step_kw):
+        """A loop's step where it is the `cg` step (cg given) or the fused step (plan; over the groups pg where given):
+        the step's noise -- the counters of _step_rng or, with noise_draw = 'torch', a draw for the whole batch -- then the
+        step.  y: the measurement, contiguous fp32 (converted once per trajectory).  -> (x_next, distance [N])"""
+        rng = self._step_rng(idx, img.shape[0], images)
+        noise = self._randn(img) if rng is None else None
+        if self.rng_parity:
+            self._randn(y, self.parity_measurement_stride)      # the reference's q_sample draw (:224, :668), result unused
+        if cg is not None:
+            return self.cg_step(model, img, idx, y, cg[0], cg[1], noise=noise, rng=rng)
+        if pg is not None:
+            return self.dps_step_grouped(model, img, idx, y, plan[0], plan[1], pg, noise, rng=rng, **step_kw)
+        return self.dps_step(model, img, idx, y, plan[0], plan[1], plan[2], noise=noise, rng=rng, **step_kw)
+
     # -- the base loop (reference :175-303) -------------------------------------
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         img = x_start.detach()
@@ -573,33 +583,23 @@ class GaussianDiffusion:
         if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
             pg = self._particle_group_set(plan[0], plan[1], img, images=images)
         self._step_rng(0, img.shape[0], images)       # validates noise_draw before the first step
+        # one conversion per trajectory, alive until the groups are joined (the per-op path takes `measurement` as given)
+        y = kernels.f32c(measurement, "measurement") if cg is not None or plan is not None else None
         for idx in steps:
             projecting = project and returns_gradient and period != 0 and idx % period == 0
-            rng = self._step_rng(idx, img.shape[0], images)
             if cg is not None:
-                noise = self._randn(img) if rng is None else None
-                if self.rng_parity:
-                    self._randn(measurement, self.parity_measurement_stride)      # the reference's q_sample draw (:224)
-                img, distance = self.cg_step(model, img, idx, measurement, cg[0], cg[1], noise=noise, rng=rng)
+                img, distance = self._loop_step(model, img, idx, y, images, plan, cg=cg)
             elif plan is not None and not projecting:
-                noise = self._randn(img) if rng is None else None
-                if self.rng_parity:
-                    # the reference's q_sample draw (:224), result unused by ps*
-                    self._randn(measurement, self.parity_measurement_stride)
                 snapshot = bool(record) and idx % 100 == 0
-                if pg is not None:
-                    img, distance = self.dps_step_grouped(model, img, idx, measurement, plan[0], plan[1], pg, noise,
-                                                          want_x0=snapshot, rng=rng)
-                    if snapshot:
-                        pg.join()
-                else:
-                    img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise,
-                                                  want_x0=snapshot, rng=rng)
+                img, distance = self._loop_step(model, img, idx, y, images, plan, pg=pg, want_x0=snapshot)
+                if snapshot and pg is not None:
+                    pg.join()
                 if self._step_semantic is not None:
                     semantic = self._step_semantic
             else:
                 img = img.detach().requires_grad_()
                 time = torch.tensor([idx], device=img.device)
+                rng = self._step_rng(idx, img.shape[0], images)
                 if rng is None:
                     out = self.p_sample(x=img, t=time, model=model)
                 else:                     # per-op step: the same counters, filled by the stand-alone launch
@@ -1007,22 +1007,16 @@ class TTC_DDIM(DDIM):
                 raise NotImplementedError(f"ttc_ddim: {e}") from None
         self._resample_segments = segments      # the images of this trajectory's particle set (_resample draws per image)
         self._step_rng(0, n, segments)    # validates noise_draw before the first step
+        y = kernels.f32c(measurement, "measurement") if cg is not None or plan is not None else None
         for idx in range(self.num_timesteps - 1, -1, -1):
-            rng = self._step_rng(idx, n, segments)
             if cg is not None:
-                noise = self._randn(img) if rng is None else None
-                if self.rng_parity:
-                    self._randn(measurement, self.parity_measurement_stride)      # q_sample's draw (:668)
-                img, distance = self.cg_step(model, img, idx, measurement, cg[0], cg[1], noise=noise, rng=rng)
+                img, distance = self._loop_step(model, img, idx, y, segments, plan, cg=cg)
             elif plan is not None:
-                noise = self._randn(img) if rng is None else None
-                if self.rng_parity:
-                    self._randn(measurement, self.parity_measurement_stride)      # q_sample's draw (:668)
                 # this loop passes no beta_scale / t to the conditioning method (:678-682): same on both routes
-                img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise,
-                                              loop_kw={}, rng=rng)
+                img, distance = self._loop_step(model, img, idx, y, segments, plan, loop_kw={})
             else:
                 img = img.detach().requires_grad_()
+                rng = self._step_rng(idx, n, segments)
                 out = self.p_sample(x=img, t=torch.tensor([idx], device=img.device), model=model,
                                     noise=None if rng is None else kernels.randn(img.shape, rng, img.device))
                 noisy_measurement = self.q_sample(measurement, t=idx)
@@ -1156,11 +1150,9 @@ class SMC_DDPM(DDPM):
         state = kernels.SmcState(n, img.shape[1:], img.device)
         reset, distance = None, None
         self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
+        y = kernels.f32c(measurement, "measurement")
         for idx in range(self.num_timesteps - 1, -1, -1):
-            rng = self._step_rng(idx, n, segments)
-            noise = self._randn(img) if rng is None else None
-            img, distance = self.dps_step(model, img, idx, measurement, plan[0], plan[1], plan[2], noise=noise, rng=rng,
-                                          corr_state=state)
+            img, distance = self._loop_step(model, img, idx, y, segments, plan, corr_state=state)
             kernels.smc_accum(state, distance, reset, segments, scale, power, weight)
             reset = None
             if idx % every == 0 and idx > 0:

@@ -880,24 +880,32 @@ class SmcState:
         self.corr_partials = torch.empty((self.n, self.slots), **f)
 
 
+def _update_place(buf, model_out, noise, rng):
+    """what the launches in K3's place share: exactly one noise source, model_out against the buffers' shape, the x_next
+    buffer of this step (the ping-pong flips) and the rng record's pointer -> (out, rng pointer or None)"""
+    _noise_or_rng(noise, rng)
+    n, c, h, w = buf.shape
+    if model_out is not None and (model_out.shape[0] != n or (n and model_out[0].numel() != 2 * c * h * w)):
+        raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of {buf.shape}")
+    out = buf.x_next[buf.flip]
+    buf.flip ^= 1
+    return out, None if rng is None else byref(rng.rec())
+
+
 def step_update_corr(buf, g_unet, coefs, model_out, noise=None, rng=None, state=None, stream=None):
     """K3 with the proposal correction's partial sums, one launch (dpsx_step_update_corr_f32): -> (x_next, corr_partials).
     x_next has step_update's bits; corr_partials [N, corr_slots] (state.corr_partials, or a fresh tensor) holds
     sum q (z - q / 2), q = s / sd, per block.  model_out is the UNet output K1 read (its variance half gives sd); the noise
     is K1's: noise= or the same rng=, exactly one of them."""
-    _noise_or_rng(noise, rng)
     n, c, h, w = buf.shape
     part = state.corr_partials if state is not None else \
         torch.empty((n, corr_slots(c * h * w)), dtype=torch.float32, device=buf.sample.device)
     if tuple(part.shape) != (n, corr_slots(c * h * w)):
         raise ValueError(f"SmcState of {tuple(part.shape)} partials for step buffers of shape {buf.shape}")
-    if model_out is not None and (model_out.shape[0] != n or (n and model_out[0].numel() != 2 * c * h * w)):
-        raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of {buf.shape}")
-    out = buf.x_next[buf.flip]
-    buf.flip ^= 1
-    check(lib().dpsx_step_update_corr_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise),
-                                          None if rng is None else byref(rng.rec()), ptr(out), ptr(part), n, c * h * w,
-                                          byref(coefs), _stream_arg(stream, buf.sample)), "dpsx_step_update_corr_f32")
+    out, rec = _update_place(buf, model_out, noise, rng)
+    check(lib().dpsx_step_update_corr_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise), rec,
+                                          ptr(out), ptr(part), n, c * h * w, byref(coefs), _stream_arg(stream, buf.sample)),
+          "dpsx_step_update_corr_f32")
     return out, part
 
 
@@ -926,7 +934,6 @@ def step_update_dsg(buf, g_unet, coefs, model_out, guidance_rate, noise=None, rn
     of s = (-a/b) g_eps + g_unet (guidance_rate = 1); stats [N, corr_slots, 4] (the given tensor, or a fresh one) holds the
     per-block partials of (sum s^2, sum n^2, sum s n, sum sd^2).  model_out is the UNet output K1 read (its variance half
     gives sd); the noise is K1's: noise= or the same rng=, exactly one of them."""
-    _noise_or_rng(noise, rng)
     n, c, h, w = buf.shape
     want = (n, corr_slots(c * h * w), 4)
     if stats is None:
@@ -935,14 +942,10 @@ def step_update_dsg(buf, g_unet, coefs, model_out, guidance_rate, noise=None, rn
             stats.device != buf.sample.device:
         raise ValueError(f"stats must be a contiguous float32 {want} tensor on {buf.sample.device} for step buffers of "
                          f"shape {buf.shape}")
-    if model_out is not None and (model_out.shape[0] != n or (n and model_out[0].numel() != 2 * c * h * w)):
-        raise ValueError(f"model_out {tuple(model_out.shape)} does not hold 2x the channels of {buf.shape}")
-    out = buf.x_next[buf.flip]
-    buf.flip ^= 1
-    check(lib().dpsx_step_update_dsg_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise),
-                                         None if rng is None else byref(rng.rec()), float(guidance_rate), ptr(out),
-                                         ptr(stats), n, c * h * w, byref(coefs), _stream_arg(stream, buf.sample)),
-          "dpsx_step_update_dsg_f32")
+    out, rec = _update_place(buf, model_out, noise, rng)
+    check(lib().dpsx_step_update_dsg_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(model_out), ptr(noise), rec,
+                                         float(guidance_rate), ptr(out), ptr(stats), n, c * h * w, byref(coefs),
+                                         _stream_arg(stream, buf.sample)), "dpsx_step_update_dsg_f32")
     return out, stats
 
 
@@ -1055,13 +1058,12 @@ class ParticleGroups:
     def step_update(self, j, g_unet, coefs):
         return step_update(self.bufs[j], self._slice(j, g_unet), coefs, stream=self.streams[j])
 
-    def step_update_dsg(self, j, g_unet, coefs, model_out, guidance_rate, noise=None, rng=None):
-        """step_update_dsg for group j with the group's own stats buffer (bufs[j].dsg_stats()); noise / rng as in
-        step_fwd: the full batch's tensor or record"""
-        _noise_or_rng(noise, rng)
-        return step_update_dsg(self.bufs[j], self._slice(j, g_unet), coefs, self._slice(j, model_out), guidance_rate,
-                               noise=self._slice(j, noise), rng=None if rng is None else rng.offset(self.starts[j]),
-                               stats=self.bufs[j].dsg_stats(), stream=self.streams[j])
+    def group_args(self, j, noise=None, y=None, rng=None):
+        """what a caller that enqueues group j's launches itself passes to step_fwd / step_bwd / step_update*:
+        -> (handle, buffers, stream, the group's noise rows, its measurement rows, the record offset to its first particle)
+        of the full batch's noise / y / rng (each may be None)"""
+        return (self.handles[j], self.bufs[j], self.streams[j], self._slice(j, noise),
+                None if y is None else self.y_rows(j, y), None if rng is None else rng.offset(self.starts[j]))
 
     def x_next(self):
         """[N, C, H, W]: the state the groups' last step_update calls wrote (all groups flip together)"""

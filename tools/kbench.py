@@ -263,10 +263,11 @@ def cg_step(args):
             vec_bytes = (9 + m_over_e) * P * n
             k3_bytes = bench.algo_p(name, x0_store=False)["algorithmic"]["upd"] * P * n
             tag = f"cg {name:16s} N={n:2d}"
-            print(f"{tag} ps step (K1+K2+K3) avg {t['ps']:8.1f} us  min {lo['ps']:8.1f}", flush=True)
+            runs = {key: " / ".join(f"{r.mean():.1f}" for r in v) for key, v in res.items()}
+            print(f"{tag} ps step (K1+K2+K3) avg {t['ps']:8.1f} us  min {lo['ps']:8.1f}  (runs {runs['ps']})", flush=True)
             for it, key in ((1, "cg1"), (5, "cg5")):
                 launches = 5 + 5 * it - 1
-                print(f"{tag} cg_step iters={it}     avg {t[key]:8.1f} us  min {lo[key]:8.1f}   {launches:2d} launches, "
+                print(f"{tag} cg_step iters={it}     avg {t[key]:8.1f} us  min {lo[key]:8.1f}  (runs {runs[key]})   {launches:2d} launches, "
                       f"{t[key] / launches:6.1f} us each   {t[key] / t['ps']:5.2f} x the ps step", flush=True)
             print(f"{tag} A {t['A']:7.1f} us  A^T {t['At']:7.1f} us  K3 {t['K3']:7.1f} us = {k3_bytes / t['K3'] / 1e3:7.1f} GB/s"
                   f"   vector side of one iteration {vec_us:7.1f} us = {vec_bytes / max(vec_us, 1e-3) / 1e3:7.1f} GB/s "

@@ -25,6 +25,7 @@ def main():
             m = re.search(r"\." + key + r":\s*(\S+)", blk)
             return m.group(1) if m else "?"
         name = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip()
+        name = name.replace("(anonymous namespace)::", "")       # cg.hip's and dsg.hip's kernels have internal linkage
         name = re.sub(r"\(.*", "", name).replace("void dpsx::", "")
         if re.search(flt, name):
             print("%-58s vgpr %4s spill %4s  sgpr %4s spill %4s  scratch %5s  lds %6s" % (
