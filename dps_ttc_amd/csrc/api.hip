@@ -1169,62 +1169,52 @@ int dpsx_replicate_f32(const float *src, const int64_t *idx_dev, float *dst, int
     return replicate_seg_f32(src, idx_dev, dst, n_out, n_out, n_src, chw, (hipStream_t)stream);     // one id for all rows
 }
 
-// shared argument checks of the two resampling entry points
-static int resample_args(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const int64_t *ids)
+// The four resampling entry points: !fused is the draw alone (src .. chw unused), opts == nullptr the plain form.  The checks
+// run in a fixed order (a call that is wrong in several ways keeps its code): the draw's arguments, the fused form's
+// gathers, then the scheme and the trigger.
+static int resample_entry(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, bool fused,
+                          const float *src, float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t n, int64_t chw,
+                          const ResampleOpts *opts, void *stream)
 {
     if (!d || !u || !ids || segments < 1 || k < 1 || !(inv_scale >= 0.0f) || inv_scale > 3.402823466e38f)
         return DPSX_EINVAL;
     if (k > kResampleMaxK || segments > (1 << 24)) return DPSX_EUNSUPPORTED;       // the CDF of a segment lives in 8 k bytes of LDS
-    return DPSX_OK;
+    if (fused) {
+        if (!src || !dst || !d_out || n != segments * k || chw < 1) return DPSX_EINVAL;
+        // the gather reads whole particles of src while other blocks write dst: no overlap of the two ranges, and the
+        // distances are read by every block while one of them writes d_out
+        const char *sb = reinterpret_cast<const char *>(src), *db = reinterpret_cast<const char *>(dst);
+        const int64_t bytes = n * chw * (int64_t)sizeof(float);
+        if (sb < db + bytes && db < sb + bytes) return DPSX_EINVAL;
+        if (d_out < d + n && d < d_out + n) return DPSX_EINVAL;
+        if (n > 65535) return DPSX_EUNSUPPORTED;                              // one grid row per destination particle
+    }
+    if (opts && !(opts->scheme >= DPSX_RESAMPLE_MULTINOMIAL && opts->scheme <= DPSX_RESAMPLE_SYSTEMATIC &&
+                  opts->ess_q16 >= 0 && opts->ess_q16 <= 65536))
+        return DPSX_EINVAL;
+    if (!fused) return resample_draw_seg(d, u, segments, k, inv_scale, ids, q_out, opts, (hipStream_t)stream);
+    return resample_seg(d, u, segments, k, inv_scale, src, dst, d_out, ids, q_out, chw, opts, (hipStream_t)stream);
 }
 
 int dpsx_resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
                                int64_t *ids_out, int32_t *q_out, void *stream)
 {
-    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
-    if (rc != DPSX_OK) return rc;
-    return resample_draw_seg_f32(d, u, segments, k, inv_scale, ids_out, q_out, (hipStream_t)stream);
-}
-
-// ... and of the fused form's gathers
-static int resample_seg_args(const float *d, int64_t segments, int64_t k, const float *src, const float *dst,
-                             const float *d_out, int64_t n, int64_t chw)
-{
-    if (!src || !dst || !d_out || n != segments * k || chw < 1) return DPSX_EINVAL;
-    // the gather reads whole particles of src while other blocks write dst: no overlap of the two ranges, and the
-    // distances are read by every block while one of them writes d_out
-    const char *sb = reinterpret_cast<const char *>(src), *db = reinterpret_cast<const char *>(dst);
-    const int64_t bytes = n * chw * (int64_t)sizeof(float);
-    if (sb < db + bytes && db < sb + bytes) return DPSX_EINVAL;
-    if (d_out < d + n && d < d_out + n) return DPSX_EINVAL;
-    if (n > 65535) return DPSX_EUNSUPPORTED;                              // one grid row per destination particle
-    return DPSX_OK;
+    return resample_entry(d, u, segments, k, inv_scale, false, nullptr, nullptr, nullptr, ids_out, q_out, 0, 0, nullptr, stream);
 }
 
 int dpsx_resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
                           const float *src, float *dst, float *d_out, int64_t *ids_out, int32_t *q_out,
                           int64_t n, int64_t chw, void *stream)
 {
-    int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
-    if (rc == DPSX_OK) rc = resample_seg_args(d, segments, k, src, dst, d_out, n, chw);
-    if (rc != DPSX_OK) return rc;
-    return resample_seg_f32(d, u, segments, k, inv_scale, src, dst, d_out, ids_out, q_out, chw, (hipStream_t)stream);
-}
-
-static bool resample_scheme_ok(int scheme, int32_t ess_q16)
-{
-    return scheme >= DPSX_RESAMPLE_MULTINOMIAL && scheme <= DPSX_RESAMPLE_SYSTEMATIC && ess_q16 >= 0 && ess_q16 <= 65536;
+    return resample_entry(d, u, segments, k, inv_scale, true, src, dst, d_out, ids_out, q_out, n, chw, nullptr, stream);
 }
 
 int dpsx_resample_draw_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
                                   int64_t *ids_out, int32_t *q_out, int scheme, int32_t ess_q16,
                                   uint8_t *resampled_out, float *ess_out, void *stream)
 {
-    const int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
-    if (rc != DPSX_OK) return rc;
-    if (!resample_scheme_ok(scheme, ess_q16)) return DPSX_EINVAL;
-    return resample_draw_seg_ex_f32(d, u, segments, k, inv_scale, ids_out, q_out, scheme, ess_q16, resampled_out, ess_out,
-                                    (hipStream_t)stream);
+    const ResampleOpts opts{scheme, ess_q16, resampled_out, ess_out};
+    return resample_entry(d, u, segments, k, inv_scale, false, nullptr, nullptr, nullptr, ids_out, q_out, 0, 0, &opts, stream);
 }
 
 int dpsx_resample_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale,
@@ -1232,12 +1222,8 @@ int dpsx_resample_seg_ex_f32(const float *d, const float *u, int64_t segments, i
                              int64_t n, int64_t chw, int scheme, int32_t ess_q16, uint8_t *resampled_out,
                              float *ess_out, void *stream)
 {
-    int rc = resample_args(d, u, segments, k, inv_scale, ids_out);
-    if (rc == DPSX_OK) rc = resample_seg_args(d, segments, k, src, dst, d_out, n, chw);
-    if (rc != DPSX_OK) return rc;
-    if (!resample_scheme_ok(scheme, ess_q16)) return DPSX_EINVAL;
-    return resample_seg_ex_f32(d, u, segments, k, inv_scale, src, dst, d_out, ids_out, q_out, chw, scheme, ess_q16,
-                               resampled_out, ess_out, (hipStream_t)stream);
+    const ResampleOpts opts{scheme, ess_q16, resampled_out, ess_out};
+    return resample_entry(d, u, segments, k, inv_scale, true, src, dst, d_out, ids_out, q_out, n, chw, &opts, stream);
 }
 
 int dpsx_pack_champion_f32(const float *particles, const float *costs, const int64_t *best_idx_dev,

@@ -576,25 +576,29 @@ int plain_update(const float *sample, const float *ga, const float *gb, float *o
 int mask_step_fwd(const dpsx_op *op, const StepFwdArgs &a, int parts, hipStream_t s);
 int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s);
 int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw, hipStream_t s);
-// the per-segment resampling draw (include/dpsx.h): d, u [segments * k]; ids [segments * k] global particle indices,
-// q_out (nullable) the integer weights.  resample_seg_f32: the draw + dst[p] = src[ids[p]] + d_out[p] = d[ids[p]] in one
-// launch (chw >= 1, src and dst do not alias; the caller checked k <= 4096 and the grid limits)
-constexpr int kResampleMaxK = 4096;           // 8 B of LDS per particle of a segment: 32 KB
-int resample_draw_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, int64_t *ids,
-                          int32_t *q_out, hipStream_t s);
-int resample_seg_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
-                     float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, hipStream_t s);
-// the same two launches with a scheme (DPSX_RESAMPLE_*), the ESS trigger ess_q16 in [0, 65536] and the per-segment
-// diagnostics flag_out / ess_out [segments] (nullable); the caller checked scheme and ess_q16
-int resample_draw_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, int64_t *ids,
-                             int32_t *q_out, int scheme, int ess_q16, uint8_t *flag_out, float *ess_out, hipStream_t s);
-int resample_seg_ex_f32(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
-                        float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, int scheme, int ess_q16,
-                        uint8_t *flag_out, float *ess_out, hipStream_t s);
 int pack_champion(const float *particles, const float *costs, const int64_t *best, const float *val, float *out, int64_t n,
                   int64_t chw, hipStream_t s);
 int select_champion(const float *table, int world, int64_t chw, float *dst, int64_t n_out, int64_t *win_rank,
                     int64_t *win_local, hipStream_t s);
+
+// resample.hip: the per-segment resampling draw (include/dpsx.h): d, u [segments * k]; ids [segments * k] global
+// particle indices, q_out (nullable) the integer weights.  resample_seg: the draw + dst[p] = src[ids[p]] +
+// d_out[p] = d[ids[p]] in one launch (chw >= 1, src and dst do not alias; the caller checked k <= 4096 and the grid
+// limits).  opts == nullptr: the plain entry points' form (a flat segment keeps its particles, the others draw
+// multinomially); else the same launch with a scheme (DPSX_RESAMPLE_*), the ESS trigger ess_q16 in [0, 65536] and
+// the per-segment diagnostics flag_out / ess_out [segments] (nullable); the caller checked scheme and ess_q16
+constexpr int kResampleMaxK = 4096;           // 8 B of LDS per particle of a segment: 32 KB
+struct ResampleOpts {
+    int scheme;
+    int ess_q16;
+    uint8_t *flag_out;
+    float *ess_out;
+};
+int resample_draw_seg(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, int64_t *ids,
+                      int32_t *q_out, const ResampleOpts *opts, hipStream_t s);
+int resample_seg(const float *d, const float *u, int64_t segments, int64_t k, float inv_scale, const float *src,
+                 float *dst, float *d_out, int64_t *ids, int32_t *q_out, int64_t chw, const ResampleOpts *opts,
+                 hipStream_t s);
 
 // cg.hip: the vector launches of dpsx_cg_step_f32 (the recurrence is stated in include/dpsx.h).  Particles of e image
 // elements and m measurement elements; every sum of squares is left as cg_slots(size) fp32 partials per particle

@@ -236,6 +236,23 @@ class GaussianDiffusion:
                              f"(got {draw!r}): the schemes and the ESS trigger are the device draw's")
         return scheme, ess
 
+    def _device_resample(self, n, d, segments, inv_scale, opts, src=None):
+        """One resampling step of the device draw over d [n]: n uniforms (one per slot whatever the weights turn out to
+        be, so the stream position does not depend on data and nothing is read back), then kernels.resample_draw ->
+        ids, or with src kernels.resample (the draw and both gathers in one launch) -> (src[ids], d[ids], ids).
+        opts: (scheme, ess), or None for the plain entry points.  Records last_resample_ids / _flags / _ess (the
+        diagnostics are None without opts)."""
+        kw = {} if opts is None else dict(scheme=opts[0], ess=opts[1], want_flags=True)
+        u = self._rand(n, d)
+        if src is None:
+            out = kernels.resample_draw(d, u, segments, inv_scale, **kw)
+            out = (out,) if opts is None else out                       # the bare ids without diagnostics
+        else:
+            out = kernels.resample(src, d, u, segments, inv_scale, **kw)
+        out, diag = (out, (None, None)) if opts is None else (out[:-2], out[-2:])
+        self.last_resample_ids, (self.last_resample_flags, self.last_resample_ess) = out[-1], diag
+        return out[-1] if src is None else out
+
     @staticmethod
     def _check_noise_draw(value):
         if value not in ("torch", "device"):
@@ -914,16 +931,9 @@ class SearchDDPM(DDPM):
         opts = self._check_resample_scheme(draw, kwargs.get('resample_scheme', None), kwargs.get('resample_ess', None))
         if draw == "device":
             if resample and prev_costs is not None:
-                # one uniform per slot whatever the weights turn out to be (a flat segment keeps its particles: the
-                # draw's identity rule), so the stream position does not depend on data and nothing is read back
+                # a flat segment keeps its particles: the draw's identity rule
                 inv = rs_temp / steps_done if potential_type == 'mean' else rs_temp
-                if opts is None:
-                    ids = kernels.resample_draw(prev_costs, self._rand(n, prev_costs), segments, inv)
-                    self.last_resample_flags = self.last_resample_ess = None
-                else:
-                    ids, self.last_resample_flags, self.last_resample_ess = kernels.resample_draw(
-                        prev_costs, self._rand(n, prev_costs), segments, inv, scheme=opts[0], ess=opts[1], want_flags=True)
-                self.last_resample_ids = ids
+                ids = self._device_resample(n, prev_costs, segments, inv, opts)
                 candidates = kernels.gather(candidates, ids, validate=False)      # ids inside [0, n) by construction
                 denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
                 prev_costs = kernels.gather(prev_costs.reshape(n, 1), ids, validate=False).reshape(n)
@@ -1042,7 +1052,9 @@ class TTC_DDIM(DDIM):
 
     def _resample(self, img, distance, resample_scale):
         """the resampling block (:685-698): w = exp(-d / 100), multinomial with replacement, skipped when all
-        weights are equal.  The draw is torch.multinomial (RNG parity), the particle gather is HIP."""
+        weights are equal.  By default the draw is torch.multinomial (RNG parity) and the particle gather is HIP; with
+        resample_draw = "device" the draw and both gathers are one launch (_device_resample), and with global_resample
+        the ranks' exchange draws."""
         n = len(distance)
         if self.global_resample:
             from . import distributed as dd
@@ -1053,15 +1065,8 @@ class TTC_DDIM(DDIM):
         if self.resample_draw == "device":
             # one launch: per-image draw + both gathers.  img / distance are views of the persistent step buffers on the
             # fused route (the launch's src / d), the results are fresh tensors
-            if self._resample_opts is None:
-                img, distance, ids = kernels.resample(img, distance, self._rand(n, distance),
-                                                      self._resample_segments, 1.0 / resample_scale)
-            else:
-                img, distance, ids, self.last_resample_flags, self.last_resample_ess = kernels.resample(
-                    img, distance, self._rand(n, distance), self._resample_segments, 1.0 / resample_scale,
-                    scheme=self._resample_opts[0], ess=self._resample_opts[1], want_flags=True)
-            self.last_resample_ids = ids
-            return img, distance
+            return self._device_resample(n, distance, self._resample_segments, 1.0 / resample_scale, self._resample_opts,
+                                         src=img)[:2]
         if n <= 1:
             return img, distance
         weights = torch.exp(-distance / resample_scale)
@@ -1158,10 +1163,9 @@ class SMC_DDPM(DDPM):
             if idx % every == 0 and idx > 0:
                 # one launch: per-image draw on E + the particle gather; the flags reset the resampled images' weights in
                 # the next smc_accum, which also brings the increment still missing through the gathered d_prev
-                img, _, ids, reset, self.last_resample_ess = kernels.resample(
-                    img, state.E, self._rand(n, img), segments, 1.0, scheme=scheme, ess=ess, want_flags=True)
+                img, _, ids = self._device_resample(n, state.E, segments, 1.0, (scheme, ess), src=img)
+                reset = self.last_resample_flags
                 state.d_prev = kernels.gather(state.d_prev.reshape(n, 1), ids, validate=False).reshape(n)
-                self.last_resample_ids, self.last_resample_flags = ids, reset
         self.last_neg_log_weights = state.E
         self.last_measurement_distance = distance.clone()
         return img.clone(), distance.clone()

@@ -590,7 +590,8 @@ def replicate(src, idx_dev, n_out=None):
 
 
 def _resample_args(d, u, segments):
-    d, u = f32c(d.reshape(-1), "distances"), f32c(u.reshape(-1), "uniforms")
+    d = f32c(d if d.dim() == 1 else d.reshape(-1), "distances")
+    u = f32c(u if u.dim() == 1 else u.reshape(-1), "uniforms")
     segments = int(segments)
     n = d.numel()
     if segments < 1 or n == 0 or n % segments:
@@ -616,6 +617,42 @@ def resample_scheme_args(scheme, ess):
     return RESAMPLE_SCHEMES[scheme], int(tau * 65536.0 + 0.5)
 
 
+_RESAMPLE_SYMBOLS = (("dpsx_resample_draw_seg_ex_f32", "dpsx_resample_draw_seg_f32"),       # [fused][plain]
+                     ("dpsx_resample_seg_ex_f32", "dpsx_resample_seg_f32"))
+
+
+def _resample(src, d, u, segments, inv_scale, want_weights, scheme, ess, want_flags):
+    """The front end of resample_draw (src None) and resample (src contiguous fp32): argument checks, allocation, ONE
+    launch and the result tuple ([src[ids], d[ids],] ids[, q][, flags, ess]).  The defaults take the plain entry point,
+    anything else the scheme / ESS one."""
+    fused = src is not None
+    d, u, segments, n = _resample_args(d, u, segments)
+    if fused:
+        if src.dim() < 1 or src.shape[0] != n or src.device != d.device:
+            raise ValueError(f"{n} distances for particles of shape {tuple(src.shape)} on {src.device}")
+        chw = src.numel() // n                                      # n >= 1 particles of chw elements
+        if chw == 0:
+            raise ValueError("empty particles")
+    ids = torch.empty(n, dtype=torch.int64, device=d.device)
+    q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
+    plain = scheme == "multinomial" and ess is None and not want_flags
+    ex, flags, ess_out = (), None, None
+    if not plain:
+        sid, ess_q16 = resample_scheme_args(scheme, ess)
+        if want_flags:
+            flags = torch.empty(segments, dtype=torch.uint8, device=d.device)
+            ess_out = torch.empty(segments, dtype=torch.float32, device=d.device)
+        ex = (sid, ess_q16, ptr(flags), ptr(ess_out))
+    gather, size, out = (), (), (ids,)
+    if fused:
+        dst, d_out = torch.empty_like(src), torch.empty_like(d)
+        gather, size, out = (ptr(src), ptr(dst), ptr(d_out)), (n, chw), (dst, d_out, ids)
+    name = _RESAMPLE_SYMBOLS[fused][plain]
+    check(getattr(lib(), name)(ptr(d), ptr(u), segments, n // segments, float(inv_scale), *gather, ptr(ids), ptr(q), *size,
+                               *ex, stream_of(src if fused else d)), name)
+    return out + ((q,) if want_weights else ()) + ((flags, ess_out) if want_flags else ())
+
+
 def resample_draw(d, u, segments, inv_scale, want_weights=False, scheme="multinomial", ess=None, want_flags=False):
     """The resampling draw of include/dpsx.h per segment of K = N / segments particles: d [N] distances, u [N] uniforms in
     [0, 1) (one per output slot, e.g. torch.rand) -> ids [N] int64 global particle indices, each inside its own segment;
@@ -623,47 +660,14 @@ def resample_draw(d, u, segments, inv_scale, want_weights=False, scheme="multino
     scheme "stratified" / "systematic", ess (tau in [0, 1]: a segment resamples only while its effective sample size is
     below tau K, else it keeps its particles) or want_flags (also flags [segments] uint8, 1 where the segment resampled,
     and its ESS [segments] fp32) take the scheme / ESS entry point; the defaults take the plain one."""
-    d, u, segments, n = _resample_args(d, u, segments)
-    ids = torch.empty(n, dtype=torch.int64, device=d.device)
-    q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
-    if scheme == "multinomial" and ess is None and not want_flags:
-        check(lib().dpsx_resample_draw_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
-                                               stream_of(d)), "dpsx_resample_draw_seg_f32")
-        return (ids, q) if want_weights else ids
-    sid, ess_q16 = resample_scheme_args(scheme, ess)
-    flags = torch.empty(segments, dtype=torch.uint8, device=d.device) if want_flags else None
-    ess_out = torch.empty(segments, dtype=torch.float32, device=d.device) if want_flags else None
-    check(lib().dpsx_resample_draw_seg_ex_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(ids), ptr(q),
-                                              sid, ess_q16, ptr(flags), ptr(ess_out), stream_of(d)),
-          "dpsx_resample_draw_seg_ex_f32")
-    out = (ids,) + ((q,) if want_weights else ()) + ((flags, ess_out) if want_flags else ())
-    return out if len(out) > 1 else ids
+    out = _resample(None, d, u, segments, inv_scale, want_weights, scheme, ess, want_flags)
+    return out if len(out) > 1 else out[0]
 
 
 def resample(src, d, u, segments, inv_scale, want_weights=False, scheme="multinomial", ess=None, want_flags=False):
     """resample_draw fused with the gathers, ONE launch: -> (src[ids], d[ids], ids[, q][, flags, ess]) for src [N, ...]
     fp32.  The results are fresh tensors (the launch does not work in place); a segment that does not resample is copied."""
-    src = f32c(src, "particles")
-    d, u, segments, n = _resample_args(d, u, segments)
-    if src.dim() < 1 or src.shape[0] != n or src.device != d.device:
-        raise ValueError(f"{n} distances for particles of shape {tuple(src.shape)} on {src.device}")
-    if src[0].numel() == 0:
-        raise ValueError("empty particles")
-    dst, d_out = torch.empty_like(src), torch.empty_like(d)
-    ids = torch.empty(n, dtype=torch.int64, device=d.device)
-    q = torch.empty(n, dtype=torch.int32, device=d.device) if want_weights else None
-    if scheme == "multinomial" and ess is None and not want_flags:
-        check(lib().dpsx_resample_seg_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
-                                          ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), stream_of(src)),
-              "dpsx_resample_seg_f32")
-        return (dst, d_out, ids, q) if want_weights else (dst, d_out, ids)
-    sid, ess_q16 = resample_scheme_args(scheme, ess)
-    flags = torch.empty(segments, dtype=torch.uint8, device=d.device) if want_flags else None
-    ess_out = torch.empty(segments, dtype=torch.float32, device=d.device) if want_flags else None
-    check(lib().dpsx_resample_seg_ex_f32(ptr(d), ptr(u), segments, n // segments, float(inv_scale), ptr(src), ptr(dst),
-                                         ptr(d_out), ptr(ids), ptr(q), n, src[0].numel(), sid, ess_q16, ptr(flags),
-                                         ptr(ess_out), stream_of(src)), "dpsx_resample_seg_ex_f32")
-    return (dst, d_out, ids) + ((q,) if want_weights else ()) + ((flags, ess_out) if want_flags else ())
+    return _resample(f32c(src, "particles"), d, u, segments, inv_scale, want_weights, scheme, ess, want_flags)
 
 
 def pack_champion(particles, costs=None, best=None, best_val=None, out=None):
