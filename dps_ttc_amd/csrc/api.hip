@@ -783,6 +783,28 @@ int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, cons
                            stats, n, chw, to_coefs(coefs_host), (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ image metrics (metrics.hip)
+int64_t dpsx_metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w)
+{
+    if (n < 0 || m < 1 || n % m) return DPSX_EINVAL;
+    if (c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
+    if (n > 65535 || !metrics_shape_ok(c, h, w)) return DPSX_EUNSUPPORTED;
+    return metrics_workspace_bytes(n, m, c, h, w);
+}
+
+int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float data_range, float *mse, float *psnr,
+                           float *ssim, int64_t n, int64_t c, int64_t h, int64_t w, void *workspace,
+                           int64_t workspace_bytes, void *stream)
+{
+    if (!x || !label || !workspace || (!mse && !psnr && !ssim)) return DPSX_EINVAL;
+    if (n < 0 || m < 1 || n % m || c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
+    if (!(data_range >= 0.0f) || !std::isfinite(data_range)) return DPSX_EINVAL;           // NaN included
+    if (ssim && (h < 11 || w < 11)) return DPSX_EINVAL;
+    if (n > 65535 || !metrics_shape_ok(c, h, w)) return DPSX_EUNSUPPORTED;
+    if (workspace_bytes < metrics_workspace_bytes(n, m, c, h, w)) return DPSX_EWORKSPACE;
+    return image_metrics(x, label, m, data_range, mse, psnr, ssim, n, c, h, w, workspace, (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

@@ -633,6 +633,13 @@ int step_update_dsg(const float *sample, const float *g_mo, const float *g_unet,
                     bool use_rng, const RngK &r, float rate, float *x_next, float *stats, int64_t n, int64_t chw,
                     const Coefs &k, hipStream_t s);
 
+// metrics.hip: per-particle mse / psnr / ssim against the particle's label row (the definition is stated in include/dpsx.h);
+// the caller checked the arguments and the workspace size
+bool metrics_shape_ok(int64_t c, int64_t h, int64_t w);      // the index arithmetic fits
+int64_t metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w);
+int image_metrics(const float *x, const float *label, int64_t m, float data_range, float *mse, float *psnr, float *ssim,
+                  int64_t n, int64_t c, int64_t h, int64_t w, void *workspace, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op);
 void phase_destroy(dpsx_op *op);

@@ -193,6 +193,29 @@ class GaussianDiffusion:
         #: Groups exist only under a fused plan: the `cg` method has none and runs one chain whatever this says.
         self.particle_groups = 1
         self._pgroups = None
+        #: a kernels.MetricTrace: the fused base loop writes mse / psnr / ssim of x0_hat against the trace's label and the
+        #: step's distance into it every `every` steps (evaluation only; None: the loop launches what it always did)
+        self.metric_trace = None
+
+    def _check_metric_trace(self, plan=None, cg=None, projecting=False, base_loop=True):
+        """sampler.metric_trace runs in the fused branch of the base loop, one chain: anything else is refused before the
+        first step"""
+        if self.metric_trace is None:
+            return
+        why = None
+        if not base_loop:
+            why = f"sampler {type(self).__name__} has its own loop"
+        elif cg is not None:
+            why = "the cg step has no fused plan (x0_hat + d is its own quantity)"
+        elif plan is None:
+            why = "this sampler / conditioning method / shape has no fused plan (only the fused step leaves x0_hat in a buffer)"
+        elif projecting:
+            why = "a DiffStateGrad projection takes the per-op path on its steps"
+        elif self.particle_groups > 1:
+            why = f"particle_groups = {self.particle_groups} (the trace follows one chain)"
+        if why is not None:
+            raise NotImplementedError(f"metric_trace is an option of the fused base loop (ddpm / ddim, ps-type methods and "
+                                      f"dsg), one chain: {why}")
 
     # -- RNG ---------------------------------------------------------------
     def _randn(self, like, stride=None, shape=None):
@@ -596,6 +619,8 @@ class GaussianDiffusion:
         images = self._measurement_images(measurement, img.shape[0])
         if images is not None and cg is None:
             self._check_multi_image(plan, method, project and returns_gradient, images, img.shape[0])
+        self._check_metric_trace(plan, cg, project and returns_gradient)
+        trace = None if self.metric_trace is None else self.metric_trace.start(self.num_timesteps, img)
         pg = None
         if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
             pg = self._particle_group_set(plan[0], plan[1], img, images=images)
@@ -608,7 +633,10 @@ class GaussianDiffusion:
                 img, distance = self._loop_step(model, img, idx, y, images, plan, cg=cg)
             elif plan is not None and not projecting:
                 snapshot = bool(record) and idx % 100 == 0
-                img, distance = self._loop_step(model, img, idx, y, images, plan, pg=pg, want_x0=snapshot)
+                tracing = trace is not None and idx % trace.every == 0
+                img, distance = self._loop_step(model, img, idx, y, images, plan, pg=pg, want_x0=snapshot or tracing)
+                if tracing:               # one chain (_check_metric_trace): x0_hat and the distance are the step buffers'
+                    trace.record(idx, self._bufs[1].x0_hat, distance)
                 if snapshot and pg is not None:
                     pg.join()
                 if self._step_semantic is not None:
@@ -881,6 +909,7 @@ class SearchDDPM(DDPM):
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, operator,
                       potential_type='min', resample_every_steps=10, rs_temp=0.1, **kwargs):
+        self._check_metric_trace(base_loop=False)
         if self.beam_width != 1:
             return self._beam_loop(model, x_start, measurement, operator, **kwargs)
         img = x_start.detach()
@@ -987,6 +1016,7 @@ class TTC_DDIM(DDIM):
     _resample_opts = None
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
+        self._check_metric_trace(base_loop=False)
         img = x_start.detach()
         self._check_dsg(measurement_cond_fn, img)
         kernels.require_cuda(img, "x_start")
@@ -1131,6 +1161,7 @@ class SMC_DDPM(DDPM):
         return scale, int(self.twist_power), weight, every, self.resample_scheme, self.resample_ess
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
+        self._check_metric_trace(base_loop=False)
         scale, power, weight, every, scheme, ess = self._smc_options()
         self._check_dsg(measurement_cond_fn, x_start)
         img = x_start.detach()

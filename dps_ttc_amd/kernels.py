@@ -953,6 +953,93 @@ def step_update_dsg(buf, g_unet, coefs, model_out, guidance_rate, noise=None, rn
     return out, stats
 
 
+# ------------------------------------------------------------------ image metrics (include/dpsx.h: "reconstruction metrics")
+METRIC_NAMES = ("mse", "psnr", "ssim")
+_metrics_ws = {}         # (device, n, m, c, h, w) -> the call's workspace, as StepBuffers keeps its buffers per shape
+
+
+def _label_rows(label, x):
+    """label as [M, C, H, W] for particles x [N, C, H, W]: [C, H, W], [1, ...] or [M, ...] with M | N"""
+    label = f32c(label, "label")
+    if label.dim() == 3:
+        label = label.unsqueeze(0)
+    if label.dim() != 4 or tuple(label.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"label {tuple(label.shape)} does not match particles {tuple(x.shape)}")
+    if label.device != x.device:
+        raise ValueError(f"label on {label.device} for particles on {x.device}")
+    m = label.shape[0]
+    if m < 1 or x.shape[0] % m:
+        raise ValueError(f"{m} labels do not divide {x.shape[0]} particles")
+    return label
+
+
+def image_metrics(x, label, data_range=None, want=METRIC_NAMES, out=None, stream=None):
+    """Per-particle mse / psnr / ssim of x [N, C, H, W] against its label row, one device call (dpsx_image_metrics_f32):
+    -> {name: [N] float32 tensor} for the names in `want`.  label: [C, H, W], [1, ...] or [M, ...] with M | N, image-major
+    (particle p belongs to label p // (N // M)).  data_range None: each label's max - min, as metrics.compute_psnr.
+    out: a dict of preallocated contiguous float32 [N] tensors to write into (names missing from it are allocated).
+    No host read; the workspace is cached per shape and serves one stream at a time."""
+    want = tuple(want)
+    if not want or any(k not in METRIC_NAMES for k in want) or len(set(want)) != len(want):
+        raise ValueError(f"want must name some of {METRIC_NAMES} once each (got {want})")
+    x = f32c(x, "particles")
+    if x.dim() != 4:
+        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
+    label = _label_rows(label, x)
+    n, c, h, w = (int(v) for v in x.shape)
+    m = int(label.shape[0])
+    res = {}
+    for k in want:
+        t = out.get(k) if out is not None else None
+        if t is None:
+            t = torch.empty(n, dtype=torch.float32, device=x.device)
+        elif tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"out[{k!r}] must be a contiguous float32 [{n}] tensor on {x.device}")
+        res[k] = t
+    key = (x.device, n, m, c, h, w)
+    ws = _metrics_ws.get(key)
+    if ws is None:
+        need = lib().dpsx_metrics_workspace_bytes(n, m, c, h, w)
+        if need < 0:
+            check(int(need), "dpsx_metrics_workspace_bytes")
+        ws = _metrics_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    check(lib().dpsx_image_metrics_f32(ptr(x), ptr(label), m, 0.0 if data_range is None else float(data_range),
+                                       ptr(res.get("mse")), ptr(res.get("psnr")), ptr(res.get("ssim")), n, c, h, w,
+                                       ptr(ws), ws.numel(), _stream_arg(stream, x)), "dpsx_image_metrics_f32")
+    return res
+
+
+class MetricTrace:
+    """A per-step view of x0_hat's true quality beside the measurement distance the selects steer by, for the fused base
+    loop (sampler.metric_trace = MetricTrace(label, every=k)): on the steps with idx % every == 0 the loop has K1 write
+    x0_hat and calls record(), which puts image_metrics(x0_hat) and the step's distance into row idx // every of
+    `data` [rows, N, 4] (columns COLUMNS; rows of steps that did not run stay NaN).  One device call and one small
+    device copy per traced step, no host read; evaluation only -- the label never reaches the sampler's arithmetic."""
+
+    COLUMNS = ("mse", "psnr", "ssim", "distance")
+
+    def __init__(self, label, every=1, data_range=None):
+        if isinstance(every, bool) or int(every) != every or every < 1:
+            raise ValueError(f"every must be a positive integer (got {every!r})")
+        self.label, self.every, self.data_range = label, int(every), data_range
+        self.data = self._store = None
+
+    def start(self, num_steps, x):
+        """allocate `data` for a loop of num_steps steps over particles shaped like x (checks the label against them)"""
+        self.label = _label_rows(self.label, x)
+        rows = (int(num_steps) - 1) // self.every + 1
+        # stored [rows, 4, N] so that a row's columns are the call's contiguous [N] outputs; `data` is the [rows, N, 4] view
+        self._store = torch.full((rows, 4, x.shape[0]), float("nan"), dtype=torch.float32, device=x.device)
+        self.data = self._store.permute(0, 2, 1)
+        return self
+
+    def record(self, idx, x0_hat, distance, stream=None):
+        row = self._store[idx // self.every]
+        image_metrics(x0_hat, self.label, data_range=self.data_range, out={k: row[j] for j, k in enumerate(METRIC_NAMES)},
+                      stream=stream)
+        row[3].copy_(distance.reshape(-1))
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,

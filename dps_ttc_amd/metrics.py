@@ -1,6 +1,8 @@
 """Reconstruction metrics the driver logs.  PSNR as torchmetrics' PeakSignalNoiseRatio() computes it with its
-defaults (compute_metrics.py:77-90): data range = max(target) - min(target).  LPIPS / FID need downloaded networks
-and stay out of scope."""
+defaults (compute_metrics.py:77-90): data range = max(target) - min(target).  SSIM, the per-path vectors and the
+best-of-n curve (the prefix rule of best_of_n_simple.py:20-40) come from one device call (kernels.image_metrics).
+LPIPS / FID need downloaded networks and stay out of scope."""
+import numpy as np
 import torch
 
 
@@ -14,3 +16,41 @@ def compute_psnr(real_images, fake_images):
 def compute_psnr_manual(real_images, fake_images):
     mse = torch.mean((real_images - fake_images) ** 2)
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
+
+
+def compute_ssim(real_images, fake_images, data_range=None):
+    """Mean SSIM of fake_images [N, C, H, W] against real_images ([C, H, W], [1, ...] or [M, ...], M | N): the 11 x 11
+    Gaussian window (sigma 1.5), unpadded, C1 = (0.01 L)^2, C2 = (0.03 L)^2 -- skimage's and torchmetrics' convention;
+    data_range None: each label's max - min, as compute_psnr.  One device call (kernels.image_metrics); the per-path
+    values come from pathwise_metrics."""
+    from . import kernels
+    return kernels.image_metrics(fake_images, real_images, data_range=data_range, want=("ssim",))["ssim"].mean()
+
+
+def pathwise_metrics(refs, samples, n_images=1):
+    """The per-path metrics of samples [N, C, H, W] against refs [n_images, C, H, W] (image-major: path p belongs to
+    image p // (N // n_images)) -> {"mse", "psnr", "ssim"}: [N] device tensors.  One device call, no host read; psnr is
+    compute_psnr's definition per path."""
+    from . import kernels
+    if refs.dim() == 3:
+        refs = refs.unsqueeze(0)
+    if refs.shape[0] != n_images:
+        raise ValueError(f"{refs.shape[0]} reference images given for n_images = {n_images}")
+    return kernels.image_metrics(samples.detach(), refs)
+
+
+def best_of_n_curve(distances, metric):
+    """curve[n - 1] = metric[argmin(distances[:n])] for n = 1 .. len: the metric of the best-of-n pick over the first n
+    paths.  The pick is np.argmin's: a NaN distance first, then the smallest, the first index among equals -- the
+    library's select order."""
+    d, v = np.asarray(distances).reshape(-1), np.asarray(metric).reshape(-1)
+    if d.shape != v.shape:
+        raise ValueError(f"{d.size} distances for {v.size} metric values")
+    curve = np.empty_like(v)
+    best = 0
+    for n in range(d.size):
+        # the prefix's pick moves only when the new path comes strictly before the current one in the select's order
+        if not np.isnan(d[best]) and (np.isnan(d[n]) or d[n] < d[best]):
+            best = n
+        curve[n] = v[best]
+    return curve

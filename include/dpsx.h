@@ -501,6 +501,42 @@ int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, cons
                              float guidance_rate, float *x_next, float *stats /* [n, slots, 4] */,
                              int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream);
 
+/* ---- per-particle reconstruction metrics against the label, on the device: what compute_metrics.py:77-90 (PSNR with
+ * torchmetrics' default range) and the per-path loop feeding best_of_n_simple.py:20-40 compute on the host, plus SSIM
+ * (Wang et al. 2004, the convention skimage and torchmetrics share).  Evaluation only: nothing here steers a sampler.
+ *   x [n, c, h, w] particles, label [m, c, h, w], m | n, image-major: particle p belongs to image p / (n / m).
+ *   L_m    = data_range if data_range > 0, else max(label_m) - min(label_m) (one fp32 subtraction; NaN propagates as
+ *            torch's max / min do)
+ *   mse_p  = mean over c h w of (x - label)^2 ;  psnr_p = 10 log10(L^2 / mse_p), evaluated as written in IEEE arithmetic:
+ *            mse = 0 gives +inf, L = 0 gives -inf or NaN
+ *   ssim_p = mean of s over the c (h - 10) (w - 10) positions at which the 11 x 11 window lies inside the image (no
+ *            padding); window g_k ~ exp(-(k - 5)^2 / (2 1.5^2)), k = 0 .. 10, normalised to sum 1 (taps formed in double on
+ *            the host), separable; per position and channel, with E[.] the windowed mean:
+ *              mux = E[x], muy = E[y], vx = E[x^2] - mux^2, vy = E[y^2] - muy^2, cxy = E[xy] - mux muy   (biased, weighted)
+ *              C1 = (0.01 L)^2, C2 = (0.03 L)^2
+ *              s = (2 mux muy + C1) (2 cxy + C2) / ((mux^2 + muy^2 + C1) (vx + vy + C2))
+ * One linear chain of at most three launches on `stream`: the label range (only when data_range is 0 and psnr or ssim is
+ * asked for), the partial sums, the finisher.  With ssim the partial-sum launch runs one 32 x 32 tile of window positions
+ * of one plane per block (the five windowed moments in fp32, every tap an fmaf in tap order, horizontal then vertical);
+ * without it, a float4 stream over the particle (a scalar one when c h w is no multiple of 4 or a pointer is unaligned).
+ * Every block leaves one fp32 partial (each lane adds serially, then a fixed tree); the squared-error partials of the two
+ * forms are the same launch geometry and code, so mse and psnr of a call with ssim equal those of a call without, bit for
+ * bit.  The finisher (one wave per particle) adds a particle's partials in double in a fixed order, forms mse, psnr and
+ * ssim in double and rounds each to fp32 once.  No atomics, no fence, no allocation, no host read (graph-capturable).
+ * Slot counts and the tile grid depend on (c, h, w) only: a particle's three numbers depend on its own pixels, its label
+ * row, the shape and data_range -- not on n, m or its position in the batch.  A NaN in a particle reaches that particle's
+ * numbers only; a NaN in a label reaches the particles of its image only.
+ * mse, psnr, ssim: [n] each, each nullable, not all three.  The workspace (dpsx_metrics_workspace_bytes; it holds the
+ * partial sums) serves one stream at a time.
+ * DPSX_EINVAL: a null x, label or workspace; all three outputs null; m < 1 or m not dividing n; a size < 1; data_range
+ * negative or not finite; ssim requested with h < 11 or w < 11.  DPSX_EUNSUPPORTED: n > 65535 (or c h w >= 2^31).
+ * DPSX_EWORKSPACE: a short workspace.  All of them return before anything is launched. */
+int64_t dpsx_metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w);
+int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float data_range,
+                           float *mse, float *psnr, float *ssim,
+                           int64_t n, int64_t c, int64_t h, int64_t w,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

@@ -41,7 +41,7 @@ from dps_ttc_amd.data import get_dataloader, get_dataset, to_minus1_1  # noqa: E
 from dps_ttc_amd.gaussian_diffusion import create_sampler  # noqa: E402
 from dps_ttc_amd.img_utils import clear_color, mask_generator  # noqa: E402
 from dps_ttc_amd.measurements import get_noise, get_operator  # noqa: E402
-from dps_ttc_amd.metrics import compute_psnr  # noqa: E402
+from dps_ttc_amd.metrics import compute_psnr, pathwise_metrics  # noqa: E402
 from dps_ttc_amd.unet import create_model  # noqa: E402
 
 
@@ -137,7 +137,25 @@ def parse_args(argv=None):
     p.add_argument('--beam_width', type=int, default=1,
                    help='search_ddpm: keep this many best proposals per image and step instead of one (beam search); '
                         'must divide batch_size; one rank only')
-    return p.parse_args(argv)
+    p.add_argument('--path_metrics', type=str, default='torch', choices=('torch', 'device'),
+                   help='torch: PSNR per path in a host loop (one read per particle).  device: PSNR and SSIM of a particle '
+                        'group in one device call and one copy; also writes {fname}_pathwise_psnr.npy / _pathwise_ssim.npy '
+                        'and the best-of-n curves {fname}_best_of_n_psnr.npy / _best_of_n_ssim.npy; one rank only')
+    args = p.parse_args(argv)
+    if args.path_metrics == 'device' and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        raise SystemExit("--path_metrics device runs on one rank only: the per-path metric vectors are not gathered between "
+                         f"ranks (WORLD_SIZE={os.environ['WORLD_SIZE']})")
+    return args
+
+
+def save_path_metrics(out_path, fname, distances, psnr, ssim):
+    """--path_metrics device: the per-path metrics in the path order of {fname}_pathwise_distances.npy and the
+    best-of-n curves over that order"""
+    from dps_ttc_amd.metrics import best_of_n_curve
+    for name, v in (("psnr", psnr), ("ssim", ssim)):
+        v = np.asarray(v, dtype=np.float32)
+        np.save(os.path.join(out_path, f'{fname}_pathwise_{name}.npy'), v)
+        np.save(os.path.join(out_path, f'{fname}_best_of_n_{name}.npy'), best_of_n_curve(distances, v))
 
 
 def start_particles(args, sampler, g, shape, device, per_image=0):
@@ -408,6 +426,7 @@ def main(argv=None):
             imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(ref_img))
 
         distances, finals = [], []
+        device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
         for g in my_groups:
             x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
@@ -419,11 +438,20 @@ def main(argv=None):
                 dist_g = handle.score(sample, y_n)                             # ||y - A(x_p)||_2 per particle (HIP)
             distances.append(dist_g)
             finals.append(sample)
+            if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
+                pm = pathwise_metrics(ref_img, sample)
+                pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
+                path_psnr.append(pm_host[0])
+                path_ssim.append(pm_host[1])
             for i in range(len(sample)):
                 path_idx = args.path_start_idx + g * args.batch_size + i
-                psnr = compute_psnr(ref_img, sample[i].unsqueeze(0))
-                logger.info(f"Path#{path_idx + 1} | Method:{diffusion_config['sampler']} / PSNR: {float(psnr):.4f} / "
-                            f"distance: {float(dist_g[i]):.4f}")
+                if device_metrics:
+                    logger.info(f"Path#{path_idx + 1} | Method:{diffusion_config['sampler']} / PSNR: {pm_host[0, i]:.4f} / "
+                                f"SSIM: {pm_host[1, i]:.4f} / distance: {pm_host[2, i]:.4f}")
+                else:
+                    psnr = compute_psnr(ref_img, sample[i].unsqueeze(0))
+                    logger.info(f"Path#{path_idx + 1} | Method:{diffusion_config['sampler']} / PSNR: {float(psnr):.4f} / "
+                                f"distance: {float(dist_g[i]):.4f}")
                 imsave(os.path.join(out_path, 'recon_paths', fname, f'path#{path_idx + 1}.png'), clear_color(sample[i].unsqueeze(0)))
                 imsave(os.path.join(out_path, 'recon_paths_y', fname, f'path#{path_idx + 1}_y_space.png'),
                        clear_color(y_space[i].unsqueeze(0)))
@@ -437,6 +465,9 @@ def main(argv=None):
                         f"{float(compute_psnr(ref_img, winner)):.4f} | distance: {float(all_d[best]):.4f}")
             imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winner))
             np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), all_d.cpu().numpy())
+            if device_metrics:       # one rank (parse_args): the groups' order is the path order of all_d
+                save_path_metrics(out_path, fname, all_d.cpu().numpy(), np.concatenate(path_psnr),
+                                  np.concatenate(path_ssim))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -475,6 +506,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
         imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(refs[b:b + 1]))
 
     distances, finals = [], []
+    device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
     for g in range(groups):
         x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
@@ -486,12 +518,21 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
             dist_g = handle.score(sample, y)                          # ||y_{p // K} - A(x_p)||_2 per particle
         distances.append(dist_g)
         finals.append(sample)
+        if device_metrics:            # one device call and one copy for the group's B x K particles
+            pm = pathwise_metrics(refs, sample, n_images=B)
+            pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
+            path_psnr.append(pm_host[0].reshape(B, K))
+            path_ssim.append(pm_host[1].reshape(B, K))
         for b, fname in enumerate(fnames):
             for i in range(K):
                 p, path_idx = b * K + i, args.path_start_idx + g * K + i
-                psnr = compute_psnr(refs[b:b + 1], sample[p].unsqueeze(0))
-                logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {float(psnr):.4f} / "
-                            f"distance: {float(dist_g[p]):.4f}")
+                if device_metrics:
+                    logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {pm_host[0, p]:.4f} / "
+                                f"SSIM: {pm_host[1, p]:.4f} / distance: {pm_host[2, p]:.4f}")
+                else:
+                    psnr = compute_psnr(refs[b:b + 1], sample[p].unsqueeze(0))
+                    logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {float(psnr):.4f} / "
+                                f"distance: {float(dist_g[p]):.4f}")
                 imsave(os.path.join(out_path, 'recon_paths', fname, f'path#{path_idx + 1}.png'),
                        clear_color(sample[p].unsqueeze(0)))
                 imsave(os.path.join(out_path, 'recon_paths_y', fname, f'path#{path_idx + 1}_y_space.png'),
@@ -510,6 +551,9 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
                     f"{float(compute_psnr(refs[b:b + 1], winners[b:b + 1])):.4f} | distance: {float(d_host[b, k]):.4f}")
         imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winners[b:b + 1]))
         np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), d_host[b])
+        if device_metrics:       # [groups][B, K] -> image b's n_paths values in path order (group-major), as d_host[b]
+            save_path_metrics(out_path, fname, d_host[b], np.concatenate([v[b] for v in path_psnr]),
+                              np.concatenate([v[b] for v in path_ssim]))
 
 
 if __name__ == '__main__':

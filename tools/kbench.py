@@ -35,6 +35,11 @@ against the bytes by shape arithmetic; (b) and (c) also as a fraction of K3's ra
 in one process: (a) K3 alone (4 P), (b) step_update_corr with a noise pointer (6 P), (c) step_update_dsg with a noise pointer
 (stats 4 P + apply 6 P), (d) the same with rng= (3 P + 5 P).  Per form: the time as a multiple of K3's and the rate against
 the bytes by shape arithmetic as a fraction of K3's rate, all from the same run.
+    python tools/kbench.py --metrics                                                  (per-path PSNR / SSIM, 256^2)
+--metrics: the per-path metrics of [N, 3, 256, 256] particles, N = 64 with M = 1 and M = 4 labels and N = 512 with M = 1,
+3 x --reps repetitions alternated in one process: (a) the driver's per-particle metrics.compute_psnr loop with its host
+read (PSNR only), (b) PSNR and SSIM as batched torch ops (five depthwise conv2d with the 11 x 11 window, the elementwise map,
+the means), (c) kernels.image_metrics with all three outputs and its PSNR-only call.  (b) is the yardstick of (c).
 """
 import argparse
 import os
@@ -62,7 +67,10 @@ def main():
     ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
     ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
     ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
+    ap.add_argument("--metrics", action="store_true", help="time per-path PSNR / SSIM: host loop / torch ops / image_metrics")
     args = ap.parse_args()
+    if args.metrics:
+        return metrics_step(args)
     if args.dsg:
         return dsg_step(args)
     if args.smc:
@@ -402,6 +410,71 @@ def dsg_step(args):
                   f"{ts.mean() / t_k3:4.2f} x K3's time  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = "
                   f"{bps / k3:4.2f} x K3's rate", flush=True)
         del buf, st, handle, op
+
+
+def metrics_step(args):
+    from dps_ttc_amd import kernels, metrics
+    dev = torch.device("cuda", 0)
+    k = torch.arange(11, dtype=torch.float64) - 5
+    g = torch.exp(-(k * k) / (2 * 1.5 * 1.5))
+    g = (g / g.sum()).float().to(dev)
+    win = (g[:, None] * g[None, :]).expand(3, 1, 11, 11).contiguous()
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    def torch_ops(x, label, per):
+        """the same three numbers as batched torch ops (no host read)"""
+        y = label.repeat_interleave(per, dim=0)
+        flat = label.reshape(label.shape[0], -1)
+        L = (flat.max(dim=1).values - flat.min(dim=1).values).repeat_interleave(per)
+        mse = ((x - y) ** 2).reshape(x.shape[0], -1).mean(dim=1)
+        psnr = 10.0 * torch.log10(L * L / mse)
+        f = lambda a: torch.nn.functional.conv2d(a, win, groups=3)
+        mx, my = f(x), f(y)
+        vx, vy, cxy = f(x * x) - mx * mx, f(y * y) - my * my, f(x * y) - mx * my
+        c1, c2 = ((0.01 * L) ** 2)[:, None, None, None], ((0.03 * L) ** 2)[:, None, None, None]
+        s = (2 * mx * my + c1) * (2 * cxy + c2) / ((mx * mx + my * my + c1) * (vx + vy + c2))
+        return mse, psnr, s.reshape(x.shape[0], -1).mean(dim=1)
+
+    for n, m in ((64, 1), (64, 4), (512, 1)):
+        torch.manual_seed(n + m)
+        label = torch.rand(m, 3, 256, 256, device=dev) * 2 - 1
+        x = (label.repeat_interleave(n // m, dim=0) + 0.1 * torch.randn(n, 3, 256, 256, device=dev)).contiguous()
+        out = {name: torch.empty(n, dtype=torch.float32, device=dev) for name in kernels.METRIC_NAMES}
+        both = {name: out[name] for name in ("mse", "psnr")}
+
+        def host_loop(i):
+            for p in range(n):
+                float(metrics.compute_psnr(label[p // (n // m):p // (n // m) + 1], x[p].unsqueeze(0)))
+
+        forms = {"a compute_psnr loop, host reads (PSNR only)": host_loop,
+                 "b torch ops: 5 depthwise conv2d + map + means": lambda i: torch_ops(x, label, n // m),
+                 "c image_metrics, mse + psnr + ssim": lambda i: kernels.image_metrics(x, label, out=out),
+                 "c image_metrics, PSNR only": lambda i: kernels.image_metrics(x, label, want=("mse", "psnr"), out=both)}
+        ref, got = torch_ops(x, label, n // m), kernels.image_metrics(x, label)
+        agree = " ".join(f"{name} {float((got[name] - r).abs().max()):.1e}" for name, r in zip(kernels.METRIC_NAMES, ref))
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for key, fn in forms.items():
+                res.setdefault(key, []).append(timed(fn))
+        t_b = float(np.concatenate(res["b torch ops: 5 depthwise conv2d + map + means"]).mean())
+        for key in forms:
+            ts = np.concatenate(res[key])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[key])
+            print(f"metrics 256^2 N={n:3d} M={m} {key:46s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs})  "
+                  f"{ts.mean() / t_b:6.3f} x (b)'s time", flush=True)
+        print(f"metrics 256^2 N={n:3d} M={m} max |(c) - (b)|: {agree}", flush=True)
+        del x, label, out
 
 
 def resample_step(args):
