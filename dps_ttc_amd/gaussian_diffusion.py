@@ -23,6 +23,7 @@ import functools
 import math
 import os
 from operator import index as _index
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -119,6 +120,17 @@ def space_timesteps(num_timesteps, section_counts):
 
 
 # ------------------------------------------------------------------ base class
+class _Trajectory(NamedTuple):
+    """what GaussianDiffusion._trajectory settles for a guided loop before its first step"""
+    img: torch.Tensor                   # x_start, detached
+    n: int                              # its particles
+    method: object                      # the conditioning function's ConditioningMethod, or None
+    plan: Optional[tuple]               # _fusion_plan's (method, kw, handle)
+    cg: Optional[tuple]                 # _cg_plan's (method, kw)
+    images: Optional[int]               # the images of the batch (the base loop: None for one)
+    y: Optional[torch.Tensor]           # the measurement, contiguous fp32; None on the per-op route
+
+
 class GaussianDiffusion:
     def __init__(self, betas, model_mean_type, model_var_type, dynamic_threshold, clip_denoised,
                  rescale_timesteps):
@@ -328,7 +340,7 @@ class GaussianDiffusion:
         return {'mean': model_mean, 'variance': model_variance, 'log_variance': model_log_variance,
                 'pred_xstart': pred_xstart}
 
-    def p_sample(self, model, x, t):
+    def p_sample(self, model, x, t, noise=None):
         raise NotImplementedError
 
     def sample_coefs(self, idx):
@@ -351,21 +363,31 @@ class GaussianDiffusion:
             return method, kw
         return None, kw
 
-    def _fusion_plan(self, measurement_cond_fn, x_start):
+    def _no_plan_reason(self, method, kw):
+        """The fusion rule, as far as the host alone knows it: which condition of a fused step this sampler and
+        conditioning function (unwrapped: method, kw) miss -- "sampler", "method" or "mask" -- or None.  The shape is the
+        handle's to judge (OpHandle.fuses_step)."""
         if not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
-            return None
-        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+            return "sampler"            # another sampler, or a posterior the HIP S1 does not compute
         if method is None or method.fused_spec(**kw) is None:
+            return "method"             # not a ConditioningMethod's conditioning, or one without a fused form
+        if method.operator.name == 'inpainting' and kw.get('mask', None) is None:
+            return "mask"               # inpainting without its mask bound to the conditioning function
+        return None
+
+    @staticmethod
+    def _op_handle(operator, mask, like):
+        """the operator's HIP handle: inpainting's belongs to the mask, every other to the operator (and like's shape)"""
+        return operator.hip_handle_for(mask) if operator.name == 'inpainting' else operator.hip_handle(like)
+
+    def _fusion_plan(self, measurement_cond_fn, x_start):
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if self._no_plan_reason(method, kw) is not None:
             return None
         op = method.operator
-        if op.name == 'inpainting':
-            if kw.get('mask', None) is None:
-                return None
-            handle = op.hip_handle_for(kw['mask'])
-        elif hasattr(op, 'hip_handle'):
-            handle = op.hip_handle(x_start)
-        else:
+        if op.name != 'inpainting' and not hasattr(op, 'hip_handle'):
             return None
+        handle = self._op_handle(op, kw.get('mask', None), x_start)
         # a shape the fused launches refuse (inpainting with H * W off the float4 grid): decided here, before the first
         # step, so the loop -- and the particle groups, which exist only under a plan -- takes the per-op path
         if not handle.fuses_step(*x_start.shape[1:]):
@@ -384,18 +406,16 @@ class GaussianDiffusion:
         if isinstance(self, SMC_DDPM):
             raise NotImplementedError("dsg under smc_ddpm is not supported: the weights' proposal correction assumes the "
                                       "Gaussian-shift proposal x_next = sample - s, and dsg's x_next is a point on a sphere")
-        why = None
-        if not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
-            why = ("it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised posterior (a "
-                   "fixed-variance model has no fused step)")
-        elif method.fused_spec(**kw) is None:
-            why = f"it needs a Gaussian noiser (got {getattr(method.noiser, '__name__', method.noiser)!r})"
-        elif method.operator.name == 'inpainting' and kw.get('mask', None) is None:
-            why = "inpainting needs its mask bound to the conditioning function"
-        elif method.operator.name == 'inpainting' and (x_start.shape[-2] * x_start.shape[-1]) % 4:
+        why = {"sampler": "it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised posterior (a "
+                          "fixed-variance model has no fused step)",
+               "method": f"it needs a Gaussian noiser (got {getattr(method.noiser, '__name__', method.noiser)!r})",
+               "mask": "inpainting needs its mask bound to the conditioning function",
+               }.get(self._no_plan_reason(method, kw))
+        # the shape is the handle's to judge (plan is None); inpainting's rule is said here, while there is no handle yet
+        if why is None and method.operator.name == 'inpainting' and not kernels.OpHandle._mask_fuses(*x_start.shape[-2:]):
             why = (f"the fused inpainting step exists on the float4 grid only, H * W a multiple of 4 (got "
                    f"{x_start.shape[-2]} x {x_start.shape[-1]})")
-        elif plan is None:
+        if why is None and plan is None:
             why = f"{type(method.operator).__name__} has no fused step at {tuple(x_start.shape)}"
         if why is not None:
             raise NotImplementedError("dsg has no fused plan here and runs nowhere else (the update needs the step's sd and "
@@ -411,12 +431,16 @@ class GaussianDiffusion:
             self._bufs = (handle, kernels.StepBuffers(handle, n, c, h, w, x.device))
         return self._bufs[1]
 
-    def _step_spec(self, idx, method, cond_kw, loop_kw):
-        """the method's fused_spec at loop index idx.  loop_kw: the keyword arguments the calling loop passes to
-        measurement_cond_fn besides the tensors (base loop: beta_scale, t -- reference :230-236; ttc_ddim: none -- :678-682)"""
+    def _loop_kw(self, idx, loop_kw):
+        """the keyword arguments the calling loop passes to measurement_cond_fn besides the tensors (loop_kw=None, the base
+        loop: beta_scale, t -- reference :230-236; ttc_ddim: none, {} -- :678-682)"""
         if loop_kw is None:
-            loop_kw = {'beta_scale': self.betas[idx], 't': idx / self.num_timesteps}
-        return method.fused_spec(**loop_kw, **cond_kw)
+            return {'beta_scale': self.betas[idx], 't': idx / self.num_timesteps}
+        return loop_kw
+
+    def _step_spec(self, idx, method, cond_kw, loop_kw):
+        """the method's fused_spec at loop index idx.  loop_kw: see _loop_kw"""
+        return method.fused_spec(**self._loop_kw(idx, loop_kw), **cond_kw)
 
     def _fused_step(self, model, x_prev, idx, y, spec, handle, buf, stream, noise, rng, want_x0, corr_state=None):
         """The fused DPS step of one chain of particles -- model call, K1, [semantic term], K2, model VJP, K3 -- on `stream`
@@ -516,20 +540,21 @@ class GaussianDiffusion:
             raise ValueError(f"{n} particles do not split into {segments} images")
         return segments
 
-    def _check_multi_image(self, plan, method, projecting, images, n):
+    def _check_multi_image(self, plan, method, projecting, images, n, prefix=""):
         """a multi-image batch runs the fused ps / ps_anneal / ps_semantic-without-embedder step only (and `cg`, whose
-        loops do not come here: every launch of its step takes one measurement row and one mask per image)"""
+        loops do not come here: every launch of its step takes one measurement row and one mask per image).
+        prefix: what a sampler with a loop of its own puts in front of the refusal ("ttc_ddim: ")"""
         name = type(method).__name__ if method is not None else "this conditioning function"
         if plan is None or projecting:
             raise NotImplementedError(
-                f"multi-image batch ({images} measurements for {n} particles): {name} runs the per-op path, which takes "
-                "one measurement or one per particle; only the fused ps / ps_anneal / ps_semantic (no embedder) step "
+                f"{prefix}multi-image batch ({images} measurements for {n} particles): {name} runs the per-op path, which "
+                "takes one measurement or one per particle; only the fused ps / ps_anneal / ps_semantic (no embedder) step "
                 "and DiffStateGrad off support one measurement per image")
         last = self.num_timesteps - 1
         if "semantic" in plan[0].fused_spec(beta_scale=self.betas[last], t=last / self.num_timesteps, **plan[1]):
             raise NotImplementedError(
-                f"multi-image batch ({images} images): semantic guidance has one target for all particles; per-image "
-                "targets are not supported (set sem_guid_scale = 0 or run one image per call)")
+                f"{prefix}multi-image batch ({images} images): semantic guidance has one target for all particles; "
+                "per-image targets are not supported (set sem_guid_scale = 0 or run one image per call)")
 
     def dps_step_grouped(self, model, img, idx, measurement, method, cond_kw, pg, noise, loop_kw=None, want_x0=False,
                          rng=None):
@@ -561,7 +586,7 @@ class GaussianDiffusion:
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)
         if not isinstance(method, ConjugateGradientConsistency):
             return None
-        if not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
+        if self._no_plan_reason(method, kw) == "sampler":
             raise NotImplementedError("cg needs the epsilon / learned_range / clip_denoised posterior (the HIP S1) under a "
                                       "DDPM or DDIM sampler")
         return method, kw
@@ -596,39 +621,71 @@ class GaussianDiffusion:
             return self.dps_step_grouped(model, img, idx, y, plan[0], plan[1], pg, noise, rng=rng, **step_kw)
         return self.dps_step(model, img, idx, y, plan[0], plan[1], plan[2], noise=noise, rng=rng, **step_kw)
 
-    # -- the base loop (reference :175-303) -------------------------------------
-    def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
+    def _per_op_step(self, model, img, idx, measurement, measurement_cond_fn, images, loop_kw):
+        """A loop's step where it is neither of _loop_step's: p_sample with a graph back to x_t, the noisy measurement, and
+        the conditioning function as the reference calls it (loop_kw: see _loop_kw).  The noise is p_sample's own torch
+        draw or, with noise_draw = 'device', the same counters as the fused step's, filled by the stand-alone launch.
+        -> (p_sample's dict, what measurement_cond_fn returned)"""
+        img = img.detach().requires_grad_()
+        rng = self._step_rng(idx, img.shape[0], images)
+        out = self.p_sample(x=img, t=torch.tensor([idx], device=img.device), model=model,
+                            noise=None if rng is None else kernels.randn(img.shape, rng, img.device))
+        noisy_measurement = self.q_sample(measurement, t=idx)
+        return out, measurement_cond_fn(x_t=out['sample'], measurement=measurement, noisy_measurement=noisy_measurement,
+                                        x_prev=img, x_0_hat=out['pred_xstart'], **self._loop_kw(idx, loop_kw))
+
+    def _trajectory(self, x_start, measurement, measurement_cond_fn, n_images=False, refuse_multi=None, project=False,
+                    prefix=""):
+        """What a guided loop settles before its first step, refusals first: `dsg` from the host's knowledge alone, the
+        device, the fusion plan (and `dsg` again, now with it), the `cg` plan, the images of the batch and what a
+        multi-image batch can run, noise_draw, and the measurement converted once (alive until a loop's groups are joined;
+        None on the per-op route, which takes `measurement` as given).  The loop's policy:
+        n_images: False (the base loop) -- the images are the measurement's rows, None for one image; else the call's
+        n_images= for _segments (the resampling loops: always a count), with refuse_multi, why the call takes one image only;
+        project: a DiffStateGrad projection is asked for (its steps take the per-op path);
+        prefix: the sampler's name in front of a multi-image refusal."""
         img = x_start.detach()
+        n = img.shape[0]
         self._check_dsg(measurement_cond_fn, img)
         kernels.require_cuda(img, "x_start")
-        ttc_driver_call = 'operator' in kwargs      # sample_condition_batched_ttc.py:91-100
         plan = self._fusion_plan(measurement_cond_fn, img)
         self._check_dsg(measurement_cond_fn, img, plan)
         cg = self._cg_plan(measurement_cond_fn)
         method, _ = self._unwrap_cond_fn(measurement_cond_fn)
-        returns_gradient = True if method is None else method.returns_gradient
+        if n_images is False:
+            images = self._measurement_images(measurement, n)
+        else:
+            images = self._segments(measurement, n, n_images, refuse_multi=refuse_multi)
+        if (images or 1) > 1 and cg is None:
+            projecting = project and (method is None or method.returns_gradient)
+            self._check_multi_image(plan, method, projecting, images, n, prefix)
+        self._step_rng(0, n, images)      # validates noise_draw before the first step
+        y = kernels.f32c(measurement, "measurement") if cg is not None or plan is not None else None
+        return _Trajectory(img, n, method, plan, cg, images, y)
+
+    # -- the base loop (reference :175-303) -------------------------------------
+    def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
+        # DiffStateGrad (reference :203-204, 240-251): off by default; a projected step needs the gradient
+        # itself, so it takes the per-op path; every other step keeps the fused launches
+        period, project = kwargs.get('period', 20), kwargs.get('project', False)
+        tr = self._trajectory(x_start, measurement, measurement_cond_fn, project=project)
+        img, n, plan, cg, images, y = tr.img, tr.n, tr.plan, tr.cg, tr.images, tr.y
+        ttc_driver_call = 'operator' in kwargs      # sample_condition_batched_ttc.py:91-100
+        returns_gradient = True if tr.method is None else tr.method.returns_gradient
+        project = project and returns_gradient
         distance, semantic = None, torch.zeros((), device=img.device)
         steps = range(self.num_timesteps - 1, -1, -1)
         if self.progress:
             from tqdm.auto import tqdm
             steps = tqdm(list(steps))
-        # DiffStateGrad (reference :203-204, 240-251): off by default; a projected step needs the gradient
-        # itself, so it takes the per-op path; every other step keeps the fused launches
-        period, project = kwargs.get('period', 20), kwargs.get('project', False)
-        # particle groups on streams (sampler.particle_groups > 1): only where every step is a fused step
-        images = self._measurement_images(measurement, img.shape[0])
-        if images is not None and cg is None:
-            self._check_multi_image(plan, method, project and returns_gradient, images, img.shape[0])
-        self._check_metric_trace(plan, cg, project and returns_gradient)
+        self._check_metric_trace(plan, cg, project)
         trace = None if self.metric_trace is None else self.metric_trace.start(self.num_timesteps, img)
+        # particle groups on streams (sampler.particle_groups > 1): only where every step is a fused step
         pg = None
-        if plan is not None and self.particle_groups > 1 and img.shape[0] > 1 and not (project and returns_gradient):
+        if plan is not None and self.particle_groups > 1 and n > 1 and not project:
             pg = self._particle_group_set(plan[0], plan[1], img, images=images)
-        self._step_rng(0, img.shape[0], images)       # validates noise_draw before the first step
-        # one conversion per trajectory, alive until the groups are joined (the per-op path takes `measurement` as given)
-        y = kernels.f32c(measurement, "measurement") if cg is not None or plan is not None else None
         for idx in steps:
-            projecting = project and returns_gradient and period != 0 and idx % period == 0
+            projecting = project and period != 0 and idx % period == 0
             if cg is not None:
                 img, distance = self._loop_step(model, img, idx, y, images, plan, cg=cg)
             elif plan is not None and not projecting:
@@ -642,18 +699,7 @@ class GaussianDiffusion:
                 if self._step_semantic is not None:
                     semantic = self._step_semantic
             else:
-                img = img.detach().requires_grad_()
-                time = torch.tensor([idx], device=img.device)
-                rng = self._step_rng(idx, img.shape[0], images)
-                if rng is None:
-                    out = self.p_sample(x=img, t=time, model=model)
-                else:                     # per-op step: the same counters, filled by the stand-alone launch
-                    out = self.p_sample(x=img, t=time, model=model, noise=kernels.randn(img.shape, rng, img.device))
-                noisy_measurement = self.q_sample(measurement, t=idx)
-                ret = measurement_cond_fn(x_t=out['sample'], measurement=measurement,
-                                          noisy_measurement=noisy_measurement, x_prev=img,
-                                          x_0_hat=out['pred_xstart'], beta_scale=self.betas[idx],
-                                          t=idx / self.num_timesteps)
+                out, ret = self._per_op_step(model, img, idx, measurement, measurement_cond_fn, images, None)
                 if not isinstance(ret, tuple):
                     ret = (ret,)
                 if returns_gradient:
@@ -836,15 +882,21 @@ class SearchDDPM(DDPM):
             noise = self._randn(like, shape=None if like.shape[0] == n else (n,) + tuple(like.shape[1:]))
         return noise, rng
 
-    def search_step(self, model, img, idx, measurement, handle, noise=None, segments=None):
+    def _search(self, launch, model, states, proposals, idx, measurement, noise, segments, **kw):
+        """the body of the three steps below: the model on `states`, the noise source of the proposals, then `launch` (a
+        handle's search_step*: S1 -> scoring launch -> costs + select -> the winners' copy: one library call, nothing
+        leaves the device) -> its (winners, sample, costs, best, costs[best]), best kept in last_best"""
         with torch.no_grad():
-            model_out = self._call_model(model, img, idx)
-        noise, rng = self._proposal_noise(img, img.shape[0], idx, segments, noise)
-        # S1 -> scoring launch -> costs + select -> the winner's replication: one library call, nothing leaves the device
+            model_out = self._call_model(model, states, idx)
+        noise, rng = self._proposal_noise(states, proposals, idx, segments, noise)
+        out = launch(states, model_out, noise, measurement, self.step_coefs[idx], segments=segments, rng=rng, **kw)
+        self.last_best = out[3]
+        return out
+
+    def search_step(self, model, img, idx, measurement, handle, noise=None, segments=None):
         local = self.global_select is None
-        x_next, sample, costs, best, _ = handle.search_step(img, model_out, noise, measurement, self.step_coefs[idx],
-                                                            replicate=local, segments=segments, rng=rng)
-        self.last_best = best
+        x_next, sample, costs, _, _ = self._search(handle.search_step, model, img, img.shape[0], idx, measurement, noise,
+                                                   segments, replicate=local)
         if not local:
             return self.global_select(costs, sample), costs
         return x_next, costs
@@ -852,14 +904,10 @@ class SearchDDPM(DDPM):
     def search_step_one(self, model, state, n, idx, measurement, handle, noise=None, segments=None):
         """One step from the single state particle `state` [1,C,H,W] -> (winner [1,C,H,W], costs [n]).
         segments=M: one state per image, [M,C,H,W] -> (winners [M,C,H,W], costs [n])."""
-        with torch.no_grad():
-            model_out = self._call_model(model, state, idx)
-        noise, rng = self._proposal_noise(state, n, idx, segments, noise)
         local = self.global_select is None
-        winner, sample, costs, best, _ = handle.search_step_one(state, model_out, noise, measurement,
-                                                                self.step_coefs[idx], want_winner=local,
-                                                                segments=segments, rng=rng, n=n if rng is not None else None)
-        self.last_best = best
+        # n=: read with the in-launch draw only (a noise tensor brings its own count)
+        winner, sample, costs, _, _ = self._search(handle.search_step_one, model, state, n, idx, measurement, noise,
+                                                   segments, want_winner=local, n=n)
         if not local:
             winner = self.global_select(costs, sample, n_out=1)
         return winner, costs
@@ -867,12 +915,8 @@ class SearchDDPM(DDPM):
     def search_step_beam(self, model, states, n, idx, measurement, handle, noise=None, segments=None):
         """One beam step from `states` [S,C,H,W] (S = n on the first step, images * beam_width after it): n proposals,
         n / S per state -> (survivors [images * beam_width, C, H, W], costs [n], their costs [images * beam_width])."""
-        with torch.no_grad():
-            model_out = self._call_model(model, states, idx)
-        noise, rng = self._proposal_noise(states, n, idx, segments, noise)
-        winners, _, costs, best, val = handle.search_step_beam(states, model_out, noise, measurement, self.step_coefs[idx],
-                                                               n=n, beam=self.beam_width, segments=segments, rng=rng)
-        self.last_best = best
+        winners, _, costs, _, val = self._search(handle.search_step_beam, model, states, n, idx, measurement, noise,
+                                                 segments, n=n, beam=self.beam_width)
         return winners, costs, val
 
     def _beam_loop(self, model, x_start, measurement, operator, **kwargs):
@@ -891,8 +935,7 @@ class SearchDDPM(DDPM):
         kernels.require_cuda(img, "x_start")
         if not self.hip_posterior:
             raise NotImplementedError("search_ddpm runs the epsilon / learned_range / clip configuration")
-        mask = kwargs.get('mask', None)
-        handle = operator.hip_handle_for(mask) if operator.name == 'inpainting' else operator.hip_handle(img)
+        handle = self._op_handle(operator, kwargs.get('mask', None), img)
         self.best_paths, self.best_costs = [], []
         self._step_rng(0, n, segments)    # validates noise_draw before the first step
         state = img                       # the first step: n states, one proposal each; then [images * beam]
@@ -916,8 +959,7 @@ class SearchDDPM(DDPM):
         kernels.require_cuda(img, "x_start")
         if not self.hip_posterior:
             raise NotImplementedError("search_ddpm runs the epsilon / learned_range / clip configuration")
-        mask = kwargs.get('mask', None)
-        handle = operator.hip_handle_for(mask) if operator.name == 'inpainting' else operator.hip_handle(img)
+        handle = self._op_handle(operator, kwargs.get('mask', None), img)
         self.best_paths, self.best_costs = [], []
         n = img.shape[0]
         # n_images=M: M images x n / M particles (image-major), measurement [1 or M, ...]: every select is per image
@@ -958,14 +1000,11 @@ class SearchDDPM(DDPM):
             "resample_update over a multi-image batch is not supported: the multinomial draw would mix particles of "
             "different images (it needs a per-image RNG stream policy; resample_draw='device' draws per image)"))
         opts = self._check_resample_scheme(draw, kwargs.get('resample_scheme', None), kwargs.get('resample_ess', None))
-        if draw == "device":
-            if resample and prev_costs is not None:
-                # a flat segment keeps its particles: the draw's identity rule
-                inv = rs_temp / steps_done if potential_type == 'mean' else rs_temp
-                ids = self._device_resample(n, prev_costs, segments, inv, opts)
-                candidates = kernels.gather(candidates, ids, validate=False)      # ids inside [0, n) by construction
-                denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
-                prev_costs = kernels.gather(prev_costs.reshape(n, 1), ids, validate=False).reshape(n)
+        ids = None                        # stays None where nothing is drawn: the particles keep their places
+        if resample and prev_costs is not None and draw == "device":
+            # a flat segment keeps its particles: the draw's identity rule
+            inv = rs_temp / steps_done if potential_type == 'mean' else rs_temp
+            ids = self._device_resample(n, prev_costs, segments, inv, opts)
         elif resample and prev_costs is not None:
             pot = torch.exp(-rs_temp * prev_costs / steps_done) if potential_type == 'mean' \
                 else torch.exp(-rs_temp * prev_costs)
@@ -973,12 +1012,11 @@ class SearchDDPM(DDPM):
                 ids = torch.multinomial(pot.cpu(), n, replacement=True).to(pot.device) if self.rng_parity \
                     else torch.multinomial(pot, n, replacement=True)
                 self.last_resample_ids = ids
-                candidates = kernels.gather(candidates, ids, validate=False)      # ids drawn above over [0, n)
-                denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
-                prev_costs = kernels.gather(prev_costs.reshape(n, 1), ids, validate=False).reshape(n)
-        mask = kwargs.get('mask', None)
-        handle = operator.hip_handle_for(mask) if operator.name == 'inpainting' \
-            else operator.hip_handle(denoised_candidates)
+        if ids is not None:               # drawn over [0, n) either way: nothing to validate
+            candidates = kernels.gather(candidates, ids, validate=False)
+            denoised_candidates = kernels.gather(denoised_candidates, ids, validate=False)
+            prev_costs = kernels.gather(prev_costs.reshape(n, 1), ids, validate=False).reshape(n)
+        handle = self._op_handle(operator, kwargs.get('mask', None), denoised_candidates)
         self.last_curr_costs, net = handle.resample_cost(denoised_candidates, measurement, prev_costs, potential_type)
         return candidates, net
 
@@ -1017,37 +1055,25 @@ class TTC_DDIM(DDIM):
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         self._check_metric_trace(base_loop=False)
-        img = x_start.detach()
-        self._check_dsg(measurement_cond_fn, img)
-        kernels.require_cuda(img, "x_start")
         draw = self._check_resample_draw(self.resample_draw)
-        n = img.shape[0]
-        segments = self._segments(measurement, n, kwargs.get('n_images', None))
         resample_every_steps, resample_scale = self._check_resample_every(self.resample_every), 100
         self._resample_opts = self._check_resample_scheme(draw)
-        distance = None
-        self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
+        refuse_multi = None               # why this call's particles are one image's
+        if draw != "device":
+            refuse_multi = ("ttc_ddim over a multi-image batch is not supported: its resampling would mix particles of "
+                            "different images (it needs a per-image RNG stream policy: resample_draw = 'device' draws "
+                            "per image)")
+        elif self.global_resample:
+            refuse_multi = ("ttc_ddim over a multi-image batch with global (multi-rank) resampling is not supported: the "
+                            "exchange draws over all ranks' particles as one set")
         # 'ps'-type methods run the three fused launches with the DDIM variant of S1; the rest (e.g. 'mcg', the
         # method whose two return values fit the reference loop's unpacking at :672) go through the per-op path
-        plan = self._fusion_plan(measurement_cond_fn, img)
-        self._check_dsg(measurement_cond_fn, img, plan)
-        cg = self._cg_plan(measurement_cond_fn)
-        if segments > 1:
-            if draw != "device":
-                raise NotImplementedError("ttc_ddim over a multi-image batch is not supported: its resampling would mix "
-                                          "particles of different images (it needs a per-image RNG stream policy: "
-                                          "resample_draw = 'device' draws per image)")
-            if self.global_resample:
-                raise NotImplementedError("ttc_ddim over a multi-image batch with global (multi-rank) resampling is not "
-                                          "supported: the exchange draws over all ranks' particles as one set")
-            try:
-                if cg is None:
-                    self._check_multi_image(plan, self._unwrap_cond_fn(measurement_cond_fn)[0], False, segments, n)
-            except NotImplementedError as e:
-                raise NotImplementedError(f"ttc_ddim: {e}") from None
+        tr = self._trajectory(x_start, measurement, measurement_cond_fn, n_images=kwargs.get('n_images', None),
+                              refuse_multi=refuse_multi, prefix="ttc_ddim: ")
+        img, plan, cg, segments, y = tr.img, tr.plan, tr.cg, tr.images, tr.y
+        distance = None
+        self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
         self._resample_segments = segments      # the images of this trajectory's particle set (_resample draws per image)
-        self._step_rng(0, n, segments)    # validates noise_draw before the first step
-        y = kernels.f32c(measurement, "measurement") if cg is not None or plan is not None else None
         for idx in range(self.num_timesteps - 1, -1, -1):
             if cg is not None:
                 img, distance = self._loop_step(model, img, idx, y, segments, plan, cg=cg)
@@ -1055,14 +1081,7 @@ class TTC_DDIM(DDIM):
                 # this loop passes no beta_scale / t to the conditioning method (:678-682): same on both routes
                 img, distance = self._loop_step(model, img, idx, y, segments, plan, loop_kw={})
             else:
-                img = img.detach().requires_grad_()
-                rng = self._step_rng(idx, n, segments)
-                out = self.p_sample(x=img, t=torch.tensor([idx], device=img.device), model=model,
-                                    noise=None if rng is None else kernels.randn(img.shape, rng, img.device))
-                noisy_measurement = self.q_sample(measurement, t=idx)
-                ret = measurement_cond_fn(x_t=out['sample'], measurement=measurement,
-                                          noisy_measurement=noisy_measurement, x_prev=img,
-                                          x_0_hat=out['pred_xstart'])
+                _, ret = self._per_op_step(model, img, idx, measurement, measurement_cond_fn, segments, {})
                 img, distance = ret[0].detach(), ret[1].detach()
             if idx % resample_every_steps == 0:
                 img, distance = self._resample(img, distance, resample_scale)
@@ -1163,30 +1182,20 @@ class SMC_DDPM(DDPM):
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         self._check_metric_trace(base_loop=False)
         scale, power, weight, every, scheme, ess = self._smc_options()
-        self._check_dsg(measurement_cond_fn, x_start)
-        img = x_start.detach()
-        n = img.shape[0]
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)
-        if not self.hip_posterior or method is None or method.fused_spec(**kw) is None:
+        if self._no_plan_reason(method, kw) in ("sampler", "method"):
             name = type(method).__name__ if method is not None else "this conditioning function"
             raise NotImplementedError(f"smc_ddpm needs the fused ps / ps_anneal / ps_semantic step under the epsilon / "
                                       f"learned_range / clip_denoised posterior: {name} has no fused plan")
-        segments = self._segments(measurement, n, kwargs.get('n_images', None))
-        kernels.require_cuda(img, "x_start")
-        plan = self._fusion_plan(measurement_cond_fn, img)
-        if plan is None:
+        tr = self._trajectory(x_start, measurement, measurement_cond_fn, n_images=kwargs.get('n_images', None),
+                              prefix="smc_ddpm: ")
+        img, n, plan, segments, y = tr.img, tr.n, tr.plan, tr.images, tr.y
+        if plan is None:                  # the rest of the rule: inpainting's mask unbound, a shape the handle refuses
             raise NotImplementedError(f"smc_ddpm: {type(method).__name__} on {tuple(img.shape)} particles has no fused plan "
                                       "(the per-op path computes no proposal correction)")
-        if segments > 1:
-            try:
-                self._check_multi_image(plan, method, False, segments, n)
-            except NotImplementedError as e:
-                raise NotImplementedError(f"smc_ddpm: {e}") from None
-        self._step_rng(0, n, segments)    # validates noise_draw before the first step
         state = kernels.SmcState(n, img.shape[1:], img.device)
         reset, distance = None, None
         self.last_resample_ids = self.last_resample_flags = self.last_resample_ess = None
-        y = kernels.f32c(measurement, "measurement")
         for idx in range(self.num_timesteps - 1, -1, -1):
             img, distance = self._loop_step(model, img, idx, y, segments, plan, corr_state=state)
             kernels.smc_accum(state, distance, reset, segments, scale, power, weight)

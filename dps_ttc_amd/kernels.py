@@ -226,7 +226,12 @@ class OpHandle:
         torch allocated): the inpainting step exists in its float4 form only, H * W a multiple of 4; every other operator
         has a scalar form.  Where this is False the launches return DPSX_EUNSUPPORTED and the loops take the per-op path
         (GaussianDiffusion._fusion_plan asks before the first step)."""
-        return self.kind != _lib.KIND_MASK or (int(h) * int(w)) % 4 == 0
+        return self.kind != _lib.KIND_MASK or self._mask_fuses(h, w)
+
+    @staticmethod
+    def _mask_fuses(h, w):
+        """fuses_step's shape test for an inpainting handle, askable before there is a handle (or a device)"""
+        return (int(h) * int(w)) % 4 == 0
 
     def draws_in_kernel(self, c, h, w):
         """whether step_fwd(rng=) draws the noise inside this handle's K1 at [N, c, h, w] (dpsx_step_draws_in_kernel, for
