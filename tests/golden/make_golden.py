@@ -24,7 +24,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from standin import StandInModel, synthetic_motion_kernel  # noqa: E402
+from standin import StandInModel, rel_l2, synthetic_motion_kernel  # noqa: E402
 
 REF = "/root/reference"
 sys.dont_write_bytecode = True
@@ -303,6 +303,7 @@ def main():
     ddim_fixtures(GD, CM, MS)
     project_fixtures(GD, CM, MS)
     resample_fixtures(GD, CM, MS)
+    unet_fixtures(GD, CM, MS)
 
 
 def ddim_fixtures(GD, CM, MS):
@@ -458,8 +459,111 @@ def resample_fixtures(GD, CM, MS):
     save("resample.npz", **out)
 
 
+@contextlib.contextmanager
+def float64_twin(model):
+    """The reference's model in float64: `deepcopy(model).double()` with `dtype = float64`, and for the duration of the
+    block its two fp32 pins lifted -- GroupNorm32.forward becomes plain GroupNorm.forward, and the timestep embedding
+    is evaluated in double (frequencies, arguments, cos / sin).  The attention softmax the reference hard-casts to
+    fp32 (`weight.float()`) STAYS fp32: its input and output are double, the exponentials and the row sums are not."""
+    import copy
+    import math
+    import guided_diffusion.nn as RN
+    import guided_diffusion.unet as RU
+
+    def embedding64(timesteps, dim, max_period=10000):
+        half = dim // 2
+        freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float64) / half)
+        args = timesteps[:, None].double() * freqs[None]
+        emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
+        return torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1) if dim % 2 else emb
+
+    twin = copy.deepcopy(model).double()
+    twin.dtype = torch.float64
+    saved = RN.GroupNorm32.forward, RU.timestep_embedding
+    RN.GroupNorm32.forward, RU.timestep_embedding = torch.nn.GroupNorm.forward, embedding64
+    try:
+        yield twin
+    finally:
+        RN.GroupNorm32.forward, RU.timestep_embedding = saved
+
+
+def unet_fixtures(GD, CM, MS):
+    """10. the denoiser (guided_diffusion/unet.py) under shared synthetic weights -> unet.npz.  Per variant of
+    tests/unet_ref.py: the float64 twin's output and VJP (stored fp32), the CRC-32 of the reference's own fp32 output
+    and VJP, and the reference's own fp32 error against its twin (e_ref_*).  Then one conditioning call with a real
+    denoiser, once in fp32 and once with the twin as the model (e_call_*: the call's sensitivity to fp32-level
+    denoiser error).  The reference has to pass the suite's gate with room: e_ref <= TOL / 4."""
+    import unet_ref as U
+    with quiet():
+        from guided_diffusion.unet import create_model
+    out = {"env": np.asarray(U.cpu_build()), "threads": np.int64(torch.get_num_threads())}
+    t64 = lambda a: torch.from_numpy(np.asarray(a)).double()
+
+    def build(name):
+        with quiet():
+            model = create_model(**U.config(name))
+        return U.fill_weights(model).eval()
+
+    for name in U.CPU_VARIANTS + ("FFHQ",):
+        model = build(name)
+        x, t, w, labels = U.inputs(name)
+        lab = None if labels is None else torch.from_numpy(labels)
+        y32, g32 = U.forward_and_vjp(model, torch.from_numpy(x), torch.from_numpy(t), torch.from_numpy(w), lab)
+        with float64_twin(model) as twin:
+            y64, g64 = U.forward_and_vjp(twin, t64(x), torch.from_numpy(t), t64(w), lab)
+        e_out, e_grad = rel_l2(np32(y32), y64.numpy()), rel_l2(np32(g32), g64.numpy())
+        print(f"unet {name:5s} e_ref_out {e_out:.3e}  e_ref_grad {e_grad:.3e}  |y| {float(y64.norm()):.3e}")
+        assert e_out <= U.TOL / 4 and e_grad <= U.TOL / 4, name
+        whole = U.stored_whole(name)
+        out[f"{name}.x_crc"], out[f"{name}.w_crc"] = U.crc(x), U.crc(w)
+        out[f"{name}.y32_crc"], out[f"{name}.g32_crc"] = U.crc(np32(y32)), U.crc(np32(g32))
+        out[f"{name}.y64"] = U.pick(f"{name}.y", np32(y64), whole)
+        out[f"{name}.g64"] = U.pick(f"{name}.g", np32(g64), whole)
+        out[f"{name}.e_ref_out"], out[f"{name}.e_ref_grad"] = np.float64(e_out), np.float64(e_grad)
+        del model, twin
+
+    # one conditioning call, built like the conditioning.npz entries, with A64 as the denoiser
+    c = U.CALL
+    model = build(c["variant"])
+    gb = MS.get_operator("gaussian_blur", kernel_size=61, intensity=3.0, device="cpu")
+    noiser = MS.get_noise("gaussian", sigma=c["sigma"])
+    with quiet():
+        ddpm = GD.create_sampler(sampler="ddpm", timestep_respacing="", **DIFF)
+    truth, ynoise = U.call_inputs(c["ts"][0])[:2]
+    y = gb.forward(torch.from_numpy(truth)) + c["sigma"] * torch.from_numpy(ynoise)
+    out["call.y"] = np32(y)
+    def one_call(mdl, t):
+        _, _, x_prev0, noise = U.call_inputs(t)
+        with quiet():
+            cm = CM.get_conditioning_method("ps", gb, noiser, scale=c["scale"])
+        x_prev = torch.from_numpy(x_prev0).requires_grad_()
+        torch.manual_seed(U.call_seed(t))
+        assert torch.equal(torch.randn_like(x_prev), torch.from_numpy(noise))
+        torch.manual_seed(U.call_seed(t))
+        with quiet():
+            res = ddpm.p_sample(model=mdl, x=x_prev, t=torch.tensor([t]))
+            sample0 = res["sample"].detach().clone()
+            r = cm.conditioning(x_prev=x_prev, x_t=res["sample"], x_0_hat=res["pred_xstart"], measurement=y,
+                                noisy_measurement=y)
+        return {"x0_hat": np32(res["pred_xstart"]), "sample": np32(sample0), "ret0": np32(r[0]), "ret1": np32(r[1])}
+
+    run32 = {t: one_call(model, t) for t in c["ts"]}
+    with float64_twin(model) as twin:                   # float64 inside, fp32 in and out
+        run64 = {t: one_call(lambda z, ts: twin(z.double(), ts).float(), t) for t in c["ts"]}
+    for t in c["ts"]:
+        _, _, x_prev0, noise = U.call_inputs(t)
+        out[f"call.t{t}.x_prev_crc"], out[f"call.t{t}.noise_crc"] = U.crc(x_prev0), U.crc(noise)
+        for f in U.CALL_FIELDS:
+            e = rel_l2(run32[t][f], run64[t][f])
+            print(f"unet call t={t:3d} e_call_{f:7s} {e:.3e}")
+            out[f"call.t{t}.e_call_{f}"] = np.float64(e)
+            out[f"call.t{t}.{f}"] = U.pick(f"call.t{t}", run32[t][f], whole=(f == "ret1"))   # one set of positions per call
+    save("unet.npz", **out)
+
+
 if __name__ == "__main__":
-    extra = {"--only-ddim": ddim_fixtures, "--only-project": project_fixtures, "--only-resample": resample_fixtures}
+    extra = {"--only-ddim": ddim_fixtures, "--only-project": project_fixtures, "--only-resample": resample_fixtures,
+             "--only-unet": unet_fixtures}
     chosen = [fn for flag, fn in extra.items() if flag in sys.argv]
     if chosen:                          # add fixtures without rewriting the others
         install_stubs()
