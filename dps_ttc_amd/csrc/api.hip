@@ -805,6 +805,46 @@ int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float 
     return image_metrics(x, label, m, data_range, mse, psnr, ssim, n, c, h, w, workspace, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ particle repulsion (repulse.hip)
+static int repulse_shape(int64_t n, int64_t chw, int64_t segments)
+{
+    if (n < 0 || chw < 1 || segments < 1 || n % segments) return DPSX_EINVAL;
+    if (n / segments > kRepulseMaxK || segments > 65535 || chw > INT32_MAX) return DPSX_EUNSUPPORTED;
+    return DPSX_OK;
+}
+
+int64_t dpsx_repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments)
+{
+    const int rc = repulse_shape(n, chw, segments);
+    return rc != DPSX_OK ? rc : repulse_workspace_bytes(n, chw, segments);
+}
+
+int dpsx_pairwise_sqdist_f32(const float *x, float *d2, float *info, int64_t n, int64_t chw, int64_t segments,
+                             void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!x || !d2 || !workspace) return DPSX_EINVAL;
+    const int rc = repulse_shape(n, chw, segments);
+    if (rc != DPSX_OK) return rc;
+    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments)) return DPSX_EWORKSPACE;
+    return repulse(false, 0.0f, 0.0f, x, nullptr, d2, nullptr, info, nullptr, n, chw, segments, workspace,
+                   (hipStream_t)stream);
+}
+
+int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float *d2, float *w, float *info,
+                     uint8_t *applied, int64_t n, int64_t chw, int64_t segments, void *workspace, int64_t workspace_bytes,
+                     void *stream)
+{
+    if (!x || !out || !workspace) return DPSX_EINVAL;
+    if (!(c >= 0.0f) || !std::isfinite(c) || !(bandwidth >= 0.0f) || !std::isfinite(bandwidth)) return DPSX_EINVAL;
+    const int rc = repulse_shape(n, chw, segments);
+    if (rc != DPSX_OK) return rc;
+    const char *xb = reinterpret_cast<const char *>(x), *ob = reinterpret_cast<const char *>(out);
+    const int64_t bytes = n * chw * (int64_t)sizeof(float);
+    if (xb < ob + bytes && ob < xb + bytes) return DPSX_EINVAL;       // every particle reads all K: out must not overlap x
+    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments)) return DPSX_EWORKSPACE;
+    return repulse(true, c, bandwidth, x, out, d2, w, info, applied, n, chw, segments, workspace, (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

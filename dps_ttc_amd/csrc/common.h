@@ -640,6 +640,14 @@ int64_t metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int6
 int image_metrics(const float *x, const float *label, int64_t m, float data_range, float *mse, float *psnr, float *ssim,
                   int64_t n, int64_t c, int64_t h, int64_t w, void *workspace, hipStream_t s);
 
+// repulse.hip: the K x K squared distances of every image's particles and, with apply, the repulsion step (the definition
+// is stated in include/dpsx.h); the caller checked the arguments (segments | n, n / segments <= kRepulseMaxK) and the
+// workspace size.  d2, w, info, applied: nullable (the workspace holds what the launches need of them)
+constexpr int kRepulseMaxK = 512;
+int64_t repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments);
+int repulse(bool apply, float c, float bandwidth, const float *x, float *out, float *d2, float *w, float *info,
+            uint8_t *applied, int64_t n, int64_t chw, int64_t segments, void *workspace, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op);
 void phase_destroy(dpsx_op *op);

@@ -1,4 +1,5 @@
-// The per-particle slotted pass of cg.hip, smc.hip, dsg.hip and metrics.hip (no other translation unit includes this header).
+// The per-particle slotted pass of cg.hip, smc.hip, dsg.hip and metrics.hip (repulse.hip, whose blocks own particle tiles, takes
+// the units, the loads, the block range and the host rules from here; no other translation unit includes this header).
 //
 // Grid (slots, n): block (q, p) owns one contiguous range of particle p's work items and leaves its partial sums in slot
 // q; slots = cg_slots(size) is a function of the particle size only, so a particle's partials do not depend on the batch it

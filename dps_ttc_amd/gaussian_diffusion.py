@@ -208,6 +208,60 @@ class GaussianDiffusion:
         #: a kernels.MetricTrace: the fused base loop writes mse / psnr / ssim of x0_hat against the trace's label and the
         #: step's distance into it every `every` steps (evaluation only; None: the loop launches what it always did)
         self.metric_trace = None
+        #: particle repulsion (include/dpsx.h "particle repulsion"; Corso et al. 2023): > 0, after every step with idx > 0
+        #: and idx / num_timesteps >= repulsion_stop the particles of an image are pushed apart by kernels.repulse with
+        #: strength repulsion_scale * betas[idx] and bandwidth repulsion_bandwidth (a mean squared per-element difference;
+        #: None: the mean-distance heuristic).  An option of the base loop (ddpm / ddim, every route) and of ttc_ddim, where
+        #: the push comes before the resampling block.  0: the loops launch what they always did and allocate nothing.
+        self.repulsion_scale = 0.0
+        self.repulsion_bandwidth = None
+        self.repulsion_stop = 0.0
+        self._repulse_out = None
+
+    def _check_repulsion(self, n=None, measurement=None, n_images=False):
+        """The repulsion options, checked from the host's knowledge alone before the first step (and before the device is
+        asked for anything); n, measurement, n_images: the trajectory's, for the particles per image (a loop that has no
+        trajectory to settle passes none: it refuses the option whatever its shape)."""
+        scale = kernels.repulse_strength(self.repulsion_scale, "repulsion_scale")
+        if self.repulsion_bandwidth is not None:
+            kernels.repulse_strength(self.repulsion_bandwidth, "repulsion_bandwidth")
+        stop = self.repulsion_stop
+        if isinstance(stop, bool) or not isinstance(stop, (int, float)) or not 0.0 <= stop <= 1.0:
+            raise ValueError(f"repulsion_stop must be a number in [0, 1] (got {stop!r})")
+        if scale == 0.0:
+            return
+        why = None
+        if isinstance(self, SearchDDPM):
+            why = "search_ddpm keeps one state per image: there is nothing to push apart"
+        elif isinstance(self, SMC_DDPM):
+            why = "smc_ddpm's proposal correction assumes the unrepulsed proposal"
+        elif getattr(self, "global_resample", False):
+            why = "with global (multi-rank) resampling an image's particles live on several ranks"
+        elif self.particle_groups > 1:
+            why = f"particle_groups = {self.particle_groups}: the step crosses the groups"
+        elif self.rng_parity:
+            why = "rng_parity replays the reference's loop, which has no such step"
+        if why is not None:
+            raise NotImplementedError(f"repulsion_scale = {self.repulsion_scale} is not supported here: {why}")
+        if n_images is False:
+            images = self._measurement_images(measurement, n) or 1
+        else:
+            images = self._segments(measurement, n, n_images)
+        if n // images > kernels.REPULSE_MAX_K:
+            raise NotImplementedError(f"repulsion_scale = {self.repulsion_scale}: {n // images} particles per image, the "
+                                      f"repulsion step takes at most {kernels.REPULSE_MAX_K}")
+
+    def _repulse(self, img, idx, images):
+        """the repulsion step on the state a loop's step returned (repulsion_scale > 0; checked by _check_repulsion): the
+        particles of every image pushed apart with strength repulsion_scale * betas[idx], on the steps with idx > 0 and
+        idx / num_timesteps >= repulsion_stop; elsewhere img as it is.  -> a persistent buffer, valid until the next step"""
+        if not self.repulsion_scale or idx <= 0 or idx / self.num_timesteps < self.repulsion_stop:
+            return img
+        img = kernels.f32c(img.detach(), "particles")
+        out = self._repulse_out
+        if out is None or out.shape != img.shape or out.device != img.device:
+            out = self._repulse_out = torch.empty_like(img)
+        return kernels.repulse(img, self.repulsion_scale * self.betas[idx], images or 1, self.repulsion_bandwidth, out=out)
 
     def _check_metric_trace(self, plan=None, cg=None, projecting=False, base_loop=True):
         """sampler.metric_trace runs in the fused branch of the base loop, one chain: anything else is refused before the
@@ -647,6 +701,7 @@ class GaussianDiffusion:
         img = x_start.detach()
         n = img.shape[0]
         self._check_dsg(measurement_cond_fn, img)
+        self._check_repulsion(n, measurement, n_images)
         kernels.require_cuda(img, "x_start")
         plan = self._fusion_plan(measurement_cond_fn, img)
         self._check_dsg(measurement_cond_fn, img, plan)
@@ -715,6 +770,7 @@ class GaussianDiffusion:
                     img = ret[0].detach()
                 distance = ret[1] if len(ret) > 1 else None
                 semantic = ret[2] if len(ret) > 2 and returns_gradient else semantic
+            img = self._repulse(img, idx, images)
             if record and idx % 100 == 0:
                 self._record(save_root, kwargs.get('path_curr_group_idx', 0), idx)
         if pg is not None:
@@ -953,6 +1009,7 @@ class SearchDDPM(DDPM):
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, operator,
                       potential_type='min', resample_every_steps=10, rs_temp=0.1, **kwargs):
         self._check_metric_trace(base_loop=False)
+        self._check_repulsion()
         if self.beam_width != 1:
             return self._beam_loop(model, x_start, measurement, operator, **kwargs)
         img = x_start.detach()
@@ -1083,6 +1140,7 @@ class TTC_DDIM(DDIM):
             else:
                 _, ret = self._per_op_step(model, img, idx, measurement, measurement_cond_fn, segments, {})
                 img, distance = ret[0].detach(), ret[1].detach()
+            img = self._repulse(img, idx, segments)
             if idx % resample_every_steps == 0:
                 img, distance = self._resample(img, distance, resample_scale)
         return img.clone(), distance.clone()
@@ -1181,6 +1239,7 @@ class SMC_DDPM(DDPM):
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         self._check_metric_trace(base_loop=False)
+        self._check_repulsion()
         scale, power, weight, every, scheme, ess = self._smc_options()
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)
         if self._no_plan_reason(method, kw) in ("sampler", "method"):

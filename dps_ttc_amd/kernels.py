@@ -1045,6 +1045,84 @@ class MetricTrace:
         row[3].copy_(distance.reshape(-1))
 
 
+# ------------------------------------------------------------------ particle repulsion (include/dpsx.h: "particle repulsion")
+REPULSE_MAX_K = 512      # particles per image (DPSX_EUNSUPPORTED above)
+REPULSE_INFO = ("h", "gain", "mean", "min")      # the columns of info [M, 4]
+_repulse_ws = {}         # (device, n, chw, images) -> the call's workspace, as _metrics_ws
+
+
+def _repulse_args(x, images):
+    x = f32c(x, "particles")
+    if x.dim() < 2:
+        raise ValueError(f"particles must be [N, ...] (got {tuple(x.shape)})")
+    n, images = int(x.shape[0]), int(images)
+    if images < 1 or n % images:
+        raise ValueError(f"{n} particles do not split into {images} images")
+    chw = x[0].numel() if n else int(np.prod(x.shape[1:]))
+    key = (x.device, n, chw, images)
+    ws = _repulse_ws.get(key)
+    if ws is None:
+        need = lib().dpsx_repulse_workspace_bytes(n, chw, images)
+        if need < 0:
+            check(int(need), "dpsx_repulse_workspace_bytes")
+        ws = _repulse_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    return x, n, chw, images, ws
+
+
+def pairwise_sqdist(x, images=1, want_info=False, stream=None):
+    """The squared distances between the particles of every image, one device call (dpsx_pairwise_sqdist_f32): x [N, ...],
+    image-major, `images` images of K = N / images particles -> d2 [images, K, K] float32 (symmetric bit for bit, +0.0 on
+    the diagonal, exactly 0 between particles with equal bits).  want_info: -> (d2, info [images, 4]) with the columns
+    REPULSE_INFO: the mean heuristic's bandwidth h, 0, the mean and the minimum off-diagonal distance (0: duplicates).
+    K <= 512.  No host read; the workspace is cached per shape and serves one stream at a time."""
+    x, n, chw, images, ws = _repulse_args(x, images)
+    k = n // images
+    d2 = torch.empty((images, k, k), dtype=torch.float32, device=x.device)
+    info = torch.empty((images, 4), dtype=torch.float32, device=x.device) if want_info else None
+    check(lib().dpsx_pairwise_sqdist_f32(ptr(x), ptr(d2), ptr(info), n, chw, images, ptr(ws), ws.numel(),
+                                         _stream_arg(stream, x)), "dpsx_pairwise_sqdist_f32")
+    return (d2, info) if want_info else d2
+
+
+def repulse_strength(value, what="strength"):
+    """a strength / bandwidth of the repulsion step as the library takes it: a finite float >= 0 (ValueError otherwise)"""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(value, bool) or not (v >= 0.0) or v == float("inf"):
+        raise ValueError(f"{what} must be a finite number >= 0 (got {value!r})")
+    return v
+
+
+def repulse(x, strength, images=1, bandwidth=None, out=None, want_info=False, stream=None):
+    """The repulsion step (dpsx_repulse_f32, three launches): every particle of an image is pushed away from the image's
+    other particles, out_i = x_i + gain sum_j w_ij (x_i - x_j) with w_ij = exp(-d2_ij / h), gain = 2 strength / h and
+    h = bandwidth * D (bandwidth: a mean squared per-element difference) or, with bandwidth None / 0, mean d2 / ln(K + 1).
+    x [N, ...] image-major, `images` images of K = N / images <= 512 particles; x is not written.  An image of one
+    particle, of equal particles, or with a NaN / Inf in it is copied.  out: a contiguous float32 tensor shaped like x that
+    does not overlap it (default: a fresh one).  want_info: -> (out, {"d2": [M, K, K], "w": [M, K, K], "info": [M, 4]
+    (REPULSE_INFO), "applied": [M] uint8}).  No host read; the workspace is cached per shape and serves one stream at a time."""
+    c = repulse_strength(strength)
+    bw = 0.0 if bandwidth is None else repulse_strength(bandwidth, "bandwidth")
+    x, n, chw, images, ws = _repulse_args(x, images)
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous() or \
+            out.device != x.device:
+        raise ValueError(f"out must be a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
+    k = n // images
+    rec = None
+    if want_info:
+        f = dict(dtype=torch.float32, device=x.device)
+        rec = {"d2": torch.empty((images, k, k), **f), "w": torch.empty((images, k, k), **f),
+               "info": torch.empty((images, 4), **f), "applied": torch.empty(images, dtype=torch.uint8, device=x.device)}
+    g = rec.get if rec else (lambda name: None)
+    check(lib().dpsx_repulse_f32(c, bw, ptr(x), ptr(out), ptr(g("d2")), ptr(g("w")), ptr(g("info")), ptr(g("applied")),
+                                 n, chw, images, ptr(ws), ws.numel(), _stream_arg(stream, x)), "dpsx_repulse_f32")
+    return (out, rec) if want_info else out
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,

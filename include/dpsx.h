@@ -537,6 +537,53 @@ int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float 
                            int64_t n, int64_t c, int64_t h, int64_t w,
                            void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- particle repulsion: after the sampler's step, every particle of an image is pushed away from the image's other
+ * particles by an RBF-kernel-weighted sum of differences (Corso et al. 2023, particle guidance, the fixed-potential form in
+ * x_t space).  No model gradient: a pure function of the image's K states.  Its first half, the K x K squared-distance
+ * matrix of an image, is also the diversity / collapse diagnostic of a particle set.  tests/repulse_ref.py restates the
+ * definition in float64.
+ *   x [n, chw] particles, image-major: M = segments images of K = n / M particles each, D = chw.  Everything below is per
+ *   image and uses the image's own particles only.
+ *   d2[i][j] = sum_e (x_i[e] - x_j[e])^2 in the difference form: one fp32 subtraction per element, the square accumulated
+ *              with one fma.  Each pair is computed once (i < j) and mirrored: the matrix is symmetric bit for bit, its
+ *              diagonal is +0.0, and two particles with equal bits have distance exactly 0.  The sum: per block (one tile
+ *              pair of 8 x 8 particles and one contiguous element range) every lane adds its elements in index order, then a
+ *              fixed tree; the slot count is a function of (D, K) only; the finisher adds a pair's slots in double in index
+ *              order and rounds to fp32 once.
+ *   mean     = sum_{i<j} d2[i][j] / (K (K - 1) / 2) in double over the fp32 entries, in a fixed order that depends on K only
+ *              (thread t of 1024 adds the pairs at matrix entries t, t + 1024, ... in index order; then a fixed tree);
+ *              min = the smallest off-diagonal entry (a NaN entry gives NaN).  K = 1: mean = 0, min = +inf.
+ *   h        = bandwidth D if bandwidth > 0 (bandwidth is then a mean squared per-element difference), else
+ *              mean / ln(K + 1): SVGD's heuristic with the mean in the median's place -- at the typical distance a weight
+ *              is 1 / (K + 1).  In double.
+ *   w[i][j]  = exp(-d2[i][j] / h) for i != j, formed in double and rounded to fp32 once; w[i][i] = 0.
+ *   gain     = 2 c / h (double, rounded to fp32 once); c >= 0 is the caller's strength for this step.
+ *   out_i[e] = fma(gain, S_i[e], x_i[e]),  S_i[e] = sum_j w[i][j] (x_i[e] - x_j[e]): j = 0 .. K - 1 in index order, each
+ *              term one fp32 subtraction and one fma into the sum.  The push is repulsive (K = 2: out_0 - out_1 =
+ *              (x_0 - x_1) (1 + 2 gain w01)) and, w being symmetric, keeps the image's mean.
+ *   The flag: an image is stepped (applied = 1) iff K > 1, mean is finite, h > 0, h is finite and gain is finite in fp32.
+ *   Otherwise it is COPIED, no arithmetic (-0.0 and NaN bits survive), its flag is 0, its w is all 0 and its gain is
+ *   reported as 0: this covers K = 1, all particles equal, and any NaN / Inf in the image, decided per image inside the
+ *   launches with no host read.  A non-finite value reaches its own image only.  All weights underflowing to 0 gives
+ *   out = x.
+ *   info [M, 4] = (h, gain, mean, min) per image; applied [M] the flag.
+ * Three launches on `stream`: the pair partials (lanes across elements, float4 units where chw % 4 == 0 and x / out are
+ * 16-byte aligned, else the scalar instantiation of the same body), the finisher (one block per image) and the apply.
+ * No atomics, no fence, no allocation, no host read (graph-capturable).  An image's numbers do not depend on M or on its
+ * place in the batch.  dpsx_pairwise_sqdist_f32 runs the first launch and the distance half of the second: d2 [M, K, K]
+ * and info (nullable; h is the mean heuristic's, gain is 0).  dpsx_repulse_f32 runs all three; out [n, chw] must not
+ * overlap x (every particle reads all K); d2 [M, K, K], w [M, K, K], info and applied are nullable outputs.  The workspace
+ * (dpsx_repulse_workspace_bytes) serves one stream at a time.
+ * DPSX_EINVAL: a null x, out (d2 for the distances) or workspace; chw < 1, segments < 1, n not divisible by segments;
+ * c or bandwidth negative or not finite; out overlapping x.  DPSX_EUNSUPPORTED: K > 512 (more than 65535 images,
+ * chw >= 2^31).  DPSX_EWORKSPACE: a short workspace.  All of them return before anything is launched. */
+int64_t dpsx_repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments);
+int dpsx_pairwise_sqdist_f32(const float *x, float *d2, float *info /* nullable */, int64_t n, int64_t chw,
+                             int64_t segments, void *workspace, int64_t workspace_bytes, void *stream);
+int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float *d2, float *w, float *info,
+                     uint8_t *applied, int64_t n, int64_t chw, int64_t segments,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

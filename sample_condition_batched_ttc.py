@@ -141,7 +141,21 @@ def parse_args(argv=None):
                    help='torch: PSNR per path in a host loop (one read per particle).  device: PSNR and SSIM of a particle '
                         'group in one device call and one copy; also writes {fname}_pathwise_psnr.npy / _pathwise_ssim.npy '
                         'and the best-of-n curves {fname}_best_of_n_psnr.npy / _best_of_n_ssim.npy; one rank only')
+    p.add_argument('--repulsion_scale', type=float, default=0.0,
+                   help='ddpm / ddim / ttc_ddim: after every step push the particles of an image apart (kernel-weighted '
+                        'particle repulsion) with strength repulsion_scale * beta_t; 0: off')
+    p.add_argument('--repulsion_bandwidth', type=float, default=None,
+                   help='the repulsion kernel\'s bandwidth as a mean squared per-element difference (default: the mean '
+                        'squared distance of the image\'s particles / ln(K + 1))')
+    p.add_argument('--repulsion_stop', type=float, default=0.0,
+                   help='no repulsion on the steps with t / T below this fraction (the last steps of the trajectory)')
+    p.add_argument('--path_diversity', action='store_true',
+                   help='write {fname}_path_diversity.npy: per particle group the [mean, min] RMS per-element distance '
+                        'between its final samples (min 0: duplicates); one rank only')
     args = p.parse_args(argv)
+    if args.path_diversity and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        raise SystemExit("--path_diversity runs on one rank only: the per-group distances are not gathered between ranks "
+                         f"(WORLD_SIZE={os.environ['WORLD_SIZE']})")
     if args.path_metrics == 'device' and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         raise SystemExit("--path_metrics device runs on one rank only: the per-path metric vectors are not gathered between "
                          f"ranks (WORLD_SIZE={os.environ['WORLD_SIZE']})")
@@ -267,6 +281,47 @@ def check_beam_width(args, sampler_name, world):
                          f"best {b} (WORLD_SIZE={world})")
 
 
+def repulsion_flags(args):
+    """the --repulsion_* options given on the command line: [(flag, value)]"""
+    given = [("--repulsion_scale", args.repulsion_scale if args.repulsion_scale != 0.0 else None),
+             ("--repulsion_bandwidth", args.repulsion_bandwidth),
+             ("--repulsion_stop", args.repulsion_stop if args.repulsion_stop != 0.0 else None)]
+    return [(flag, v) for flag, v in given if v is not None]
+
+
+def check_repulsion(args, sampler_name, world=1):
+    """--repulsion_* and --path_diversity: reject what the loops refuse, before any GPU work (one-line message)"""
+    import math
+    for flag, value in repulsion_flags(args):
+        if not math.isfinite(value) or value < 0.0:
+            raise SystemExit(f"{flag} must be finite and not negative (got {value})")
+    if not 0.0 <= args.repulsion_stop <= 1.0:
+        raise SystemExit(f"--repulsion_stop is a fraction of the trajectory in [0, 1] (got {args.repulsion_stop})")
+    if args.batch_size > 512 and (args.repulsion_scale > 0.0 or args.path_diversity):
+        raise SystemExit(f"--repulsion_scale / --path_diversity take at most 512 particles per image (--batch_size "
+                         f"{args.batch_size})")
+    if not args.repulsion_scale > 0.0:
+        for flag, value in repulsion_flags(args):
+            raise SystemExit(f"{flag} {value} needs --repulsion_scale > 0")
+        return
+    if sampler_name in ('search_ddpm', 'smc_ddpm'):
+        raise SystemExit(f"--repulsion_scale is an option of samplers ddpm, ddim and ttc_ddim (the diffusion config names "
+                         f"{sampler_name})")
+    if args.particle_groups > 1:
+        raise SystemExit("--repulsion_scale does not run with --particle_groups > 1: the step crosses the groups")
+    if world > 1 and sampler_name == 'ttc_ddim':
+        raise SystemExit("--repulsion_scale with sampler ttc_ddim runs on one rank only: with the multi-rank resampling an "
+                         f"image's particles live on several ranks (WORLD_SIZE={world})")
+
+
+def path_diversity(sample, images=1):
+    """--path_diversity: [images, 2] (mean, min) RMS per-element distance between the particles of every image of a group's
+    final samples, one device call (kernels.pairwise_sqdist) and one copy"""
+    from dps_ttc_amd import kernels
+    _, info = kernels.pairwise_sqdist(sample.detach(), images=images, want_info=True)
+    return torch.sqrt(info[:, 2:4] / sample[0].numel()).cpu().numpy()
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
@@ -281,6 +336,8 @@ def main(argv=None):
         check_dsg(args, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None)
     if args.beam_width != 1:
         check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
+    if repulsion_flags(args) or args.path_diversity:
+        check_repulsion(args, sampler_name, world)
     if args.images_per_batch != 1:
         check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
     if world > 1:
@@ -338,6 +395,8 @@ def main(argv=None):
     sampler.resample_every = args.ttc_resample_every
     sampler.noise_draw = args.noise_draw
     sampler.beam_width = args.beam_width
+    sampler.repulsion_scale, sampler.repulsion_stop = args.repulsion_scale, args.repulsion_stop
+    sampler.repulsion_bandwidth = args.repulsion_bandwidth
     for flag, value in smc_flags(args):          # check_smc: the sampler is smc_ddpm
         setattr(sampler, flag[len("--smc_"):], value)
     sampler.noise_seed = args.seed or 0          # the same on every rank: the path id tells the ranks' particles apart
@@ -427,6 +486,7 @@ def main(argv=None):
 
         distances, finals = [], []
         device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
+        diversity = []
         for g in my_groups:
             x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
@@ -438,6 +498,8 @@ def main(argv=None):
                 dist_g = handle.score(sample, y_n)                             # ||y - A(x_p)||_2 per particle (HIP)
             distances.append(dist_g)
             finals.append(sample)
+            if args.path_diversity:
+                diversity.append(path_diversity(sample)[0])
             if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
                 pm = pathwise_metrics(ref_img, sample)
                 pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -468,6 +530,8 @@ def main(argv=None):
             if device_metrics:       # one rank (parse_args): the groups' order is the path order of all_d
                 save_path_metrics(out_path, fname, all_d.cpu().numpy(), np.concatenate(path_psnr),
                                   np.concatenate(path_ssim))
+            if args.path_diversity:  # one rank (parse_args): [groups, 2]
+                np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack(diversity))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -507,6 +571,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
 
     distances, finals = [], []
     device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
+    diversity = []
     for g in range(groups):
         x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
@@ -518,6 +583,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
             dist_g = handle.score(sample, y)                          # ||y_{p // K} - A(x_p)||_2 per particle
         distances.append(dist_g)
         finals.append(sample)
+        if args.path_diversity:
+            diversity.append(path_diversity(sample, images=B))
         if device_metrics:            # one device call and one copy for the group's B x K particles
             pm = pathwise_metrics(refs, sample, n_images=B)
             pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -554,6 +621,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
         if device_metrics:       # [groups][B, K] -> image b's n_paths values in path order (group-major), as d_host[b]
             save_path_metrics(out_path, fname, d_host[b], np.concatenate([v[b] for v in path_psnr]),
                               np.concatenate([v[b] for v in path_ssim]))
+        if args.path_diversity:  # [groups][B, 2] -> image b's [groups, 2]
+            np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack([v[b] for v in diversity]))
 
 
 if __name__ == '__main__':

@@ -40,6 +40,13 @@ the bytes by shape arithmetic as a fraction of K3's rate, all from the same run.
 3 x --reps repetitions alternated in one process: (a) the driver's per-particle metrics.compute_psnr loop with its host
 read (PSNR only), (b) PSNR and SSIM as batched torch ops (five depthwise conv2d with the 11 x 11 window, the elementwise map,
 the means), (c) kernels.image_metrics with all three outputs and its PSNR-only call.  (b) is the yardstick of (c).
+    python tools/kbench.py --repulse                                                  (particle repulsion, 256^2)
+--repulse: [M K, 3, 256, 256] particles, M = 4 x K = 16, M = 1 x K = 64 and M = 1 x K = 512, 3 x --reps repetitions alternated
+in one process: (a) kernels.pairwise_sqdist (the pair partials and the finisher's distance half), (b) kernels.repulse (all
+three launches), (c) the same mathematics as torch ops (torch.cdist on the flattened particles, exp, one matmul), (d) K3 at the
+same N for scale.  (a) and (b) are stated against both floors by shape arithmetic -- bytes at 8 TB/s with every particle moved
+once, fp32 operations at the vector peak -- with the one that binds and how often the tiling fetches a particle.  The three
+launches apart come from a kernel trace (rocprofv3 --kernel-trace) of the same call in a run of its own.
 """
 import argparse
 import os
@@ -68,7 +75,10 @@ def main():
     ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
     ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
     ap.add_argument("--metrics", action="store_true", help="time per-path PSNR / SSIM: host loop / torch ops / image_metrics")
+    ap.add_argument("--repulse", action="store_true", help="time particle repulsion: the distances / the whole call / torch ops / K3")
     args = ap.parse_args()
+    if args.repulse:
+        return repulse_step(args)
     if args.metrics:
         return metrics_step(args)
     if args.dsg:
@@ -545,6 +555,83 @@ def resample_step(args):
             print(f"resample 256^2 M={M} K={k:3d} {name:36s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs})  "
                   f"{moved / ts.mean() / 1e6:6.2f} TB/s = {moved / ts.mean() / 1e6 / 8.0:.2f} of 8 TB/s", flush=True)
         del img, parts
+
+
+def repulse_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    c, h, w = 3, 256, 256
+    D, P = c * h * w, c * h * w * 4
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for M, k in ((4, 16), (1, 64), (1, 512)):
+        n = M * k
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        base = torch.randn(M, 1, c, h, w, device=dev, generator=gen)
+        x = (np.sqrt(0.5) * base + np.sqrt(0.5) * torch.randn(M, k, c, h, w, device=dev, generator=gen)).reshape(n, c, h, w)
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        strength = 0.05 * D
+        buf = kernels.StepBuffers(None, n, c, h, w, dev)
+        buf.sample.copy_(x)
+        g_unet = 1e-3 * torch.randn(n, c, h, w, device=dev, generator=gen)
+        eye = torch.eye(k, device=dev, dtype=torch.bool)
+
+        def a_dist(i):
+            kernels.pairwise_sqdist(x, images=M)
+
+        def b_whole(i):
+            kernels.repulse(x, strength, images=M, out=out)
+
+        def c_torch(i):
+            xf = x.view(M, k, D)
+            d2 = torch.cdist(xf, xf) ** 2
+            hh = d2.sum(dim=(1, 2), keepdim=True) / (k * (k - 1)) / np.log(k + 1.0)
+            wt = torch.exp(-d2 / hh).masked_fill(eye, 0.0)
+            return xf + (2.0 * strength / hh) * (wt.sum(dim=2, keepdim=True) * xf - torch.matmul(wt, xf))
+
+        def d_k3(i):
+            kernels.step_update(buf, g_unet, ck)
+
+        forms = (("a pairwise_sqdist (pairs + finisher)", a_dist), ("b repulse (all three launches)", b_whole),
+                 ("c torch cdist + exp + matmul", c_torch), ("d K3 (step_update) for scale", d_k3))
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        # the floors by shape arithmetic: bytes at 8 TB/s (each particle once; the apply also writes), fp32 vector operations
+        # at 157 TFLOP/s (the packed-fma rate; the launches issue sub + fma per element and pair)
+        pair_flop, apply_flop = 3.0 * D * M * k * (k - 1) / 2, 3.0 * D * M * k * k
+        floors = {"a": (n * P / 8e6, pair_flop / 157e6), "b": (3 * n * P / 8e6, (pair_flop + apply_flop) / 157e6)}
+        tiles = (k + 7) // 8
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            note = ""
+            if name[0] in floors:
+                fb, ff = floors[name[0]]
+                note = (f"  floors: bytes {fb:.1f} us, fp32 {ff:.1f} us ({'fp32' if ff > fb else 'bytes'} binds: "
+                        f"{max(fb, ff) / ts.mean():.2f} of it); a particle is fetched {tiles + 1} x by the pairs"
+                        + (f", {tiles} x by the apply" if name[0] == "b" else ""))
+            print(f"repulse 256^2 M={M} K={k:3d} {name:38s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
+                  flush=True)
+        del x, out, buf, g_unet, base
 
 
 def noise_draw(args):
