@@ -110,155 +110,28 @@ static int alloc_counters(dpsx_op *op)
     return DPSX_OK;
 }
 
-static int finish_create(dpsx_op *op, dpsx_op **out)
+static dpsx_op *new_op(int kind)
 {
-    int rc = alloc_counters(op);
-    if (rc != DPSX_OK) { dpsx_op_destroy(op); return rc; }
-    *out = op;
-    return DPSX_OK;
+    dpsx_op *op = new (std::nothrow) dpsx_op();
+    if (op) op->kind = kind;
+    return op;
 }
 
-static int upload_taps(dpsx_op *op, const std::vector<int> &dy, const std::vector<int> &dx,
-                       const std::vector<float> &w)
+// what every constructor ends with; rc: the kind's own construction (blur.hip, resize.hip, phase.hip)
+static int finish_create(dpsx_op *op, int rc, dpsx_op **out)
 {
-    const size_t n = std::max<size_t>(w.size(), 1);
-    DPSX_HIP_TRY(hipMalloc((void **)&op->d_tap_dy, n * sizeof(int)));
-    DPSX_HIP_TRY(hipMalloc((void **)&op->d_tap_dx, n * sizeof(int)));
-    DPSX_HIP_TRY(hipMalloc((void **)&op->d_tap_w, n * sizeof(float)));
-    if (!w.empty()) {
-        DPSX_HIP_TRY(hipMemcpy(op->d_tap_dy, dy.data(), w.size() * sizeof(int), hipMemcpyHostToDevice));
-        DPSX_HIP_TRY(hipMemcpy(op->d_tap_dx, dx.data(), w.size() * sizeof(int), hipMemcpyHostToDevice));
-        DPSX_HIP_TRY(hipMemcpy(op->d_tap_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if (rc == DPSX_OK) rc = alloc_counters(op);
+    if (rc != DPSX_OK) { dpsx_op_destroy(op); return rc; }
+    *out = op;
     return DPSX_OK;
 }
 
 int dpsx_op_create_blur(const float *kernel_host, int ks, int mode, dpsx_op **out)
 {
     if (!kernel_host || !out || ks < 1 || ks % 2 == 0 || ks > 2 * kMaxRadius + 1) return DPSX_EINVAL;
-    dpsx_op *op = new (std::nothrow) dpsx_op();
+    dpsx_op *op = new_op(OP_TAPS);       // blur_create: OP_SEP for a rank-1 kernel
     if (!op) return DPSX_ENOMEM;
-    const int R = ks / 2;
-    op->ks = ks;
-    // effective support: largest |offset| with a non-zero tap (the Gaussian sigma=3 kernel
-    // occupies 25x25 of its 61x61 grid) -- smaller halos, same result (0 * x contributes nothing)
-    int reach = 0;
-    double peak = 0.0;
-    int pi = R, pj = R;
-    for (int i = 0; i < ks; ++i)
-        for (int j = 0; j < ks; ++j) {
-            const float v = kernel_host[i * ks + j];
-            if (v != 0.0f) reach = std::max(reach, std::max(std::abs(i - R), std::abs(j - R)));
-            if (std::fabs((double)v) > peak) { peak = std::fabs((double)v); pi = i; pj = j; }
-        }
-    op->radius = R;  // the reflection pad is always ks/2 (fold geometry), taps may reach less
-    const int reach4 = std::max(4, (reach + 3) / 4 * 4);
-    op->radius4 = reach4;
-    op->reach = reach;
-    // rank-1 test in double: K ~= col (x) row with col = K[:, pj], row = K[pi, :] / K[pi, pj]
-    bool separable = mode != DPSX_BLUR_FORCE_TAPS && peak > 0.0;
-    std::vector<double> col((size_t)ks), row((size_t)ks);
-    if (separable) {
-        for (int i = 0; i < ks; ++i) col[(size_t)i] = kernel_host[i * ks + pj];
-        for (int j = 0; j < ks; ++j) row[(size_t)j] = (double)kernel_host[pi * ks + j] / (double)kernel_host[pi * ks + pj];
-        for (int i = 0; i < ks && separable; ++i)
-            for (int j = 0; j < ks; ++j)
-                if (std::fabs(col[(size_t)i] * row[(size_t)j] - (double)kernel_host[i * ks + j]) > 1e-6 * peak) {
-                    separable = false;
-                    break;
-                }
-    }
-    op->kind = separable ? OP_SEP : OP_TAPS;
-    if (separable)
-        for (int d = -reach; d <= reach; ++d) {
-            op->sep.v[reach4 + d] = (float)col[(size_t)(R + d)];
-            op->sep.h[reach4 + d] = (float)row[(size_t)(R + d)];
-        }
-    // the list of non-zero taps always exists: it is the whole implementation for non-separable kernels
-    // and the fallback of separable ones for shapes the 16-byte loader cannot take (w % 4 != 0)
-    {
-        std::vector<int> dy, dx;
-        std::vector<float> w;
-        for (int i = 0; i < ks; ++i)
-            for (int j = 0; j < ks; ++j)
-                if (kernel_host[i * ks + j] != 0.0f) {
-                    dy.push_back(i - R);
-                    dx.push_back(j - R);
-                    w.push_back(kernel_host[i * ks + j]);
-                }
-        op->nnz = (int)w.size();
-        int rc = upload_taps(op, dy, dx, w);
-        if (rc != DPSX_OK) { dpsx_op_destroy(op); return rc; }
-        // per-side halo of the forward tap list (the adjoint swaps top <-> bottom, left <-> right)
-        {
-            int t = 0, b = 0, l = 0, r = 0;
-            for (size_t i = 0; i < w.size(); ++i) {
-                t = std::max(t, -dy[i]); b = std::max(b, dy[i]);
-                l = std::max(l, -dx[i]); r = std::max(r, dx[i]);
-            }
-            if (t + b < 3) b = 3 - t;                                  // a run window spans four rows
-            op->halo_t = t; op->halo_b = b;
-            op->halo_l = (l + 3) / 4 * 4; op->halo_r = (r + 3) / 4 * 4;
-        }
-        // vertical runs of 4 or 2 taps per kernel column, window kept inside [-halo_t, halo_b]; four classes
-        // (dx parity x run length) stored one after the other -- see TapRun
-        std::vector<TapRun> cls_f[4], cls_a[4];
-        for (int j = 0; j < ks; ++j) {
-            const int dx = j - R, odd = dx & 1;
-            int i = 0;
-            while (i < ks) {
-                if (kernel_host[i * ks + j] == 0.0f) { ++i; continue; }
-                int k = 0;                                              // consecutive non-zero taps from row i
-                while (i + k < ks && k < 4 && kernel_host[(i + k) * ks + j] != 0.0f) ++k;
-                const int L = k >= 3 ? 4 : 2;
-                const int first = i - R;                               // dy of the run's first tap
-                const int dy0 = std::min(first, op->halo_b - (L - 1)); // shift up so dy0 + L - 1 <= halo_b (>= -halo_t)
-                TapRun r{};
-                r.dy0 = dy0; r.dx = dx;
-                for (int q = 0; q < L; ++q) {
-                    const int ii = dy0 + q + R;
-                    r.w[q] = (ii >= 0 && ii < ks && ii >= i) ? kernel_host[ii * ks + j] : 0.0f;
-                }
-                cls_f[2 * odd + (L == 2)].push_back(r);
-                // adjoint (correlation-transpose): V[p][q] = sum w_t u[p - dy_t][q - dx_t] -> negated offsets
-                // (same dx parity), reversed weights, same loop
-                TapRun t{};
-                t.dy0 = -(dy0 + L - 1); t.dx = -dx;
-                for (int q = 0; q < L; ++q) t.w[q] = r.w[L - 1 - q];
-                cls_a[2 * odd + (L == 2)].push_back(t);
-                i = dy0 + L + R;                                       // first row not covered by this run
-            }
-        }
-        // an even number of runs per class (the pipelined loop works on pairs): a dummy run repeats the last offsets
-        // with zero weights
-        for (int c = 0; c < 4; ++c)
-            if (cls_f[c].size() % 2) {
-                TapRun f = cls_f[c].back(), t = cls_a[c].back();
-                for (int q = 0; q < 4; ++q) f.w[q] = t.w[q] = 0.0f;
-                cls_f[c].push_back(f);
-                cls_a[c].push_back(t);
-            }
-        std::vector<TapRun> fwd, adj;
-        for (int c = 0; c < 4; ++c) {
-            std::stable_sort(cls_a[c].begin(), cls_a[c].end(), [](const TapRun &x, const TapRun &y) { return x.dx > y.dx; });
-            for (const TapRun &t : cls_a[c]) {
-                op->nrun_adj_pos[c] += t.dx >= 1;
-                op->nrun_adj_neg[c] += t.dx <= -1;
-            }
-            op->nrun[c] = (int)cls_f[c].size();
-            fwd.insert(fwd.end(), cls_f[c].begin(), cls_f[c].end());
-            adj.insert(adj.end(), cls_a[c].begin(), cls_a[c].end());
-        }
-        op->nruns = (int)fwd.size();
-        const size_t bytes = std::max<size_t>(fwd.size(), 1) * sizeof(TapRun);
-        if (hipMalloc(&op->d_runs_fwd, bytes) != hipSuccess || hipMalloc(&op->d_runs_adj, bytes) != hipSuccess ||
-            (!fwd.empty() && (hipMemcpy(op->d_runs_fwd, fwd.data(), fwd.size() * sizeof(TapRun), hipMemcpyHostToDevice) != hipSuccess ||
-                              hipMemcpy(op->d_runs_adj, adj.data(), adj.size() * sizeof(TapRun), hipMemcpyHostToDevice) != hipSuccess))) {
-            dpsx_op_destroy(op);
-            return DPSX_ENOMEM;
-        }
-    }
-    return finish_create(op, out);
+    return finish_create(op, blur_create(op, kernel_host, ks, mode), out);
 }
 
 int dpsx_op_create_resize(int64_t in_h, int64_t in_w, const float *w_h_host, const int64_t *i_h_host,
@@ -268,13 +141,10 @@ int dpsx_op_create_resize(int64_t in_h, int64_t in_w, const float *w_h_host, con
     if (!w_h_host || !i_h_host || !w_w_host || !i_w_host || !out) return DPSX_EINVAL;
     if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || taps_h < 1 || taps_w < 1) return DPSX_EINVAL;
     if (in_h > 16384 || in_w > 16384) return DPSX_EUNSUPPORTED;
-    dpsx_op *op = new (std::nothrow) dpsx_op();
+    dpsx_op *op = new_op(OP_RESIZE);
     if (!op) return DPSX_ENOMEM;
-    op->kind = OP_RESIZE;
-    op->in_h = in_h; op->in_w = in_w; op->out_h = out_h; op->out_w = out_w; op->taps_h = taps_h; op->taps_w = taps_w;
-    int rc = resize_create(op, w_h_host, i_h_host, w_w_host, i_w_host);
-    if (rc != DPSX_OK) { delete op; return rc; }
-    return finish_create(op, out);
+    const ResizeOp shape{in_h, in_w, out_h, out_w, taps_h, taps_w};
+    return finish_create(op, resize_create(op, shape, w_h_host, i_h_host, w_w_host, i_w_host), out);
 }
 
 int dpsx_op_create_mask(const float *mask_dev, int64_t h, int64_t w, dpsx_op **out)
@@ -285,47 +155,35 @@ int dpsx_op_create_mask(const float *mask_dev, int64_t h, int64_t w, dpsx_op **o
 int dpsx_op_create_mask_n(const float *mask_dev, int64_t mask_n, int64_t h, int64_t w, dpsx_op **out)
 {
     if (!mask_dev || !out || mask_n < 1 || mask_n > (1 << 24) || h < 1 || w < 1) return DPSX_EINVAL;
-    dpsx_op *op = new (std::nothrow) dpsx_op();
+    dpsx_op *op = new_op(OP_MASK);
     if (!op) return DPSX_ENOMEM;
-    op->kind = OP_MASK;
-    op->mask = mask_dev;
-    op->mask_n = mask_n;
-    op->in_h = h; op->in_w = w;
-    return finish_create(op, out);
+    op->mask = MaskOp{mask_dev, mask_n, h, w};
+    return finish_create(op, DPSX_OK, out);
 }
 
 int dpsx_op_create_identity(dpsx_op **out)
 {
     if (!out) return DPSX_EINVAL;
-    dpsx_op *op = new (std::nothrow) dpsx_op();
+    dpsx_op *op = new_op(OP_IDENT);
     if (!op) return DPSX_ENOMEM;
-    op->kind = OP_IDENT;
-    return finish_create(op, out);
+    return finish_create(op, DPSX_OK, out);
 }
 
 int dpsx_op_create_phase(int64_t h, int64_t pad, int64_t max_planes, dpsx_op **out)
 {
     if (!out || h < 1 || pad < 0 || max_planes < 1 || (h + 2 * pad) % 2 != 0) return DPSX_EINVAL;
-    dpsx_op *op = new (std::nothrow) dpsx_op();
+    dpsx_op *op = new_op(OP_PHASE);
     if (!op) return DPSX_ENOMEM;
-    op->kind = OP_PHASE;
-    op->pr_h = h; op->pr_pad = pad; op->pr_planes = max_planes;
-    int rc = phase_create(op);
-    if (rc != DPSX_OK) { delete op; return rc; }
-    return finish_create(op, out);
+    return finish_create(op, phase_create(op, PhaseOp{h, pad, max_planes}), out);
 }
 
 void dpsx_op_destroy(dpsx_op *op)
 {
     if (!op) return;
-    if (op->d_tap_dy) (void)hipFree(op->d_tap_dy);
-    if (op->d_tap_dx) (void)hipFree(op->d_tap_dx);
-    if (op->d_tap_w) (void)hipFree(op->d_tap_w);
-    if (op->d_runs_fwd) (void)hipFree(op->d_runs_fwd);
-    if (op->d_runs_adj) (void)hipFree(op->d_runs_adj);
     if (op->d_counters) (void)hipFree(op->d_counters);
-    if (op->kind == OP_RESIZE) resize_destroy(op);
-    if (op->kind == OP_PHASE) phase_destroy(op);
+    if (op->blur) blur_destroy(op);
+    if (op->resize) resize_destroy(op);
+    if (op->phase) phase_destroy(op);
     delete op;
 }
 
@@ -336,15 +194,15 @@ int dpsx_op_out_shape(const dpsx_op *op, int64_t h, int64_t w, int64_t *out_h, i
     if (!op || !out_h || !out_w) return DPSX_EINVAL;
     switch (op->kind) {
     case OP_RESIZE:
-        if (h != op->in_h || w != op->in_w) return DPSX_EINVAL;
-        *out_h = op->out_h; *out_w = op->out_w;
+        if (h != op->resize->in_h || w != op->resize->in_w) return DPSX_EINVAL;
+        *out_h = op->resize->out_h; *out_w = op->resize->out_w;
         return DPSX_OK;
     case OP_PHASE:
-        if (h != op->pr_h || w != op->pr_h) return DPSX_EINVAL;
-        *out_h = *out_w = op->pr_h + 2 * op->pr_pad;
+        if (h != op->phase->h || w != op->phase->h) return DPSX_EINVAL;
+        *out_h = *out_w = op->phase->h + 2 * op->phase->pad;
         return DPSX_OK;
     case OP_MASK:
-        if (h != op->in_h || w != op->in_w) return DPSX_EINVAL;
+        if (h != op->mask.h || w != op->mask.w) return DPSX_EINVAL;
         [[fallthrough]];
     default:
         *out_h = h; *out_w = w;
@@ -366,6 +224,22 @@ static int64_t parts_per_particle(const dpsx_op *op, int64_t c, int64_t h, int64
     return 1;
 }
 
+// The two slot-count rules: how many partial sums per particle a launch leaves for its finisher to re-sum.  The generic
+// residual pass (elementwise.hip: residual_partials) takes its chunk count from the caller, and it is kResidualSlots
+// wherever this file chooses it; every workspace holds at least that many slots per particle.
+constexpr int kResidualSlots = 64;
+// the fused step: the forward half's partials, re-summed by the in-launch norm, finalize_norm or the backward prologue
+static int step_parts(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
+{
+    return op->kind == OP_IDENT ? kResidualSlots : (int)parts_per_particle(op, c, h, w);
+}
+// scoring: inpainting, the identity and phase retrieval score through the generic residual pass
+static int score_parts(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
+{
+    if (op->kind == OP_IDENT || op->kind == OP_MASK || op->kind == OP_PHASE) return kResidualSlots;
+    return (int)parts_per_particle(op, c, h, w);
+}
+
 static inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 static int64_t meas_elems(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
@@ -375,22 +249,9 @@ static int64_t meas_elems(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
     return c * oh * ow;
 }
 
-// workspace layout: [partials | scratch A (measurement-sized) | scratch B (image-sized) | op private]
-int64_t dpsx_op_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
-{
-    if (!op || n < 0 || c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
-    const int64_t m = meas_elems(op, c, h, w);
-    if (m < 0) return DPSX_EINVAL;
-    int64_t parts = std::max<int64_t>(parts_per_particle(op, c, h, w), 64);
-    int64_t bytes = align256(n * parts * 4);
-    if (op->kind == OP_SEP || op->kind == OP_TAPS) bytes += blur_adjoint_scratch_bytes(op, n * c, h, w);
-    if (op->kind == OP_PHASE || op->kind == OP_IDENT || op->kind == OP_MASK) {
-        bytes += align256(n * m * 4) + align256(n * c * h * w * 4);
-        if (op->kind == OP_PHASE) bytes += phase_workspace_bytes(op, n * c);
-    }
-    return bytes;
-}
-
+// THE workspace layout of an operator: [partials | the kind's own part].  Blur: the adjoint's padded-domain scratch.
+// Phase, identity, mask (the ops with unfused routes): scratch A (measurement-sized), scratch B (image-sized), then
+// whatever remains -- phase's transform buffer.  Resize: nothing.
 struct Ws {
     float *partials;
     float *meas;   // measurement-sized scratch (only for unfused ops)
@@ -399,31 +260,50 @@ struct Ws {
     int64_t priv_bytes;
 };
 
+// carves `base` of ws_bytes (nullable: sizes only) and returns the bytes needed, or a negative DPSX_E* code
+static int64_t op_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, char *base, int64_t ws_bytes, Ws *o)
+{
+    const int64_t m = meas_elems(op, c, h, w);
+    if (m < 0) return DPSX_EINVAL;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) {
+        char *p = base ? base + off : nullptr;
+        off += bytes;
+        return p;
+    };
+    Ws k{};
+    k.partials = reinterpret_cast<float *>(take(align256(n * std::max<int64_t>(parts_per_particle(op, c, h, w), kResidualSlots) * 4)));
+    switch (op->kind) {
+    case OP_SEP:
+    case OP_TAPS:
+        k.priv_bytes = blur_adjoint_scratch_bytes(op, n * c, h, w);
+        k.priv = take(k.priv_bytes);
+        break;
+    case OP_PHASE:
+    case OP_IDENT:
+    case OP_MASK:
+        k.meas = reinterpret_cast<float *>(take(align256(n * m * 4)));
+        k.img = reinterpret_cast<float *>(take(align256(n * c * h * w * 4)));
+        k.priv_bytes = ws_bytes - off;
+        k.priv = take(op->kind == OP_PHASE ? phase_workspace_bytes(op, n * c) : 0);
+        break;
+    }
+    if (o) *o = k;
+    return off;
+}
+
+int64_t dpsx_op_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
+{
+    if (!op || n < 0 || c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
+    return op_carve(op, n, c, h, w, nullptr, 0, nullptr);
+}
+
+// the launch path's form: the caller checked the geometry (check_geom)
 static int carve(const dpsx_op *op, void *ws, int64_t ws_bytes, int64_t n, int64_t c, int64_t h, int64_t w, Ws &o)
 {
-    const int64_t need = dpsx_op_workspace_bytes(op, n, c, h, w);
+    const int64_t need = op_carve(op, n, c, h, w, static_cast<char *>(ws), ws_bytes, &o);
     if (need < 0) return DPSX_EINVAL;
     if (!ws || ws_bytes < need || !aligned16(ws)) return DPSX_EWORKSPACE;
-    char *p = static_cast<char *>(ws);
-    const int64_t parts = std::max<int64_t>(parts_per_particle(op, c, h, w), 64);
-    o.partials = reinterpret_cast<float *>(p);
-    p += align256(n * parts * 4);
-    o.meas = o.img = nullptr;
-    o.priv = nullptr;
-    o.priv_bytes = 0;
-    if (op->kind == OP_SEP || op->kind == OP_TAPS) {
-        o.priv = p;
-        o.priv_bytes = blur_adjoint_scratch_bytes(op, n * c, h, w);
-    }
-    if (op->kind == OP_PHASE || op->kind == OP_IDENT || op->kind == OP_MASK) {
-        const int64_t m = meas_elems(op, c, h, w);
-        o.meas = reinterpret_cast<float *>(p);
-        p += align256(n * m * 4);
-        o.img = reinterpret_cast<float *>(p);
-        p += align256(n * c * h * w * 4);
-        o.priv = p;
-        o.priv_bytes = ws_bytes - (p - static_cast<char *>(ws));
-    }
     return DPSX_OK;
 }
 
@@ -433,7 +313,7 @@ static bool rows_ok(int64_t rows, int64_t n) { return rows == 1 || rows == n || 
 static int check_geom(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
 {
     if (!op || n < 0 || c < 1 || h < 1 || w < 1) return DPSX_EINVAL;
-    if (op->kind == OP_MASK && !rows_ok(op->mask_n, n)) return DPSX_EINVAL;
+    if (op->kind == OP_MASK && !rows_ok(op->mask.rows, n)) return DPSX_EINVAL;
     if (n * c > (1 << 24)) return DPSX_EUNSUPPORTED;
     int64_t oh, ow;
     return dpsx_op_out_shape(op, h, w, &oh, &ow);
@@ -450,7 +330,7 @@ int dpsx_op_forward_f32(dpsx_op *op, const float *x, float *y, int64_t n, int64_
     case OP_SEP:
     case OP_TAPS: return blur_forward(op, x, y, n * c, h, w, s);
     case OP_RESIZE: return resize_forward(op, x, y, n * c, s);
-    case OP_MASK: return mask_mul(x, op->mask, y, n * c, h * w, s, c, row_div(op->mask_n, n));
+    case OP_MASK: return mask_mul(x, op->mask.mask, y, n * c, h * w, s, c, row_div(op->mask.rows, n));
     case OP_IDENT:
         DPSX_HIP_TRY(hipMemcpyAsync(y, x, (size_t)(n * c * h * w) * 4, hipMemcpyDeviceToDevice, s));
         return DPSX_OK;
@@ -478,7 +358,7 @@ int dpsx_op_adjoint_f32(dpsx_op *op, const float *u, const float *x, float *g, i
         return blur_adjoint(op, u, g, n * c, h, w, static_cast<float *>(ws.priv), ws.priv_bytes, s);
     }
     case OP_RESIZE: return resize_adjoint(op, u, g, n * c, s);
-    case OP_MASK: return mask_mul(u, op->mask, g, n * c, h * w, s, c, row_div(op->mask_n, n));
+    case OP_MASK: return mask_mul(u, op->mask.mask, g, n * c, h * w, s, c, row_div(op->mask.rows, n));
     case OP_IDENT:
         DPSX_HIP_TRY(hipMemcpyAsync(g, u, (size_t)(n * c * h * w) * 4, hipMemcpyDeviceToDevice, s));
         return DPSX_OK;
@@ -527,14 +407,12 @@ int64_t dpsx_step_resid_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h
     }
 }
 
+// the fused inpainting step has the 16-byte form only (common.h: vec_ok): whole float4 units per plane, so that a unit
+// has one mask row, as well as per particle; ptrs: the launch's buffers beside the mask
 static bool mask_fused_ok(const dpsx_op *op, int64_t c, int64_t h, int64_t w,
                           std::initializer_list<const void *> ptrs)
 {
-    if ((h * w) % 4 != 0 || (c * h * w) % 4 != 0) return false;
-    if (!aligned16(op->mask)) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
+    return (h * w) % 4 == 0 && aligned16(op->mask.mask) && vec_ok(c * h * w, ptrs);
 }
 
 int dpsx_step_draws_in_kernel(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
@@ -545,7 +423,7 @@ int dpsx_step_draws_in_kernel(const dpsx_op *op, int64_t c, int64_t h, int64_t w
     case OP_MASK: return (h * w) % 4 == 0 && (c * h * w) % 4 == 0;
     case OP_SEP:
     case OP_TAPS: return blur_step_draws_in_kernel(op, h, w) ? 1 : 0;
-    case OP_RESIZE: return h == op->in_h && w == op->in_w && resize_step_draws_in_kernel(op) ? 1 : 0;
+    case OP_RESIZE: return h == op->resize->in_h && w == op->resize->in_w && resize_step_draws_in_kernel(op) ? 1 : 0;
     default: return 0;       // phase retrieval: fill + pointer form
     }
 }
@@ -583,17 +461,17 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
     StepFwdArgs a{x_t, model_out, noise, y, y_n, x0_hat, sample, inside, static_cast<float *>(resid),
                   ws.partials, n, c, h, w, k};
     a.y_div = row_div(y_n, n);
-    a.mask_div = row_div(op->mask_n, n);
+    a.mask_div = row_div(op->mask.rows, n);
     a.use_rng = rng != nullptr;
     a.rng = rk;
-    int parts = (int)parts_per_particle(op, c, h, w);
+    const int parts = step_parts(op, c, h, w);
     // norm != NULL: the launch itself finishes the per-particle reduction (each particle's last block re-sums its
     // partials in the order of k_finalize_norm -- bit-identical, no extra launch; common.h: NormTail)
     bool tail_done = false;
     if (norm && op->d_counters && n <= kTailMaxParticles && op->kind != OP_PHASE) {
         a.tail.counters = op->d_counters;
         a.tail.partials = ws.partials;
-        a.tail.parts = op->kind == OP_IDENT ? 64 : parts;
+        a.tail.parts = parts;
         a.tail.out = norm;
         tail_done = true;
     }
@@ -606,14 +484,13 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
         // kernels.py mirrors mask_fused_ok) and GaussianDiffusion._fusion_plan then runs the step per op under autograd --
         // S1, dpsx_op_forward_f32, dpsx_residual_norm_f32 and their VJPs; a caller that launches anyway gets the refusal
         if (!mask_fused_ok(op, c, h, w, {x_t, model_out, noise, y, x0_hat, sample}) ||
-            (reinterpret_cast<uintptr_t>(inside) & 3u) != 0)
+            !aligned4(inside))
             return DPSX_EUNSUPPORTED;
         rc = mask_step_fwd(op, a, parts, s);
         break;
     case OP_IDENT:
         rc = posterior_fwd(x_t, model_out, noise, a.use_rng, rk, x0_hat, sample, inside, n, chw, k, s);
         if (rc != DPSX_OK) return rc;
-        parts = 64;
         rc = residual_partials(y, y_n, x0_hat, static_cast<float *>(resid), ws.partials, n, chw, parts, s, 0, nullptr, 0, 1,
                                a.tail);
         break;
@@ -678,9 +555,8 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     hipStream_t s = (hipStream_t)stream;
     const Coefs k = to_coefs(coefs_host);
     const int64_t chw = c * h * w;
-    int parts = (int)parts_per_particle(op, c, h, w);
+    const int parts = step_parts(op, c, h, w);
     if (op->kind == OP_IDENT || op->kind == OP_PHASE) {
-        if (op->kind == OP_IDENT) parts = 64;
         // (the hand-written spectral phase step finalises the norm in its backward launch's prologue)
         if (!norm && !(op->kind == OP_PHASE && phase_norm_in_bwd(op))) {     // no fused prologue: finalise with the small kernel
             if ((rc = finalize_norm(ws.partials, parts, norm_out, n, s)) != DPSX_OK) return rc;
@@ -690,22 +566,21 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     StepBwdArgs b{static_cast<const float *>(resid), norm, ws.partials, parts, norm_out, inside, x0_hat, y, y_n,
                   scale, power, g_model_out, n, c, h, w, k, g_x0_extra};
     b.y_div = row_div(y_n, n);
-    b.mask_div = row_div(op->mask_n, n);
+    b.mask_div = row_div(op->mask.rows, n);
     switch (op->kind) {
     case OP_SEP:
     case OP_TAPS: return blur_step_bwd(op, b, static_cast<float *>(ws.priv), ws.priv_bytes, s);
     case OP_RESIZE: return resize_step_bwd(op, b, s);
     case OP_MASK:
         if (!x0_hat || !y || !rows_ok(y_n, n)) return DPSX_EINVAL;
-        if (!mask_fused_ok(op, c, h, w, {x0_hat, y, g_model_out}) || (reinterpret_cast<uintptr_t>(inside) & 3u))
+        if (!mask_fused_ok(op, c, h, w, {x0_hat, y, g_model_out}) || !aligned4(inside))
             return DPSX_EUNSUPPORTED;
         return mask_step_bwd(op, b, s);
     case OP_IDENT:
         return clamp_scale_to_eps(static_cast<const float *>(resid), norm, inside, scale, power, g_model_out, n,
                                   chw, k, s, g_x0_extra);
     case OP_PHASE:
-        if (phase_vec4_ok(op) && aligned16(g_model_out) && aligned16(g_x0_extra) &&
-            (reinterpret_cast<uintptr_t>(inside) & 3u) == 0)
+        if (phase_vec4_ok(op) && vec_ok(h, {g_model_out, g_x0_extra}) && aligned4(inside))   // (h % 4 == 0: phase_vec4_ok)
             return phase_step_bwd_fused(op, const_cast<float *>(static_cast<const float *>(resid)), b, s);
         if (phase_is_spectral(op)) return DPSX_EUNSUPPORTED;     // its buffers have no unaligned form
         rc = phase_step_bwd(op, const_cast<float *>(static_cast<const float *>(resid)), ws.img, n * c, s);
@@ -959,7 +834,7 @@ static int score_launch(dpsx_op *op, const Ws &ws, const float *x, const float *
     case OP_RESIZE: return resize_score(op, x, y, y_n, ws.partials, n, c, l1, s);
     case OP_IDENT: return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1);
     case OP_MASK:      // y - mask * x in the reduction itself (one launch, no scratch)
-        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, op->mask, h * w, op->mask_n);
+        return residual_partials(y, y_n, x, nullptr, ws.partials, n, chw, parts, s, l1, op->mask.mask, h * w, op->mask.rows);
     case OP_PHASE: {
         // A x into scratch, then the generic residual reduction
         const int64_t m = meas_elems(op, c, h, w);
@@ -970,12 +845,6 @@ static int score_launch(dpsx_op *op, const Ws &ws, const float *x, const float *
     }
     default: return DPSX_EUNSUPPORTED;
     }
-}
-
-static int score_parts(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
-{
-    if (op->kind == OP_IDENT || op->kind == OP_MASK || op->kind == OP_PHASE) return 64;
-    return (int)parts_per_particle(op, c, h, w);
 }
 
 static CostArgs cost_args(const Ws &ws, int parts, int l1, const float *prev, int potential, float *raw_out, float *costs,
@@ -1083,7 +952,7 @@ static int search_step_impl(dpsx_op *op, const float *x_t, const float *model_ou
         return gather_f32(sample, best_idx_dev, x_next, images * beam, n, chw, s);
     }
     static const bool unfused = getenv("DPSX_SEARCH_ONE_UNFUSED") != nullptr;       // A/B switch for tools/kbench_search.py
-    if (one_state && !unfused && x_next && chw % 4 == 0 && aligned16(sample) && aligned16(x_next))
+    if (one_state && !unfused && x_next && vec_ok(chw, {sample, x_next}))
         return finalize_select_copy(fin, (int)images, sample, x_next, chw, s);   // costs + select + the winners' copies: one launch
     rc = finalize_select(fin, (int)images, s);
     if (rc != DPSX_OK || !x_next) return rc;

@@ -17,7 +17,10 @@
 // Blocks are numbered so that the tiles of one plane share blockIdx % 8, i.e.
 // one XCD and its L2 (halo re-reads then hit L2, not HBM).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <new>
+#include <type_traits>
 
 #include "common.h"
 
@@ -1208,15 +1211,144 @@ __global__ __launch_bounds__(NT) void k_blur_fold4(FoldArgs f)
 // =====================================================================
 // host dispatch
 // =====================================================================
+// ---------------------------------------------------------------- the operator's tables
+// Everything a blur handle knows, from the kernel alone: no HIP call (blur_create uploads the two run tables).
+BlurTables blur_tables(const float *kernel_host, int ks, int mode)
+{
+    BlurTables b;
+    const int R = ks / 2;
+    auto K = [&](int i, int j) { return kernel_host[i * ks + j]; };
+    // effective support: largest |offset| with a non-zero tap (the Gaussian sigma=3 kernel
+    // occupies 25x25 of its 61x61 grid) -- smaller halos, same result (0 * x contributes nothing)
+    int reach = 0;
+    double peak = 0.0;
+    int pi = R, pj = R;
+    for (int i = 0; i < ks; ++i)
+        for (int j = 0; j < ks; ++j) {
+            const float v = K(i, j);
+            if (v != 0.0f) reach = std::max(reach, std::max(std::abs(i - R), std::abs(j - R)));
+            if (std::fabs((double)v) > peak) { peak = std::fabs((double)v); pi = i; pj = j; }
+        }
+    b.radius = R;  // the reflection pad is always ks/2 (fold geometry), taps may reach less
+    const int reach4 = std::max(4, (reach + 3) / 4 * 4);
+    b.radius4 = reach4;
+    b.reach = reach;
+    // rank-1 test in double: K ~= col (x) row with col = K[:, pj], row = K[pi, :] / K[pi, pj]
+    b.separable = mode != DPSX_BLUR_FORCE_TAPS && peak > 0.0;
+    std::vector<double> col((size_t)ks), row((size_t)ks);
+    if (b.separable) {
+        for (int i = 0; i < ks; ++i) col[(size_t)i] = K(i, pj);
+        for (int j = 0; j < ks; ++j) row[(size_t)j] = (double)K(pi, j) / (double)K(pi, pj);
+        for (int i = 0; i < ks && b.separable; ++i)
+            for (int j = 0; j < ks; ++j)
+                if (std::fabs(col[(size_t)i] * row[(size_t)j] - (double)K(i, j)) > 1e-6 * peak) {
+                    b.separable = false;
+                    break;
+                }
+    }
+    if (b.separable)
+        for (int d = -reach; d <= reach; ++d) {
+            b.sep.v[reach4 + d] = (float)col[(size_t)(R + d)];
+            b.sep.h[reach4 + d] = (float)row[(size_t)(R + d)];
+        }
+    // per-side halo of the forward tap list (the adjoint swaps top <-> bottom, left <-> right)
+    int ht = 0, hb = 0, hl = 0, hr = 0;
+    for (int i = 0; i < ks; ++i)
+        for (int j = 0; j < ks; ++j)
+            if (K(i, j) != 0.0f) {
+                ht = std::max(ht, R - i); hb = std::max(hb, i - R);
+                hl = std::max(hl, R - j); hr = std::max(hr, j - R);
+            }
+    if (ht + hb < 3) hb = 3 - ht;                                  // a run window spans four rows
+    b.halo_t = ht; b.halo_b = hb;
+    b.halo_l = (hl + 3) / 4 * 4; b.halo_r = (hr + 3) / 4 * 4;
+    // vertical runs of 4 or 2 taps per kernel column, window kept inside [-halo_t, halo_b]; four classes
+    // (dx parity x run length) stored one after the other -- see TapRun
+    std::vector<TapRun> cls_f[4], cls_a[4];
+    for (int j = 0; j < ks; ++j) {
+        const int dx = j - R, odd = dx & 1;
+        int i = 0;
+        while (i < ks) {
+            if (K(i, j) == 0.0f) { ++i; continue; }
+            int k = 0;                                              // consecutive non-zero taps from row i
+            while (i + k < ks && k < 4 && K(i + k, j) != 0.0f) ++k;
+            const int L = k >= 3 ? 4 : 2;
+            const int first = i - R;                               // dy of the run's first tap
+            const int dy0 = std::min(first, b.halo_b - (L - 1));   // shift up so dy0 + L - 1 <= halo_b (>= -halo_t)
+            TapRun r{};
+            r.dy0 = dy0; r.dx = dx;
+            for (int q = 0; q < L; ++q) {
+                const int ii = dy0 + q + R;
+                r.w[q] = (ii >= 0 && ii < ks && ii >= i) ? K(ii, j) : 0.0f;
+            }
+            cls_f[2 * odd + (L == 2)].push_back(r);
+            // adjoint (correlation-transpose): V[p][q] = sum w_t u[p - dy_t][q - dx_t] -> negated offsets
+            // (same dx parity), reversed weights, same loop
+            TapRun t{};
+            t.dy0 = -(dy0 + L - 1); t.dx = -dx;
+            for (int q = 0; q < L; ++q) t.w[q] = r.w[L - 1 - q];
+            cls_a[2 * odd + (L == 2)].push_back(t);
+            i = dy0 + L + R;                                       // first row not covered by this run
+        }
+    }
+    // an even number of runs per class (the pipelined loop works on pairs): a dummy run repeats the last offsets
+    // with zero weights
+    for (int c = 0; c < 4; ++c)
+        if (cls_f[c].size() % 2) {
+            TapRun f = cls_f[c].back(), t = cls_a[c].back();
+            for (int q = 0; q < 4; ++q) f.w[q] = t.w[q] = 0.0f;
+            cls_f[c].push_back(f);
+            cls_a[c].push_back(t);
+        }
+    for (int c = 0; c < 4; ++c) {
+        std::stable_sort(cls_a[c].begin(), cls_a[c].end(), [](const TapRun &x, const TapRun &y) { return x.dx > y.dx; });
+        for (const TapRun &t : cls_a[c]) {
+            b.nrun_adj_pos[c] += t.dx >= 1;
+            b.nrun_adj_neg[c] += t.dx <= -1;
+        }
+        b.nrun[c] = (int)cls_f[c].size();
+        b.fwd.insert(b.fwd.end(), cls_f[c].begin(), cls_f[c].end());
+        b.adj.insert(b.adj.end(), cls_a[c].begin(), cls_a[c].end());
+    }
+    return b;
+}
+
+int blur_create(dpsx_op *op, const float *kernel_host, int ks, int mode)
+{
+    BlurOp *b = new (std::nothrow) BlurOp();
+    if (!b) return DPSX_ENOMEM;
+    b->t = blur_tables(kernel_host, ks, mode);
+    b->d_runs_fwd = b->tables.upload(b->t.fwd);
+    b->d_runs_adj = b->tables.upload(b->t.adj);
+    const int rc = b->tables.rc();
+    if (rc != DPSX_OK) { delete b; return rc; }
+    op->kind = b->t.separable ? OP_SEP : OP_TAPS;
+    op->blur = b;
+    return DPSX_OK;
+}
+
+void blur_destroy(dpsx_op *op)
+{
+    delete op->blur;
+    op->blur = nullptr;
+}
+
+// ---------------------------------------------------------------- launches
+// the ablation build's occupancy probe: extra dynamic LDS per workgroup (DPSX_LDS_PAD bytes)
+static inline size_t ablation_lds_pad()
+{
+#if defined(DPSX_ABLATION) && DPSX_ABLATION
+    static const size_t env_pad = getenv("DPSX_LDS_PAD") ? (size_t)atoi(getenv("DPSX_LDS_PAD")) : 0;
+    return env_pad;
+#else
+    return 0;
+#endif
+}
+
 // small: only the reduction slots (regular multi-tile geometry: no slow folds, which keep 160 tap words in the scratch)
 static inline size_t sep_lds_bytes(int rr, bool small_scratch = false)
 {
-    size_t pad = 0;
-#if defined(DPSX_ABLATION) && DPSX_ABLATION
-    static const size_t env_pad = getenv("DPSX_LDS_PAD") ? (size_t)atoi(getenv("DPSX_LDS_PAD")) : 0;   // occupancy probe
-    pad = env_pad;
-#endif
-    return (size_t)((TH + 2 * rr) * (TW + 2 * rr + 4)) * 4 + (small_scratch ? 256 : kScratchBytes) + pad;
+    return (size_t)((TH + 2 * rr) * (TW + 2 * rr + 4)) * 4 + (small_scratch ? 256 : kScratchBytes) + ablation_lds_pad();
 }
 
 static void fill_geometry(BlurArgs &a, int64_t planes, int64_t c, int64_t h, int64_t w)
@@ -1244,49 +1376,36 @@ int64_t blur_parts_per_particle(const dpsx_op *, int64_t c, int64_t h, int64_t w
     return c * ((h + TH - 1) / TH) * ((w + TW - 1) / TW);
 }
 
-// dynamic LDS above 64 KiB needs the attribute once per kernel symbol
-template <typename K>
-static int allow_lds(K kernel, size_t bytes, bool &done)
+// every blur launch: NT threads, blocks numbered by grid_blocks (common.h: launch_lds)
+template <auto Kernel, class... Args>
+static int launch(const BlurArgs &a, size_t lds, hipStream_t s, const Args &...args)
 {
-    if (!done) {
-        DPSX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(144 * 1024)));
-        done = true;
-    }
-    (void)bytes;
-    return DPSX_OK;
+    return launch_lds<Kernel>(grid_blocks(a), NT, lds, s, a, args...);
 }
 
-#define DPSX_LAUNCH(KERNEL, GRID, LDS, STREAM, ...)                      \
-    do {                                                                  \
-        static bool s_attr_done = false;                                  \
-        int rc_ = allow_lds(&KERNEL, LDS, s_attr_done);                   \
-        if (rc_ != DPSX_OK) return rc_;                                   \
-        hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(NT), LDS, STREAM, __VA_ARGS__); \
-        return check_launch();                                            \
-    } while (0)
-
-template <int R4, bool POST, bool RESID, bool RNG = false>
-static int launch_sep_fwd(const BlurArgs &a, const SepTaps &t, hipStream_t s)
+// radius4 / 4 -> the separable kernels' template argument: f(std::integral_constant<int, R4>) for R4 = 1 ... 8
+template <class F> static int with_r4(int r4, F &&f)
 {
-    const size_t lds = sep_lds_bytes(4 * R4);
-    DPSX_LAUNCH((k_blur_sep_fwd<R4, POST, RESID, RNG>), grid_blocks(a), lds, s, a, t);
+    switch (r4) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return DPSX_EUNSUPPORTED;
 }
 
 template <bool POST, bool RESID, bool RNG = false>
-static int dispatch_sep_fwd(const dpsx_op *op, const BlurArgs &a, hipStream_t s)
+static int dispatch_sep_fwd(const BlurTables &b, const BlurArgs &a, hipStream_t s)
 {
-    switch (op->radius4 / 4) {
-    case 1: return launch_sep_fwd<1, POST, RESID, RNG>(a, op->sep, s);
-    case 2: return launch_sep_fwd<2, POST, RESID, RNG>(a, op->sep, s);
-    case 3: return launch_sep_fwd<3, POST, RESID, RNG>(a, op->sep, s);
-    case 4: return launch_sep_fwd<4, POST, RESID, RNG>(a, op->sep, s);
-    case 5: return launch_sep_fwd<5, POST, RESID, RNG>(a, op->sep, s);
-    case 6: return launch_sep_fwd<6, POST, RESID, RNG>(a, op->sep, s);
-    case 7: return launch_sep_fwd<7, POST, RESID, RNG>(a, op->sep, s);
-    case 8: return launch_sep_fwd<8, POST, RESID, RNG>(a, op->sep, s);
-    }
-    return DPSX_EUNSUPPORTED;
+    return with_r4(b.radius4 / 4, [&](auto r4) {
+        constexpr int R4 = decltype(r4)::value;
+        return launch<k_blur_sep_fwd<R4, POST, RESID, RNG>>(a, sep_lds_bytes(4 * R4), s, b.sep);
+    });
 }
 
 template <int R4, bool EPI>
@@ -1296,9 +1415,9 @@ static int launch_sep_adj(const BlurArgs &a, const SepTaps &t, int reach, hipStr
     const size_t lds = sep_lds_bytes(4 * R4, a.h % TH == 0 && a.w % TW == 0 && a.tiles_x >= 2 && a.tiles_y >= 2);
     // the fused epilogue is compiled with and without the extra cotangent: the default step carries neither its loads nor a branch
     if constexpr (EPI) {
-        if (a.g_extra) DPSX_LAUNCH((k_blur_sep_adj<R4, true, true>), grid_blocks(a), lds, s, a, t, reach);
+        if (a.g_extra) return launch<k_blur_sep_adj<R4, true, true>>(a, lds, s, t, reach);
     }
-    DPSX_LAUNCH((k_blur_sep_adj<R4, EPI, false>), grid_blocks(a), lds, s, a, t, reach);
+    return launch<k_blur_sep_adj<R4, EPI, false>>(a, lds, s, t, reach);
 }
 
 template <int R4, bool EPI>
@@ -1306,63 +1425,39 @@ static int launch_sep_adj_sym(const BlurArgs &a, const SepTaps &t, hipStream_t s
 {
     const size_t lds = sep_lds_bytes(4 * R4, true);
     if constexpr (EPI) {
-        if (a.g_extra) DPSX_LAUNCH((k_blur_sep_adj_sym<R4, true, true>), grid_blocks(a), lds, s, a, t);
+        if (a.g_extra) return launch<k_blur_sep_adj_sym<R4, true, true>>(a, lds, s, t);
     }
-    DPSX_LAUNCH((k_blur_sep_adj_sym<R4, EPI, false>), grid_blocks(a), lds, s, a, t);
+    return launch<k_blur_sep_adj_sym<R4, EPI, false>>(a, lds, s, t);
 }
 
 // symmetric taps on both axes (bitwise), whole tiles, two or more of them per axis, reach inside the image: the adjoint
 // without fold terms (k_blur_sep_adj_sym)
-static bool sep_adj_sym_ok(const dpsx_op *op, const BlurArgs &a)
+static bool sep_adj_sym_ok(const BlurTables &b, const BlurArgs &a)
 {
     static const char *force = getenv("DPSX_SEP_ADJ");          // A/B switch for tools/kbench.py: "fold" = the general kernel
     if (force && force[0] == 'f') return false;
-    const int rr = op->radius4;
+    const int rr = b.radius4;
     if (a.h % TH != 0 || a.w % TW != 0 || a.tiles_x < 2 || a.tiles_y < 2 || rr + 1 >= a.h || rr + 1 >= a.w) return false;
     for (int i = 0; i < rr; ++i)
-        if (op->sep.h[i] != op->sep.h[2 * rr - i] || op->sep.v[i] != op->sep.v[2 * rr - i]) return false;
+        if (b.sep.h[i] != b.sep.h[2 * rr - i] || b.sep.v[i] != b.sep.v[2 * rr - i]) return false;
     return true;
 }
 
 template <bool EPI>
-static int dispatch_sep_adj(const dpsx_op *op, const BlurArgs &a, hipStream_t s)
+static int dispatch_sep_adj(const BlurTables &b, const BlurArgs &a, hipStream_t s)
 {
+    const int rr = b.radius4;
+    const bool sym = sep_adj_sym_ok(b, a);
     SepTaps f{};  // adjoint of a correlation = correlation with the reversed taps
-    const int rr = op->radius4;
-    if (sep_adj_sym_ok(op, a)) {
-        switch (rr / 4) {
-        case 1: return launch_sep_adj_sym<1, EPI>(a, op->sep, s);
-        case 2: return launch_sep_adj_sym<2, EPI>(a, op->sep, s);
-        case 3: return launch_sep_adj_sym<3, EPI>(a, op->sep, s);
-        case 4: return launch_sep_adj_sym<4, EPI>(a, op->sep, s);
-        case 5: return launch_sep_adj_sym<5, EPI>(a, op->sep, s);
-        case 6: return launch_sep_adj_sym<6, EPI>(a, op->sep, s);
-        case 7: return launch_sep_adj_sym<7, EPI>(a, op->sep, s);
-        case 8: return launch_sep_adj_sym<8, EPI>(a, op->sep, s);
+    if (!sym)
+        for (int i = 0; i <= 2 * rr; ++i) {
+            f.h[i] = b.sep.h[2 * rr - i];
+            f.v[i] = b.sep.v[2 * rr - i];
         }
-        return DPSX_EUNSUPPORTED;
-    }
-    for (int i = 0; i <= 2 * rr; ++i) {
-        f.h[i] = op->sep.h[2 * rr - i];
-        f.v[i] = op->sep.v[2 * rr - i];
-    }
-    switch (rr / 4) {
-    case 1: return launch_sep_adj<1, EPI>(a, f, op->reach, s);
-    case 2: return launch_sep_adj<2, EPI>(a, f, op->reach, s);
-    case 3: return launch_sep_adj<3, EPI>(a, f, op->reach, s);
-    case 4: return launch_sep_adj<4, EPI>(a, f, op->reach, s);
-    case 5: return launch_sep_adj<5, EPI>(a, f, op->reach, s);
-    case 6: return launch_sep_adj<6, EPI>(a, f, op->reach, s);
-    case 7: return launch_sep_adj<7, EPI>(a, f, op->reach, s);
-    case 8: return launch_sep_adj<8, EPI>(a, f, op->reach, s);
-    }
-    return DPSX_EUNSUPPORTED;
-}
-
-static void set_taps(const dpsx_op *op, BlurArgs &a)
-{
-    a.runs = static_cast<const TapRun *>(op->d_runs_fwd);
-    for (int k = 0; k < 4; ++k) a.nrun[k] = op->nrun[k];
+    return with_r4(rr / 4, [&](auto r4) {
+        constexpr int R4 = decltype(r4)::value;
+        return sym ? launch_sep_adj_sym<R4, EPI>(a, b.sep, s) : launch_sep_adj<R4, EPI>(a, f, b.reach, s);
+    });
 }
 
 // compile-time LDS row-stride classes of the 16-byte-load variants (0 = runtime stride, the scalar-load variants):
@@ -1376,12 +1471,7 @@ static inline int taps_swc(const TapGeom &g, bool vec)
 static inline size_t taps_lds(const TapGeom &g, int swc)
 {
     const int rh = TH + g.t + g.b, sw = swc > 0 ? swc : TW + g.l + g.r;
-    size_t pad = 0;
-#if defined(DPSX_ABLATION) && DPSX_ABLATION
-    static const size_t env_pad = getenv("DPSX_LDS_PAD") ? (size_t)atoi(getenv("DPSX_LDS_PAD")) : 0;   // occupancy probe
-    pad = env_pad;
-#endif
-    return ((size_t)rh * sw) * 4 + kScratchBytes + pad;
+    return ((size_t)rh * sw) * 4 + kScratchBytes + ablation_lds_pad();
 }
 static inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); }
 
@@ -1393,95 +1483,82 @@ static TapGeom make_geom(int t, int b, int l, int r)
     return g;
 }
 
-template <bool POST, int MODE, bool VEC, int SWC, int NHB, bool RNG = false>
-static int launch_taps_kn(const BlurArgs &a, const TapGeom &g, hipStream_t s)
-{
-    const size_t lds = taps_lds(g, SWC);
-    DPSX_LAUNCH((k_blur_taps<POST, MODE, VEC, SWC, NHB, RNG>), grid_blocks(a), lds, s, a, g);
-}
-
 template <bool POST, int MODE, bool VEC, int SWC, bool RNG = false>
 static int launch_taps_k(const BlurArgs &a, const TapGeom &g, hipStream_t s)
 {
+    const size_t lds = taps_lds(g, SWC);
     if constexpr (VEC && POST) {
         const int halo_units = (g.t + g.b) * ((TW + g.l + g.r) / 4) + TH * ((g.l + g.r) / 4);
-        if (halo_units <= 2 * NT) return launch_taps_kn<POST, MODE, VEC, SWC, 2, RNG>(a, g, s);
+        if (halo_units <= 2 * NT) return launch<k_blur_taps<POST, MODE, VEC, SWC, 2, RNG>>(a, lds, s, g);
     }
-    return launch_taps_kn<POST, MODE, VEC, SWC, 4, RNG>(a, g, s);
+    return launch<k_blur_taps<POST, MODE, VEC, SWC, 4, RNG>>(a, lds, s, g);
 }
 
-template <bool POST, int MODE>
+// RNG (K1 with the noise drawn in the kernel) exists for the 16-byte fused step only: <true, 1, true>
+template <bool POST, int MODE, bool RNG = false>
 static int launch_taps(const BlurArgs &a, const TapGeom &g, bool vec, hipStream_t s)
 {
-    if (!vec) return launch_taps_k<POST, MODE, false, 0>(a, g, s);
-    if (taps_swc(g, true) == kSwNarrow) return launch_taps_k<POST, MODE, true, kSwNarrow>(a, g, s);
-    return launch_taps_k<POST, MODE, true, kSwWide>(a, g, s);
+    if constexpr (!RNG) {
+        if (!vec) return launch_taps_k<POST, MODE, false, 0>(a, g, s);
+    }
+    if (taps_swc(g, true) == kSwNarrow) return launch_taps_k<POST, MODE, true, kSwNarrow, RNG>(a, g, s);
+    return launch_taps_k<POST, MODE, true, kSwWide, RNG>(a, g, s);
 }
 
-template <bool POST, bool RESID>
-static int launch_taps_fwd(const dpsx_op *op, BlurArgs a, bool vec, hipStream_t s)
+// the forward tap list; RNG: 16-byte path on regular geometry only (the caller checked: vec is true)
+template <bool POST, bool RESID, bool RNG = false>
+static int launch_taps_fwd(const BlurOp &op, BlurArgs a, bool vec, hipStream_t s)
 {
-    set_taps(op, a);
-    const TapGeom g = make_geom(op->halo_t, op->halo_b, op->halo_l, op->halo_r);
-    return launch_taps<POST, RESID ? 1 : 0>(a, g, vec, s);
-}
-
-// K1 of the tap list with the noise drawn in the kernel: 16-byte path on regular geometry only (the caller checked)
-static int launch_taps_fwd_rng(const dpsx_op *op, BlurArgs a, hipStream_t s)
-{
-    set_taps(op, a);
-    const TapGeom g = make_geom(op->halo_t, op->halo_b, op->halo_l, op->halo_r);
-    if (taps_swc(g, true) == kSwNarrow) return launch_taps_k<true, 1, true, kSwNarrow, true>(a, g, s);
-    return launch_taps_k<true, 1, true, kSwWide, true>(a, g, s);
+    const BlurTables &b = op.t;
+    a.runs = op.d_runs_fwd;
+    for (int k = 0; k < 4; ++k) a.nrun[k] = b.nrun[k];
+    const TapGeom g = make_geom(b.halo_t, b.halo_b, b.halo_l, b.halo_r);
+    return launch_taps<POST, RESID ? 1 : 0, RNG>(a, g, vec, s);
 }
 
 int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h, int64_t w)
 {
     // the padded-domain buffer of the two-launch adjoint; the separable 16-byte path does not need it
     if (op->kind == OP_SEP && w % 4 == 0 && (h * w) % 4 == 0) return 0;
-    const int64_t r4 = op->radius4;
+    const int64_t r4 = op->blur->t.radius4;
     return ((planes * (h + 2 * r4) * (w + 2 * r4) * 4 + 255) / 256) * 256;
-}
-
-template <bool EPI, int SWC, int PRS>
-static int launch_taps_adj1_kp(const BlurArgs &a, const TapGeom &g, const AdjReach &reach, hipStream_t s)
-{
-    const size_t lds = taps_lds(g, SWC);
-    DPSX_LAUNCH((k_blur_taps_adj<EPI, SWC, PRS>), grid_blocks(a), lds, s, a, g, reach);
 }
 
 template <bool EPI, int SWC>
 static int launch_taps_adj1_k(const BlurArgs &a, const TapGeom &g, const AdjReach &reach, hipStream_t s)
 {
+    const size_t lds = taps_lds(g, SWC);
     // strip width by the taps' horizontal reach (both sides use the same kernel instance)
-    if (std::max(reach.l, reach.r) <= 14) return launch_taps_adj1_kp<EPI, SWC, 2>(a, g, reach, s);
-    return launch_taps_adj1_kp<EPI, SWC, 4>(a, g, reach, s);
+    if (std::max(reach.l, reach.r) <= 14) return launch<k_blur_taps_adj<EPI, SWC, 2>>(a, lds, s, g, reach);
+    return launch<k_blur_taps_adj<EPI, SWC, 4>>(a, lds, s, g, reach);
 }
 
 // regular geometry: one launch on the image domain (k_blur_taps_adj)
 template <bool EPI>
-static int launch_taps_adj1(const dpsx_op *op, BlurArgs a, hipStream_t s)
+static int launch_taps_adj1(const BlurOp &op, BlurArgs a, hipStream_t s)
 {
-    a.runs = static_cast<const TapRun *>(op->d_runs_adj);
+    const BlurTables &b = op.t;
+    a.runs = op.d_runs_adj;
     for (int k = 0; k < 4; ++k) {
-        a.nrun[k] = op->nrun[k];
-        a.nhlo[k] = op->nrun_adj_pos[k];      // (as counts: runs with dx >= 1 lead the class, runs with dx <= -1 end it)
-        a.nhhi[k] = op->nrun_adj_neg[k];
+        a.nrun[k] = b.nrun[k];
+        a.nhlo[k] = b.nrun_adj_pos[k];      // (as counts: runs with dx >= 1 lead the class, runs with dx <= -1 end it)
+        a.nhhi[k] = b.nrun_adj_neg[k];
     }
     // negated offsets: the forward halos swap sides; at least 11 zero rows / 4 zero columns for the clamped mirrored windows
-    const AdjReach reach{op->halo_b, op->halo_t, op->halo_r, op->halo_l};
+    const AdjReach reach{b.halo_b, b.halo_t, b.halo_r, b.halo_l};
     const TapGeom g = make_geom(std::max(reach.t, 11), std::max(reach.b, 11), std::max(reach.l, 4), std::max(reach.r, 4));
     if (taps_swc(g, true) == kSwNarrow) return launch_taps_adj1_k<EPI, kSwNarrow>(a, g, reach, s);
     return launch_taps_adj1_k<EPI, kSwWide>(a, g, reach, s);
 }
 
 template <bool EPI>
-static int launch_taps_adj(const dpsx_op *op, BlurArgs a, bool vec, float *scratch, int64_t scratch_bytes,
+static int launch_taps_adj(const BlurOp &op, BlurArgs a, bool vec, float *scratch, int64_t scratch_bytes,
                            hipStream_t s)
 {
-    if (vec && a.h % TH == 0 && a.w % TW == 0 && (!EPI || (aligned16(a.g_extra) && (reinterpret_cast<uintptr_t>(a.inside_r) & 3u) == 0)))
+    const BlurTables &b = op.t;
+    if (vec && a.h % TH == 0 && a.w % TW == 0 && (!EPI || (aligned16(a.g_extra) && aligned4(a.inside_r))))
         return launch_taps_adj1<EPI>(op, a, s);
-    const int r4 = op->radius4;
+    const int r4 = b.radius4;
     const int ph = a.h + 2 * r4, pw = a.w + 2 * r4;
     if (!scratch || scratch_bytes < (int64_t)a.planes * ph * pw * 4) return DPSX_EWORKSPACE;
     // 1. V = C^T u on the padded domain
@@ -1489,9 +1566,9 @@ static int launch_taps_adj(const dpsx_op *op, BlurArgs a, bool vec, float *scrat
     c.x = a.x; c.out = scratch;
     fill_geometry(c, a.planes, 1, ph, pw);
     c.src_h = a.h; c.src_w = a.w; c.src_off = r4;
-    c.runs = static_cast<const TapRun *>(op->d_runs_adj);
-    for (int k = 0; k < 4; ++k) c.nrun[k] = op->nrun[k];
-    const TapGeom g = make_geom(op->halo_b, op->halo_t, op->halo_r, op->halo_l);      // negated offsets: the sides swap
+    c.runs = op.d_runs_adj;
+    for (int k = 0; k < 4; ++k) c.nrun[k] = b.nrun[k];
+    const TapGeom g = make_geom(b.halo_b, b.halo_t, b.halo_r, b.halo_l);      // negated offsets: the sides swap
     const bool v2 = vec && aligned16(scratch);
     {
         int rc = launch_taps<false, 2>(c, g, v2, s);
@@ -1502,9 +1579,9 @@ static int launch_taps_adj(const dpsx_op *op, BlurArgs a, bool vec, float *scrat
     f.v = scratch; f.g = a.out; f.norm_in = a.norm_in; f.norm_partials = a.norm_partials; f.norm_parts = a.norm_parts;
     f.norm_out = a.norm_out; f.inside = a.inside_r; f.g_extra = a.g_extra; f.g_model_out = a.g_model_out; f.scale = a.scale;
     f.neg_b = -a.k.b; f.power = a.power; f.c = a.c; f.h = a.h; f.w = a.w; f.ph = ph; f.pw = pw; f.off = r4;
-    f.reach = op->reach;
+    f.reach = b.reach;
     const bool vec4 = v2 && a.w % 4 == 0 && pw % 4 == 0 && r4 % 4 == 0 && aligned16(EPI ? (const void *)a.g_model_out : (const void *)a.out) &&
-                      aligned16(a.g_extra) && (reinterpret_cast<uintptr_t>(a.inside_r) & 3u) == 0;
+                      aligned16(a.g_extra) && aligned4(a.inside_r);
     if (vec4) {
         const dim3 grid4((unsigned)((a.h * (a.w / 4) + NT - 1) / NT), (unsigned)a.planes);
         hipLaunchKernelGGL(k_blur_fold4<EPI>, grid4, dim3(NT), 0, s, f);
@@ -1518,15 +1595,13 @@ static int launch_taps_adj(const dpsx_op *op, BlurArgs a, bool vec, float *scrat
 static bool geometry_ok(const dpsx_op *op, int64_t h, int64_t w)
 {
     // ReflectionPad2d requires pad < dim (torch raises otherwise)
-    return h > op->radius && w > op->radius && h < (1 << 15) && w < (1 << 15);
+    return h > op->blur->t.radius && w > op->blur->t.radius && h < (1 << 15) && w < (1 << 15);
 }
 
-static bool vec_ok(int64_t h, int64_t w, std::initializer_list<const void *> ptrs)
+// the 16-byte form of a blur launch (common.h: vec_ok): whole float4 units per row as well as per plane
+static bool blur_vec(int64_t h, int64_t w, std::initializer_list<const void *> ptrs)
 {
-    if (w % 4 != 0 || (h * w) % 4 != 0) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
+    return w % 4 == 0 && vec_ok(h * w, ptrs);
 }
 
 int blur_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, int64_t h, int64_t w, hipStream_t s)
@@ -1536,9 +1611,9 @@ int blur_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, in
     BlurArgs a{};
     a.x = x; a.out = y;
     fill_geometry(a, planes, 1, h, w);
-    const bool vec = vec_ok(h, w, {x, y});
-    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<false, false>(op, a, s)
-                                     : launch_taps_fwd<false, false>(op, a, vec, s);
+    const bool vec = blur_vec(h, w, {x, y});
+    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<false, false>(op->blur->t, a, s)
+                                     : launch_taps_fwd<false, false>(*op->blur, a, vec, s);
 }
 
 int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, int64_t h, int64_t w, float *scratch,
@@ -1549,9 +1624,9 @@ int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, in
     BlurArgs a{};
     a.x = u; a.out = g;
     fill_geometry(a, planes, 1, h, w);
-    const bool vec = vec_ok(h, w, {u, g});
-    return op->kind == OP_SEP && vec ? dispatch_sep_adj<false>(op, a, s)
-                                     : launch_taps_adj<false>(op, a, vec, scratch, scratch_bytes, s);
+    const bool vec = blur_vec(h, w, {u, g});
+    return op->kind == OP_SEP && vec ? dispatch_sep_adj<false>(op->blur->t, a, s)
+                                     : launch_taps_adj<false>(*op->blur, a, vec, scratch, scratch_bytes, s);
 }
 
 // K1 with the noise drawn in the kernel exists on REGULAR geometry -- whole 64 x 64 tiles, the halo shorter than both
@@ -1560,8 +1635,9 @@ int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, in
 bool blur_step_draws_in_kernel(const dpsx_op *op, int64_t h, int64_t w)
 {
     if (!geometry_ok(op, h, w) || h % TH != 0 || w % TW != 0) return false;
-    if (op->kind == OP_SEP) return op->radius4 < h && op->radius4 < w && op->radius4 / 4 >= 1 && op->radius4 / 4 <= 8;
-    return std::max(op->halo_t, op->halo_b) < h && std::max(op->halo_l, op->halo_r) < w;
+    const BlurTables &b = op->blur->t;
+    if (op->kind == OP_SEP) return b.radius4 < h && b.radius4 < w && b.radius4 / 4 >= 1 && b.radius4 / 4 <= 8;
+    return std::max(b.halo_t, b.halo_b) < h && std::max(b.halo_l, b.halo_r) < w;
 }
 
 int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
@@ -1576,14 +1652,15 @@ int blur_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     fill_geometry(a, f.n * f.c, f.c, f.h, f.w);
     a.tail = f.tail;
     a.tail.blocks_per_particle = a.c * a.tiles_x * a.tiles_y;
-    const bool vec = vec_ok(f.h, f.w, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample, f.y, f.resid}) &&
-                     (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
+    const bool vec = blur_vec(f.h, f.w, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample, f.y, f.resid}) && aligned4(f.inside);
     if (f.use_rng) {
         if (!vec || !blur_step_draws_in_kernel(op, f.h, f.w)) return DPSX_EUNSUPPORTED;      // nothing launched
         a.rng = f.rng;
-        return op->kind == OP_SEP ? dispatch_sep_fwd<true, true, true>(op, a, s) : launch_taps_fwd_rng(op, a, s);
+        return op->kind == OP_SEP ? dispatch_sep_fwd<true, true, true>(op->blur->t, a, s)
+                                  : launch_taps_fwd<true, true, true>(*op->blur, a, true, s);
     }
-    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<true, true>(op, a, s) : launch_taps_fwd<true, true>(op, a, vec, s);
+    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<true, true>(op->blur->t, a, s)
+                                     : launch_taps_fwd<true, true>(*op->blur, a, vec, s);
 }
 
 int blur_step_bwd(const dpsx_op *op, const StepBwdArgs &b, float *scratch, int64_t scratch_bytes, hipStream_t s)
@@ -1596,9 +1673,9 @@ int blur_step_bwd(const dpsx_op *op, const StepBwdArgs &b, float *scratch, int64
     a.inside_r = b.inside; a.g_extra = b.g_extra; a.g_model_out = b.g_model_out; a.scale = b.scale; a.power = b.power;
     a.k = b.k;
     fill_geometry(a, b.n * b.c, b.c, b.h, b.w);
-    const bool vec = vec_ok(b.h, b.w, {b.resid, b.g_model_out, b.g_extra}) && (reinterpret_cast<uintptr_t>(b.inside) & 3u) == 0;
-    return op->kind == OP_SEP && vec ? dispatch_sep_adj<true>(op, a, s)
-                                     : launch_taps_adj<true>(op, a, vec, scratch, scratch_bytes, s);
+    const bool vec = blur_vec(b.h, b.w, {b.resid, b.g_model_out, b.g_extra}) && aligned4(b.inside);
+    return op->kind == OP_SEP && vec ? dispatch_sep_adj<true>(op->blur->t, a, s)
+                                     : launch_taps_adj<true>(*op->blur, a, vec, scratch, scratch_bytes, s);
 }
 
 int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, float *partials, int64_t n,
@@ -1610,8 +1687,9 @@ int blur_score(const dpsx_op *op, const float *x, const float *y, int64_t y_n, f
     a.x = x; a.y = y; a.y_div = row_div(y_n, n); a.out = nullptr; a.partials = partials;
     fill_geometry(a, n * c, c, h, w);
     a.l1 = l1;
-    const bool vec = vec_ok(h, w, {x, y});
-    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<false, true>(op, a, s) : launch_taps_fwd<false, true>(op, a, vec, s);
+    const bool vec = blur_vec(h, w, {x, y});
+    return op->kind == OP_SEP && vec ? dispatch_sep_fwd<false, true>(op->blur->t, a, s)
+                                     : launch_taps_fwd<false, true>(*op->blur, a, vec, s);
 }
 
 }  // namespace dpsx

@@ -4,6 +4,7 @@
 #include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
+#include <vector>
 
 #include "../../include/dpsx.h"
 
@@ -34,6 +35,65 @@ inline int check_launch()
     } while (0)
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }   // the clamp gate's bytes, read as uchar4
+
+// THE rule of the 16-byte (float4) form of a launch: `size` -- the particle, the plane or the row, whatever the kernel
+// steps through in units of four -- is a multiple of 4 and every buffer of the launch is 16-byte aligned; ptrs: every
+// buffer read or written, null = not read (counts as aligned).  Sites with a further condition state it beside the call.
+inline bool vec_ok(int64_t size, std::initializer_list<const void *> ptrs)
+{
+    if (size % 4) return false;
+    for (const void *p : ptrs)
+        if (p && !aligned16(p)) return false;
+    return true;
+}
+
+// -------------------------------------------------------------------- host: launches with large dynamic LDS
+// Dynamic LDS above 64 KiB needs the attribute once per kernel symbol: the kernel is a template argument, so every symbol
+// has its own flag.  launch_lds<k_name<...>>(grid, threads, lds_bytes, stream, kernel arguments...)
+constexpr int kMaxDynamicLds = 144 * 1024;
+template <auto Kernel, class... Args>
+int launch_lds(unsigned grid, unsigned threads, size_t lds, hipStream_t s, const Args &...args)
+{
+    static bool attr_done = false;
+    if (!attr_done) {
+        DPSX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         kMaxDynamicLds));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, args...);
+    return check_launch();
+}
+
+// -------------------------------------------------------------------- host: an operator's device tables
+// Owns the read-only tables an operator uploads when it is created and frees them when it goes.  upload() returns the
+// device copy (one element is allocated for an empty table) or null after a failure; rc() is the first failure's code,
+// so a constructor uploads everything and asks once.
+class DeviceTables {
+public:
+    DeviceTables() = default;
+    DeviceTables(const DeviceTables &) = delete;
+    DeviceTables &operator=(const DeviceTables &) = delete;
+    ~DeviceTables() { for (void *p : allocs_) (void)hipFree(p); }
+    template <class T> const T *upload(const std::vector<T> &v)
+    {
+        void *p = nullptr;
+        if (rc_ == DPSX_OK) rc_ = put(&p, v.data(), v.size() * sizeof(T));
+        return rc_ == DPSX_OK ? static_cast<const T *>(p) : nullptr;
+    }
+    int rc() const { return rc_; }
+
+private:
+    int put(void **p, const void *src, size_t bytes)
+    {
+        DPSX_HIP_TRY(hipMalloc(p, bytes ? bytes : 1));
+        allocs_.push_back(*p);
+        if (bytes) DPSX_HIP_TRY(hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice));
+        return DPSX_OK;
+    }
+    std::vector<void *> allocs_;
+    int rc_ = DPSX_OK;
+};
 
 // -------------------------------------------------------------------- S1 point math
 // Reference op order, one rounding per ATen op (no FMA contraction), so the
@@ -415,6 +475,9 @@ __device__ __forceinline__ int reflect_idx(int i, int n)
 }  // namespace dpsx
 
 // -------------------------------------------------------------------- op object
+// dpsx_op is the kind, the arrival counters and one typed owner per kind.  Each kind's state is built, owned and read by
+// its own translation unit -- blur.hip (blur_create: the tap tables), resize.hip (resize_create: the gather tables and
+// blockings), phase.hip (phase_create: plans and twiddles) -- and api.hip reads only the shapes declared here.
 enum { OP_TAPS = 0, OP_SEP = 1, OP_RESIZE = 2, OP_MASK = 3, OP_IDENT = 4, OP_PHASE = 5 };
 
 constexpr int kMaxRadius = 32;  // kernel side <= 65
@@ -433,37 +496,54 @@ struct SepTaps {  // passed by value -> SGPRs
     float v[2 * kMaxRadius + 1];
 };
 
-struct dpsx_op {
-    int kind = OP_IDENT;
-    // ---- blur
-    int ks = 0, radius = 0;               // radius = ks/2 = the reflection pad
-    int reach = 0, radius4 = 0;           // reach: largest |offset| of a non-zero tap; radius4: reach rounded up to 4
-    SepTaps sep{};                        // centred at index radius4 (zero padded)
-    int nnz = 0;
-    int *d_tap_dy = nullptr, *d_tap_dx = nullptr;  // sparse non-zero taps, row-major order
-    float *d_tap_w = nullptr;
-    // the same taps as vertical runs of <= 4 (TapRun records): what the tap-list kernels iterate over
-    void *d_runs_fwd = nullptr, *d_runs_adj = nullptr;
-    int nruns = 0;
-    int nrun[4] = {0, 0, 0, 0};           // runs per class (even/odd dx) x (4/2 taps), in table order
+namespace dpsx {
+
+// What blur.hip: blur_tables() derives from (kernel, ks, mode) on the host, no HIP call.  The run tables are what the
+// tap-list kernels iterate over: every blur has them (a separable one takes them for shapes the 16-byte loader cannot take)
+struct BlurTables {
+    bool separable = false;               // rank 1 (and not DPSX_BLUR_FORCE_TAPS): OP_SEP, else OP_TAPS
+    int radius = 0;                       // ks / 2 = the reflection pad
+    int reach = 0, radius4 = 0;           // reach: largest |offset| of a non-zero tap; radius4: reach rounded up to 4 (>= 4)
+    SepTaps sep{};                        // centred at index radius4 (zero padded); separable only
+    std::vector<TapRun> fwd, adj;         // the runs by class (see TapRun), the same count in both
+    int nrun[4] = {0, 0, 0, 0};           // runs per class (even/odd dx) x (4/2 taps), in table order: always even
     // the ADJOINT table is sorted by dx, descending, inside each class: its first nrun_adj_pos[c] runs have dx >= 1 (the only
     // ones a left-border strip can use), its last nrun_adj_neg[c] have dx <= -1 (right border)
     int nrun_adj_pos[4] = {0, 0, 0, 0}, nrun_adj_neg[4] = {0, 0, 0, 0};
     // halo the tap list actually needs on each side of a tile (rows as they are, columns rounded up to 4): a motion
     // path usually leaves the centre in one direction, so this is about half of radius4 per axis
     int halo_t = 0, halo_b = 0, halo_l = 0, halo_r = 0;
-    // ---- resize
+};
+
+struct BlurOp {                            // blur.hip
+    BlurTables t;
+    const TapRun *d_runs_fwd = nullptr, *d_runs_adj = nullptr;
+    DeviceTables tables;
+};
+
+struct ResizeOp {                          // resize.hip extends it with its tables and blockings (ResizeHost)
     int64_t in_h = 0, in_w = 0, out_h = 0, out_w = 0, taps_h = 0, taps_w = 0;
-    float *d_w_h = nullptr;  // resize.hip keeps its table owner (ResizeHost*) here
-    // ---- mask: [mask_n, h, w], particle p of n uses mask p / (n / mask_n)
+};
+
+struct PhaseOp {                           // phase.hip extends it with its plans and twiddles (PhaseHost)
+    int64_t h = 0, pad = 0, planes = 0;    // image side, zero pad per side, the batch the first plan is built for
+};
+
+struct MaskOp {                            // [rows, h, w] on the device, not owned: particle p of n uses row p / (n / rows)
     const float *mask = nullptr;
-    int64_t mask_n = 1;
-    // ---- "last block done" arrival counters (see NormTail): kNormCounterBytes, zero between launches
+    int64_t rows = 1, h = 0, w = 0;
+};
+
+}  // namespace dpsx
+
+struct dpsx_op {
+    int kind = OP_IDENT;
+    dpsx::BlurOp *blur = nullptr;          // OP_SEP, OP_TAPS
+    dpsx::ResizeOp *resize = nullptr;      // OP_RESIZE
+    dpsx::PhaseOp *phase = nullptr;        // OP_PHASE
+    dpsx::MaskOp mask{};                   // OP_MASK (every other kind: one row, so row_div(mask.rows, n) == 0)
+    // "last block done" arrival counters (see NormTail): kNormCounterBytes, zero between launches
     unsigned *d_counters = nullptr;
-    // ---- phase
-    int64_t pr_h = 0, pr_pad = 0, pr_planes = 0;
-    void *fft_plan = nullptr;  // hipfftHandle stored as integer
-    bool has_plan = false;
 };
 
 // kernels implemented across the .hip files (all enqueue on `s`, return a DPSX_* code)
@@ -479,7 +559,7 @@ struct StepFwdArgs {
     int64_t n, c, h, w;
     Coefs k;
     NormTail tail{};  // the norm finished inside the launch (tail.counters == nullptr: not requested / not supported)
-    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
+    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask.rows, n)
     bool use_rng = false;               // draw the noise in the kernel from `rng` (noise is then null)
     RngK rng{};
 };
@@ -498,10 +578,13 @@ struct StepBwdArgs {
     int64_t n, c, h, w;
     Coefs k;
     const float *g_extra = nullptr;   // optional extra cotangent on x0_hat [n, c, h, w], added before the clamp gate
-    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask_n, n)
+    unsigned y_div = 0, mask_div = 0;   // row_div(y_n, n), row_div(op->mask.rows, n)
 };
 
 // blur.hip
+BlurTables blur_tables(const float *kernel_host, int ks, int mode);        // pure host: 1 <= ks <= 2 kMaxRadius + 1, odd
+int blur_create(dpsx_op *op, const float *kernel_host, int ks, int mode);  // sets op->kind and op->blur
+void blur_destroy(dpsx_op *op);
 int blur_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, int64_t h, int64_t w, hipStream_t s);
 int blur_adjoint(const dpsx_op *op, const float *u, float *g, int64_t planes, int64_t h, int64_t w, float *scratch,
                  int64_t scratch_bytes, hipStream_t s);
@@ -516,7 +599,9 @@ int64_t blur_parts_per_particle(const dpsx_op *op, int64_t c, int64_t h, int64_t
 
 
 // resize.hip
-int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float *w_w, const int64_t *i_w);
+// shape: the sizes and tap counts (checked by the caller); the tables are host arrays [taps, out]
+int resize_create(dpsx_op *op, const ResizeOp &shape, const float *w_h, const int64_t *i_h, const float *w_w,
+                  const int64_t *i_w);
 void resize_destroy(dpsx_op *op);
 int64_t resize_parts_per_particle(const dpsx_op *op, int64_t c);
 int resize_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, hipStream_t s);
@@ -649,7 +734,7 @@ int repulse(bool apply, float c, float bandwidth, const float *x, float *out, fl
             uint8_t *applied, int64_t n, int64_t chw, int64_t segments, void *workspace, hipStream_t s);
 
 // phase.hip
-int phase_create(dpsx_op *op);
+int phase_create(dpsx_op *op, const PhaseOp &shape);
 void phase_destroy(dpsx_op *op);
 int64_t phase_workspace_bytes(const dpsx_op *op, int64_t planes);
 // amp = |F(pad(x))| ; spec (optional) receives the centred complex spectrum, interleaved re/im

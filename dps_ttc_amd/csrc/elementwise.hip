@@ -81,8 +81,7 @@ int posterior_fwd(const float *x, const float *mo, const float *z, bool use_rng,
 {
     if (n == 0 || chw == 0) return DPSX_OK;
     const unsigned xs = one_state ? row_div(states, n) : 1u;
-    const bool vec = chw % 4 == 0 && aligned16(x) && aligned16(mo) && (use_rng || aligned16(z)) && aligned16(x0) &&
-                     aligned16(sample) && (reinterpret_cast<uintptr_t>(inside) & 3u) == 0;
+    const bool vec = vec_ok(chw, {x, mo, use_rng ? nullptr : z, x0, sample}) && aligned4(inside);
     const dim3 grid = grid_for(vec ? chw / 4 : chw, n);
     if (vec && use_rng) k_posterior_fwd<true, true><<<grid, kThreads, 0, s>>>(x, mo, r, x0, sample, inside, chw, k, xs);
     else if (vec) k_posterior_fwd<true><<<grid, kThreads, 0, s>>>(x, mo, z, x0, sample, inside, chw, k, xs);
@@ -122,7 +121,7 @@ int randn_f32(float *out, uint32_t *bits, int64_t n, int64_t chw, const RngK &r,
 {
     if (n == 0 || chw == 0) return DPSX_OK;
     const int64_t units = (chw + 3) / 4;
-    if (chw % 4 == 0 && aligned16(out)) k_randn<true><<<grid_for(units, n), kThreads, 0, s>>>(out, bits, chw, units, r);
+    if (vec_ok(chw, {out})) k_randn<true><<<grid_for(units, n), kThreads, 0, s>>>(out, bits, chw, units, r);
     else k_randn<false><<<grid_for(units, n), kThreads, 0, s>>>(out, bits, chw, units, r);
     return check_launch();
 }
@@ -194,8 +193,7 @@ int posterior_bwd(const float *g_x0, const float *g_s, const float *x, const flo
                   float *g_x, float *g_mo, int64_t n, int64_t chw, const Coefs &k, hipStream_t s)
 {
     if (n == 0 || chw == 0) return DPSX_OK;
-    const bool vec = chw % 4 == 0 && aligned16(g_x0) && aligned16(g_s) && aligned16(x) && aligned16(mo) && aligned16(z) &&
-                     aligned16(g_x) && aligned16(g_mo);
+    const bool vec = vec_ok(chw, {g_x0, g_s, x, mo, z, g_x, g_mo});
     if (vec) k_posterior_bwd<4><<<grid_for(chw / 4, n), kThreads, 0, s>>>(g_x0, g_s, x, mo, z, g_x, g_mo, chw, k);
     else k_posterior_bwd<1><<<grid_for(chw, n), kThreads, 0, s>>>(g_x0, g_s, x, mo, z, g_x, g_mo, chw, k);
     return check_launch();
@@ -645,7 +643,7 @@ int step_update(const float *sample, const float *g_mo, const float *g_unet, flo
 {
     if (n == 0 || chw == 0) return DPSX_OK;
     const float ratio = -k.a / k.b;
-    const bool vec = chw % 4 == 0 && aligned16(sample) && aligned16(g_mo) && aligned16(g_unet) && aligned16(x_next);
+    const bool vec = vec_ok(chw, {sample, g_mo, g_unet, x_next});
     if (vec)
         k_step_update<true><<<grid_for(chw / 4, n), kThreads, 0, s>>>(sample, g_mo, g_unet, x_next, chw, ratio);
     else
@@ -732,8 +730,8 @@ int mask_step_fwd(const dpsx_op *op, const StepFwdArgs &f, int parts, hipStream_
     const int64_t chw = f.c * f.h * f.w;
     StepFwdArgs a = f;
     a.tail.blocks_per_particle = parts;
-    if (a.use_rng) k_mask_step_fwd<true><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
-    else k_mask_step_fwd<false><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
+    if (a.use_rng) k_mask_step_fwd<true><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask.mask, chw, a.h * a.w);
+    else k_mask_step_fwd<false><<<dim3(parts, (unsigned)a.n), kThreads, 0, s>>>(a, op->mask.mask, chw, a.h * a.w);
     return check_launch();
 }
 
@@ -770,7 +768,7 @@ __global__ __launch_bounds__(kThreads) void k_mask_step_bwd(StepBwdArgs a, const
 int mask_step_bwd(const dpsx_op *op, const StepBwdArgs &a, hipStream_t s)
 {
     const int64_t chw = a.c * a.h * a.w;
-    k_mask_step_bwd<<<grid_for(chw / 4, a.n), kThreads, 0, s>>>(a, op->mask, chw, a.h * a.w);
+    k_mask_step_bwd<<<grid_for(chw / 4, a.n), kThreads, 0, s>>>(a, op->mask.mask, chw, a.h * a.w);
     return check_launch();
 }
 
@@ -998,7 +996,7 @@ int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t 
                       int64_t chw, hipStream_t s)
 {
     if (n_out == 0 || chw == 0) return DPSX_OK;
-    if (chw % 4 == 0 && aligned16(src) && aligned16(dst)) {
+    if (vec_ok(chw, {src, dst})) {
         const dim3 grid((unsigned)((chw / 4 + kThreads - 1) / kThreads), (unsigned)((n_out + kRepl - 1) / kRepl));
         k_replicate_seg<<<grid, kThreads, 0, s>>>(src, ids, dst, n_out, (unsigned)per, n_src, chw / 4);
     } else {
@@ -1010,7 +1008,7 @@ int replicate_seg_f32(const float *src, const int64_t *ids, float *dst, int64_t 
 int gather_f32(const float *src, const int64_t *ids, float *dst, int64_t n_out, int64_t n_src, int64_t chw, hipStream_t s)
 {
     if (n_out == 0 || chw == 0) return DPSX_OK;
-    if (chw % 4 == 0 && aligned16(src) && aligned16(dst))
+    if (vec_ok(chw, {src, dst}))
         k_gather<<<grid_for(chw / 4, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw / 4);
     else
         k_gather_scalar<<<grid_for(chw, n_out), kThreads, 0, s>>>(src, ids, dst, n_src, chw);

@@ -8,12 +8,11 @@
 //
 // Work items are units of 16 bytes per lane where the particle size is a multiple of 4 and every buffer read or written is
 // 16-byte aligned (every particle's base is then aligned too), else single elements: the scalar instantiation of the same
-// body, chosen on the host (vec_ok).
+// body, chosen on the host (common.h: vec_ok).
 #pragma once
 
 #include "common.h"
 
-#include <initializer_list>
 #include <type_traits>
 
 namespace dpsx {
@@ -59,15 +58,6 @@ __device__ __forceinline__ Range block_range(int64_t units, int64_t per)
 }
 
 // ------------------------------------------------------------------ host side
-// the vector form's rule for particles of `size` elements; ptrs: every buffer of the pass, null = not read
-inline bool vec_ok(int64_t size, std::initializer_list<const void *> ptrs)
-{
-    if (size % 4) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
-}
-
 // the launch geometry: the particle's work items (float4 units or elements) split evenly over its slots
 struct PassGeom { int64_t per; dim3 grid; };
 inline PassGeom pass_geom(int64_t size, bool vec, int64_t n)

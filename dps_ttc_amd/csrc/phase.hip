@@ -12,7 +12,10 @@
 // s = h + 2*pad is even, so both shifts are a roll by s/2.
 #include <hipfft/hipfft.h>
 
+#include <cmath>
+#include <cstdlib>
 #include <map>
+#include <new>
 
 #include "common.h"
 #include "phase_fft.h"
@@ -22,20 +25,21 @@ namespace dpsx {
 constexpr int PT = 256;
 constexpr int kChunk = 4096;  // spectrum elements per block in the reducing pass
 
-struct PhaseHost {
+struct PhaseHost : PhaseOp {                // what dpsx_op::phase points at
     std::map<int64_t, hipfftHandle> plans;  // batch * 4 + kind -> plan   (kind: 0 C2C, 1 R2C, 2 C2R)
-    float2 *d_tw = nullptr;                 // exp(-2 pi i t / 384) for the hand-written spectral step
+    const float2 *d_tw = nullptr;           // exp(-2 pi i t / 384) for the hand-written spectral step (in `tables`)
+    DeviceTables tables;
+    ~PhaseHost() { for (auto &kv : plans) (void)hipfftDestroy(kv.second); }
 };
 
-static PhaseHost *host_of(const dpsx_op *op) { return static_cast<PhaseHost *>(op->fft_plan); }
+static PhaseHost *host_of(const dpsx_op *op) { return static_cast<PhaseHost *>(op->phase); }
 
 // the hand-written three-pass spectral step (phase_fft.h) covers the BASELINE geometry: 256 x 256, oversample 2.0
 static bool spectral(const dpsx_op *op)
 {
     static const bool off = getenv("DPSX_PHASE_LIBRARY_FFT") != nullptr;      // A/B switch for tools/kbench.py
-    return !off && op->pr_h == prfft::IMG && op->pr_pad == prfft::PADW && host_of(op) && host_of(op)->d_tw;
+    return !off && host_of(op)->d_tw;        // (the twiddles exist for that geometry only: phase_create)
 }
-
 
 // A/B switch (tools/kbench.py): the round-2 passes B and C of the hand-written spectral step
 static bool phase_v1()
@@ -50,7 +54,7 @@ static int get_plan(dpsx_op *op, int64_t planes, hipfftHandle *out, int kind = 0
     PhaseHost *h = host_of(op);
     auto it = h->plans.find(planes * 4 + kind);
     if (it != h->plans.end()) { *out = it->second; return DPSX_OK; }
-    const int s = (int)(op->pr_h + 2 * op->pr_pad);
+    const int s = (int)(h->h + 2 * h->pad);
     int dims[2] = {s, s};
     hipfftHandle plan;
     const hipfftType type = kind == 0 ? HIPFFT_C2C : (kind == 1 ? HIPFFT_R2C : HIPFFT_C2R);
@@ -62,22 +66,22 @@ static int get_plan(dpsx_op *op, int64_t planes, hipfftHandle *out, int kind = 0
     return DPSX_OK;
 }
 
-int phase_create(dpsx_op *op)
+int phase_create(dpsx_op *op, const PhaseOp &shape)
 {
-    op->fft_plan = new PhaseHost();
-    op->has_plan = true;
+    PhaseHost *h = new (std::nothrow) PhaseHost();
+    if (!h) return DPSX_ENOMEM;
+    static_cast<PhaseOp &>(*h) = shape;
+    op->phase = h;
     hipfftHandle p;
-    int rc = get_plan(op, op->pr_planes, &p);  // build the plan for the expected batch up front
-    if (rc == DPSX_OK && op->pr_h == prfft::IMG && op->pr_pad == prfft::PADW) {
-        float2 tw[prfft::N];
+    int rc = get_plan(op, shape.planes, &p);  // build the plan for the expected batch up front
+    if (rc == DPSX_OK && shape.h == prfft::IMG && shape.pad == prfft::PADW) {
+        std::vector<float2> tw((size_t)prfft::N);
         for (int t = 0; t < prfft::N; ++t) {
             const double a = -2.0 * 3.14159265358979323846 * (double)t / (double)prfft::N;
-            tw[t] = make_float2((float)cos(a), (float)sin(a));
+            tw[(size_t)t] = make_float2((float)cos(a), (float)sin(a));
         }
-        PhaseHost *h = host_of(op);
-        if (hipMalloc((void **)&h->d_tw, sizeof(tw)) != hipSuccess ||
-            hipMemcpy(h->d_tw, tw, sizeof(tw), hipMemcpyHostToDevice) != hipSuccess)
-            rc = DPSX_ENOMEM;
+        h->d_tw = h->tables.upload(tw);
+        rc = h->tables.rc();
     }
     if (rc != DPSX_OK) phase_destroy(op);
     return rc;
@@ -85,17 +89,13 @@ int phase_create(dpsx_op *op)
 
 void phase_destroy(dpsx_op *op)
 {
-    PhaseHost *h = host_of(op);
-    if (!h) return;
-    for (auto &kv : h->plans) (void)hipfftDestroy(kv.second);
-    if (h->d_tw) (void)hipFree(h->d_tw);
-    delete h;
-    op->fft_plan = nullptr;
+    delete host_of(op);
+    op->phase = nullptr;
 }
 
 int64_t phase_workspace_bytes(const dpsx_op *op, int64_t planes)
 {
-    const int64_t s = op->pr_h + 2 * op->pr_pad;
+    const int64_t s = op->phase->h + 2 * op->phase->pad;
     return (planes * s * s * 8 + 255) / 256 * 256;
 }
 
@@ -105,7 +105,7 @@ int64_t phase_workspace_bytes(const dpsx_op *op, int64_t planes)
 // Half the FFT work and half the spectrum traffic of the complex-to-complex form (which the plain operator calls keep).
 int64_t phase_parts_per_particle(const dpsx_op *op, int64_t c)
 {
-    const int64_t s = op->pr_h + 2 * op->pr_pad;
+    const int64_t s = op->phase->h + 2 * op->phase->pad;
     if (spectral(op)) return c * ((prfft::HS + prfft::CT - 1) / prfft::CT);    // one partial per column tile
     return c * ((s * (s / 2 + 1) + kChunk - 1) / kChunk);
 }
@@ -113,7 +113,7 @@ int64_t phase_parts_per_particle(const dpsx_op *op, int64_t c)
 // fused-step scratch: [planes][s][s] real | [planes][s][s/2 + 1] complex
 int64_t phase_step_resid_bytes(const dpsx_op *op, int64_t planes)
 {
-    const int64_t s = op->pr_h + 2 * op->pr_pad;
+    const int64_t s = op->phase->h + 2 * op->phase->pad;
     return (planes * s * s * 4 + 255) / 256 * 256 + (planes * s * (s / 2 + 1) * 8 + 255) / 256 * 256;
 }
 
@@ -352,7 +352,7 @@ static int run_fft(dpsx_op *op, float2 *buf, int64_t planes, int dir, hipStream_
 
 static int spectrum_of(dpsx_op *op, const float *x, float2 *buf, int64_t planes, hipStream_t s)
 {
-    const int h = (int)op->pr_h, pad = (int)op->pr_pad, sz = h + 2 * pad;
+    const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     k_phase_pre<<<dim3((sz * sz + PT - 1) / PT, (unsigned)planes), PT, 0, s>>>(x, buf, h, pad, sz);
     int rc = check_launch();
     if (rc != DPSX_OK) return rc;
@@ -364,7 +364,7 @@ int phase_forward(dpsx_op *op, const float *x, float *amp, float *spec, int64_t 
 {
     if (planes == 0) return DPSX_OK;
     if (!ws || ws_bytes < phase_workspace_bytes(op, planes)) return DPSX_EWORKSPACE;
-    const int sz = (int)(op->pr_h + 2 * op->pr_pad);
+    const int sz = (int)(op->phase->h + 2 * op->phase->pad);
     float2 *buf = static_cast<float2 *>(ws);
     int rc = spectrum_of(op, x, buf, planes, s);
     if (rc != DPSX_OK) return rc;
@@ -379,7 +379,7 @@ int phase_adjoint(dpsx_op *op, const float *u, const float *x, float *g, int64_t
 {
     if (planes == 0) return DPSX_OK;
     if (!ws || ws_bytes < phase_workspace_bytes(op, planes)) return DPSX_EWORKSPACE;
-    const int h = (int)op->pr_h, pad = (int)op->pr_pad, sz = h + 2 * pad;
+    const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float2 *buf = static_cast<float2 *>(ws);
     int rc = spectrum_of(op, x, buf, planes, s);
     if (rc != DPSX_OK) return rc;
@@ -395,7 +395,7 @@ bool phase_is_spectral(const dpsx_op *op) { return spectral(op); }
 
 bool phase_vec4_ok(const dpsx_op *op)
 {
-    const int64_t h = op->pr_h, pad = op->pr_pad, sz = h + 2 * pad;
+    const int64_t h = op->phase->h, pad = op->phase->pad, sz = h + 2 * pad;
     return h % 4 == 0 && pad % 4 == 0 && (sz / 2) % 4 == 0;
 }
 
@@ -403,13 +403,13 @@ int phase_step_fwd(dpsx_op *op, const StepFwdArgs &f, float *resid_c, hipStream_
 {
     const int64_t n = f.n, c = f.c, planes = n * c;
     if (planes == 0) return DPSX_OK;
-    const int h = (int)op->pr_h, pad = (int)op->pr_pad, sz = h + 2 * pad;
+    const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
                                               (planes * sz * sz * 4 + 255) / 256 * 256);
     int rc;
-    const bool vec = phase_vec4_ok(op) && aligned16(f.x_t) && aligned16(f.model_out) && aligned16(f.noise) &&
-                     aligned16(f.x0_hat) && aligned16(f.sample) && (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
+    // (vec_ok's size test is phase_vec4_ok's h % 4 == 0)
+    const bool vec = phase_vec4_ok(op) && vec_ok(h, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) && aligned4(f.inside);
     if (spectral(op) && !vec) return DPSX_EUNSUPPORTED;   // the partial-sum layout is fixed per operator
     if (vec && spectral(op)) {       // passes A and B of the hand-written spectral step (phase_fft.h)
         float2 *hbuf = reinterpret_cast<float2 *>(resid_c);
@@ -471,7 +471,7 @@ int phase_step_bwd_fused(dpsx_op *op, float *resid_c, const StepBwdArgs &b, hipS
             b.scale, b.power, -b.k.b, b.g_model_out, host_of(op)->d_tw, (int)b.c);
         return check_launch();
     }
-    const int h = (int)op->pr_h, pad = (int)op->pr_pad, sz = h + 2 * pad;
+    const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
                                               (planes * sz * sz * 4 + 255) / 256 * 256);
@@ -488,7 +488,7 @@ int phase_step_bwd_fused(dpsx_op *op, float *resid_c, const StepBwdArgs &b, hipS
 int phase_step_bwd(dpsx_op *op, float *resid_c, float *g_x0, int64_t planes, hipStream_t s)
 {
     if (planes == 0) return DPSX_OK;
-    const int h = (int)op->pr_h, pad = (int)op->pr_pad, sz = h + 2 * pad;
+    const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
                                               (planes * sz * sz * 4 + 255) / 256 * 256);

@@ -281,7 +281,7 @@ int resample_seg(const float *d, const float *u, int64_t segments, int64_t k, fl
                  hipStream_t s)
 {
     const ResampleOpts o = opts ? *opts : ResampleOpts{};
-    const bool vec = chw % 4 == 0 && aligned16(src) && aligned16(dst);
+    const bool vec = vec_ok(chw, {src, dst});
     const int64_t units = vec ? chw / 4 : chw;
     const int64_t per_block = (int64_t)kThreads * (vec ? kResampleVecPer : kResampleScalarPer);
     const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)(segments * k));

@@ -14,6 +14,9 @@
 //             of input rows); u (the small measurement-space tensor) is read
 //             once into LDS, g is written with coalesced rows.
 #include <algorithm>
+#include <cstdlib>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "common.h"
@@ -786,22 +789,10 @@ __global__ __launch_bounds__(RT) void k_resize_adj(ResizeArgs a, ResizeDev d)
 }
 
 // ---------------------------------------------------------------- host
-struct ResizeHost {
+struct ResizeHost : ResizeOp {      // what dpsx_op::resize points at
     ResizeDev dev{};
-    std::vector<void *> allocs;
+    DeviceTables tables;            // owns every table dev points into
 };
-
-template <typename T>
-static int upload(ResizeHost *h, const std::vector<T> &v, const T **out)
-{
-    void *p = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    DPSX_HIP_TRY(hipMalloc(&p, bytes));
-    h->allocs.push_back(p);
-    if (!v.empty()) DPSX_HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T *>(p);
-    return DPSX_OK;
-}
 
 static void build_inverse(const float *w, const int64_t *idx, int64_t taps, int64_t n_out, int64_t n_in,
                           std::vector<int> &ptr, std::vector<int> &oidx, std::vector<float> &ow)
@@ -825,33 +816,49 @@ static void build_inverse(const float *w, const int64_t *idx, int64_t taps, int6
         }
 }
 
-constexpr size_t kLdsBudget = 96 * 1024;
+constexpr size_t kLdsBudget = 96 * 1024, kLdsLimit = 150 * 1024;
 
-int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float *w_w, const int64_t *i_w)
+// The dynamic LDS of the three launch forms, in bytes: the one statement of each, for resize_create's blocking search
+// and for the launchers.
+// k_resize_fwd: `rows` staged input rows (padded to float4) and their W-pass rows, the tables of a block of tp output rows
+static size_t fwd_lds(const ResizeDev &d, int rows, int tp)
 {
-    auto *h = new ResizeHost();
+    return ((size_t)rows * ((d.in_w + 3) / 4 * 4 + d.out_w) + 32 + 2 * (size_t)(d.taps_w * d.out_w + d.taps_h * tp)) * 4;
+}
+// k_resize_fwd_rows: four streamed rows per wave instead of the staged input rows
+static size_t fwd_rows_lds(const ResizeDev &d)
+{
+    return ((size_t)4 * 256 + (size_t)d.fwd_rows * d.out_w + 16 + 2 * (size_t)(d.taps_h * d.tp)) * 4;
+}
+// k_resize_adj: `rows` staged rows of u and the ti rows of the W pass, the W inverse and max_he entries of the H inverse
+static size_t adj_lds(const ResizeDev &d, int rows, int ti, int max_he)
+{
+    return ((size_t)(rows + ti) * d.out_w + 2 * (size_t)(d.ell_w * d.in_w + max_he) + ti + 8) * 4;
+}
+
+int resize_create(dpsx_op *op, const ResizeOp &shape, const float *w_h, const int64_t *i_h, const float *w_w,
+                  const int64_t *i_w)
+{
+    std::unique_ptr<ResizeHost> h(new (std::nothrow) ResizeHost());
+    if (!h) return DPSX_ENOMEM;
+    static_cast<ResizeOp &>(*h) = shape;
     ResizeDev &d = h->dev;
-    d.in_h = (int)op->in_h; d.in_w = (int)op->in_w; d.out_h = (int)op->out_h; d.out_w = (int)op->out_w;
-    d.taps_h = (int)op->taps_h; d.taps_w = (int)op->taps_w;
-    for (int64_t i = 0; i < op->taps_h * op->out_h; ++i)
-        if (i_h[i] < 0 || i_h[i] >= op->in_h) { delete h; return DPSX_EINVAL; }
-    for (int64_t i = 0; i < op->taps_w * op->out_w; ++i)
-        if (i_w[i] < 0 || i_w[i] >= op->in_w) { delete h; return DPSX_EINVAL; }
-    std::vector<float> vwh(w_h, w_h + op->taps_h * op->out_h), vww(w_w, w_w + op->taps_w * op->out_w);
-    std::vector<int> vih((size_t)(op->taps_h * op->out_h)), viw((size_t)(op->taps_w * op->out_w));
-    for (size_t i = 0; i < vih.size(); ++i) vih[i] = (int)i_h[i];
-    for (size_t i = 0; i < viw.size(); ++i) viw[i] = (int)i_w[i];
-    int rc;
-#define UP(vec, field) if ((rc = upload(h, vec, &d.field)) != DPSX_OK) { for (void *p : h->allocs) (void)hipFree(p); delete h; return rc; }
-    UP(vwh, w_h) UP(vww, w_w) UP(vih, i_h) UP(viw, i_w)
-    std::vector<int> ptr, oi;
-    std::vector<float> ow;
-    build_inverse(w_h, i_h, op->taps_h, op->out_h, op->in_h, ptr, oi, ow);
-    std::vector<int> hp = ptr, hi = oi;
-    std::vector<float> hw = ow;
-    UP(hp, inv_h_ptr) UP(hi, inv_h_idx) UP(hw, inv_h_w)
-    build_inverse(w_w, i_w, op->taps_w, op->out_w, op->in_w, ptr, oi, ow);
-    UP(ptr, inv_w_ptr) UP(oi, inv_w_idx) UP(ow, inv_w_w)
+    DeviceTables &t = h->tables;
+    d.in_h = (int)shape.in_h; d.in_w = (int)shape.in_w; d.out_h = (int)shape.out_h; d.out_w = (int)shape.out_w;
+    d.taps_h = (int)shape.taps_h; d.taps_w = (int)shape.taps_w;
+    for (int64_t i = 0; i < shape.taps_h * shape.out_h; ++i)
+        if (i_h[i] < 0 || i_h[i] >= shape.in_h) return DPSX_EINVAL;
+    for (int64_t i = 0; i < shape.taps_w * shape.out_w; ++i)
+        if (i_w[i] < 0 || i_w[i] >= shape.in_w) return DPSX_EINVAL;
+    std::vector<float> vwh(w_h, w_h + shape.taps_h * shape.out_h), vww(w_w, w_w + shape.taps_w * shape.out_w);
+    std::vector<int> vih(i_h, i_h + shape.taps_h * shape.out_h), viw(i_w, i_w + shape.taps_w * shape.out_w);
+    d.w_h = t.upload(vwh); d.w_w = t.upload(vww); d.i_h = t.upload(vih); d.i_w = t.upload(viw);
+    std::vector<int> hp, hi, ptr, oi;     // the CSR inverses: H (hp / hi / hw) and W (ptr / oi / ow)
+    std::vector<float> hw, ow;
+    build_inverse(w_h, i_h, shape.taps_h, shape.out_h, shape.in_h, hp, hi, hw);
+    d.inv_h_ptr = t.upload(hp); d.inv_h_idx = t.upload(hi); d.inv_h_w = t.upload(hw);
+    build_inverse(w_w, i_w, shape.taps_w, shape.out_w, shape.in_w, ptr, oi, ow);
+    d.inv_w_ptr = t.upload(ptr); d.inv_w_idx = t.upload(oi); d.inv_w_w = t.upload(ow);
     d.nnz_w = (int)ow.size();
     {   // ELL copy of the W inverse: same entry order per column (deterministic), zero padded
         int ell = 1;
@@ -865,7 +872,7 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
                 ew[(size_t)k * d.in_w + j] = ow[(size_t)e];
             }
         d.ell_w = ell;
-        UP(ei, ell_w_idx) UP(ew, ell_w_w)
+        d.ell_w_idx = t.upload(ei); d.ell_w_w = t.upload(ew);
     }
     {   // ELL copy of the H inverse (hp / hi / hw: CSR by input row): fixed-width rows let the adjoint's H pass run with a
         // compile-time entry count -- no per-row trip counts, no dependent pointer loads at the head of every workgroup
@@ -882,7 +889,7 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
             }
         }
         d.ell_h = ell;
-        UP(ei, ell_h_idx) UP(ew, ell_h_w)
+        d.ell_h_idx = t.upload(ei); d.ell_h_w = t.upload(ew);
     }
 
     // ---- forward blocking: largest tp (<= 16) whose staged rows fit the LDS budget
@@ -903,7 +910,7 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
             cnt[(size_t)b] = mx - mn + 1;
             maxrows = std::max(maxrows, mx - mn + 1);
         }
-        return ((size_t)maxrows * ((d.in_w + 3) / 4 * 4 + d.out_w) + 32 + 2 * (size_t)(d.taps_w * d.out_w + d.taps_h * tp)) * 4;
+        return fwd_lds(d, maxrows, tp);
     };
     int best_tp = 0;
     std::vector<int> blo, bcnt, own;
@@ -912,12 +919,12 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
         const size_t lds = fwd_blocking(tp, blo, bcnt, own, maxrows);
         if (lds <= kLdsBudget || tp == 1) {
             best_tp = tp; d.fwd_rows = maxrows;
-            if (lds > 150 * 1024) { for (void *p : h->allocs) (void)hipFree(p); delete h; return DPSX_EUNSUPPORTED; }
+            if (lds > kLdsLimit) return DPSX_EUNSUPPORTED;
             break;
         }
     }
     d.tp = best_tp;
-    UP(blo, blk_lo) UP(bcnt, blk_cnt) UP(own, own_lo)
+    d.blk_lo = t.upload(blo); d.blk_cnt = t.upload(bcnt); d.own_lo = t.upload(own);
     // the finer forward blocking (see ResizeDev): blocks of exactly RT outputs, when the coarse ones are 2 or 4 of them
     d.gparts = 1; d.tp2 = d.tp; d.fwd_rows2 = d.fwd_rows; d.blk_lo2 = d.blk_lo; d.blk_cnt2 = d.blk_cnt; d.own_lo2 = d.own_lo;
     if (RT % d.out_w == 0 && d.out_h % d.tp == 0) {
@@ -927,7 +934,7 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
             int maxrows2 = 0;
             (void)fwd_blocking(tp2, blo2, bcnt2, own2, maxrows2);        // fewer staged rows than the coarse one: fits
             d.gparts = d.tp / tp2; d.tp2 = tp2; d.fwd_rows2 = maxrows2;
-            UP(blo2, blk_lo2) UP(bcnt2, blk_cnt2) UP(own2, own_lo2)
+            d.blk_lo2 = t.upload(blo2); d.blk_cnt2 = t.upload(bcnt2); d.own_lo2 = t.upload(own2);
         }
     }
     // ---- adjoint blocking: the largest ti (<= ti_max) whose staged rows fit the LDS budget
@@ -951,37 +958,31 @@ int resize_create(dpsx_op *op, const float *w_h, const int64_t *i_h, const float
             int max_he = 1;
             for (int b = 0; b < nblk; ++b)
                 max_he = std::max(max_he, hp[(size_t)std::min(d.in_h, (b + 1) * ti)] - hp[(size_t)(b * ti)]);
-            const size_t lds = ((size_t)(maxrows + ti) * d.out_w + 2 * (size_t)(d.ell_w * d.in_w + max_he) + ti + 8) * 4;
+            const size_t lds = adj_lds(d, maxrows, ti, max_he);
             if (lds <= kLdsBudget || ti == 1) {
                 best_ti = ti; rows = maxrows; alo = lo; acnt = cnt; he = max_he;
-                return lds <= 150 * 1024;
+                return lds <= kLdsLimit;
             }
         }
         return false;
     };
     std::vector<int> alo, acnt, alo2, acnt2;
     if (!adj_blocking(64, d.ti, d.adj_rows, d.max_he, alo, acnt) ||
-        !adj_blocking(std::max(1, std::min(16, d.ti / 4)), d.ti2, d.adj_rows2, d.max_he2, alo2, acnt2)) {
-        for (void *p : h->allocs) (void)hipFree(p);
-        delete h;
+        !adj_blocking(std::max(1, std::min(16, d.ti / 4)), d.ti2, d.adj_rows2, d.max_he2, alo2, acnt2))
         return DPSX_EUNSUPPORTED;
-    }
-    UP(alo, ablk_lo) UP(acnt, ablk_cnt) UP(alo2, ablk_lo2) UP(acnt2, ablk_cnt2)
-#undef UP
-    op->d_w_h = reinterpret_cast<float *>(h);  // opaque owner pointer (see resize_destroy)
+    d.ablk_lo = t.upload(alo); d.ablk_cnt = t.upload(acnt); d.ablk_lo2 = t.upload(alo2); d.ablk_cnt2 = t.upload(acnt2);
+    if (t.rc() != DPSX_OK) return t.rc();
+    op->resize = h.release();
     return DPSX_OK;
 }
 
 void resize_destroy(dpsx_op *op)
 {
-    auto *h = reinterpret_cast<ResizeHost *>(op->d_w_h);
-    if (!h) return;
-    for (void *p : h->allocs) (void)hipFree(p);
-    delete h;
-    op->d_w_h = nullptr;
+    delete static_cast<ResizeHost *>(op->resize);
+    op->resize = nullptr;
 }
 
-static const ResizeDev &dev_of(const dpsx_op *op) { return reinterpret_cast<const ResizeHost *>(op->d_w_h)->dev; }
+static const ResizeDev &dev_of(const dpsx_op *op) { return static_cast<const ResizeHost *>(op->resize)->dev; }
 
 int64_t resize_parts_per_particle(const dpsx_op *op, int64_t c)
 {
@@ -1009,27 +1010,19 @@ static int64_t resize_fwd_blocks_per_particle(const dpsx_op *op, int64_t c, int6
     return c * ((d.out_h + d.tp - 1) / d.tp) * (fwd_fine(d, planes) ? d.gparts : 1);
 }
 
-template <typename K>
-static int allow_lds(K kernel, bool &done)
+// the launch record of a forward launch over `planes` planes: under the fine blocking, one partial per block, in the
+// slots the coarse blocks would have filled
+static ResizeDev fwd_dev(const dpsx_op *op, int64_t planes)
 {
-    if (!done) {
-        DPSX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(144 * 1024)));
-        done = true;
+    ResizeDev d = dev_of(op);
+    if (fwd_fine(d, planes)) {
+        d.tp = d.tp2; d.fwd_rows = d.fwd_rows2; d.blk_lo = d.blk_lo2; d.blk_cnt = d.blk_cnt2; d.own_lo = d.own_lo2;
+        d.gparts = 1;
     }
-    return DPSX_OK;
+    return d;
 }
 
-#define RZ_LAUNCH(KERNEL, GRID, LDS, STREAM, ...)                                   \
-    do {                                                                             \
-        static bool s_done = false;                                                  \
-        int rc_ = allow_lds(&KERNEL, s_done);                                        \
-        if (rc_ != DPSX_OK) return rc_;                                              \
-        hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(RT), LDS, STREAM, __VA_ARGS__);  \
-        return check_launch();                                                       \
-    } while (0)
-
-// the row-streaming kernel takes this operator (16-byte buffers assumed)
+// THE rule of the row-streaming kernel (and its A/B switch): it takes this operator; 16-byte buffers assumed
 static bool fwd_rows_ok(const ResizeDev &d)
 {
     static const bool no_rows = getenv("DPSX_RESIZE_NO_ROWS") != nullptr;        // A/B switch for tools/kbench.py
@@ -1040,39 +1033,25 @@ static bool fwd_rows_ok(const ResizeDev &d)
 // K1 with the noise drawn in the kernel exists in the row-streaming kernel only; the staged-rows kernel declines
 bool resize_step_draws_in_kernel(const dpsx_op *op) { return fwd_rows_ok(dev_of(op)); }
 
-static int launch_fwd_rows_rng(const dpsx_op *op, const ResizeArgs &a, hipStream_t s)
-{
-    ResizeDev d = dev_of(op);
-    if (fwd_fine(d, a.planes)) {        // as launch_fwd
-        d.tp = d.tp2; d.fwd_rows = d.fwd_rows2; d.blk_lo = d.blk_lo2; d.blk_cnt = d.blk_cnt2; d.own_lo = d.own_lo2;
-        d.gparts = 1;
-    }
-    const unsigned grid_x = (unsigned)((a.planes + 7) / 8 * 8 * ((d.out_h + d.tp - 1) / d.tp));
-    const size_t lds_r = ((size_t)4 * 256 + (size_t)d.fwd_rows * d.out_w + 16 + 2 * (size_t)(d.taps_h * d.tp)) * 4;
-    if (d.taps_w <= 16) RZ_LAUNCH((k_resize_fwd_rows<true, true, 16, 4, true>), grid_x, lds_r, s, a, d);
-    RZ_LAUNCH((k_resize_fwd_rows<true, true, 32, 2, true>), grid_x, lds_r, s, a, d);
-}
-
-template <bool POST, bool RESID>
+// RNG (the noise drawn in the kernel) exists for the fused step of the row-streaming kernel only: <true, true, true>
+template <bool POST, bool RESID, bool RNG = false>
 static int launch_fwd(const dpsx_op *op, const ResizeArgs &a, bool vec, hipStream_t s)
 {
-    ResizeDev d = dev_of(op);
-    if (fwd_fine(d, a.planes)) {        // one partial per block, in the slots the coarse blocks would have filled
-        d.tp = d.tp2; d.fwd_rows = d.fwd_rows2; d.blk_lo = d.blk_lo2; d.blk_cnt = d.blk_cnt2; d.own_lo = d.own_lo2;
-        d.gparts = 1;
+    const ResizeDev d = fwd_dev(op, a.planes);
+    const unsigned blocks = (unsigned)((d.out_h + d.tp - 1) / d.tp);
+    if (vec && fwd_rows_ok(d)) {
+        const unsigned grid_x = (unsigned)((a.planes + 7) / 8 * 8) * blocks;
+        if (d.taps_w <= 16) return launch_lds<k_resize_fwd_rows<POST, RESID, 16, 4, RNG>>(grid_x, RT, fwd_rows_lds(d), s, a, d);
+        return launch_lds<k_resize_fwd_rows<POST, RESID, 32, 2, RNG>>(grid_x, RT, fwd_rows_lds(d), s, a, d);
     }
-    const unsigned grid = (unsigned)(a.planes * ((d.out_h + d.tp - 1) / d.tp));
-    const size_t lds = ((size_t)d.fwd_rows * ((d.in_w + 3) / 4 * 4 + d.out_w) + 32 + 2 * (size_t)(d.taps_w * d.out_w + d.taps_h * d.tp)) * 4;
-    const int wu = d.in_w / 4;
-    static const bool no_rows = getenv("DPSX_RESIZE_NO_ROWS") != nullptr;        // A/B switch for tools/kbench.py
-    if (vec && !no_rows && d.in_w % 4 == 0 && wu >= 1 && wu <= 64 && 64 % wu == 0 && d.out_w <= wu && d.taps_w <= 32) {
-        const unsigned grid_x = (unsigned)((a.planes + 7) / 8 * 8 * ((d.out_h + d.tp - 1) / d.tp));
-        const size_t lds_r = ((size_t)4 * 256 + (size_t)d.fwd_rows * d.out_w + 16 + 2 * (size_t)(d.taps_h * d.tp)) * 4;
-        if (d.taps_w <= 16) RZ_LAUNCH((k_resize_fwd_rows<POST, RESID, 16, 4>), grid_x, lds_r, s, a, d);
-        RZ_LAUNCH((k_resize_fwd_rows<POST, RESID, 32, 2>), grid_x, lds_r, s, a, d);
+    if constexpr (RNG) {
+        return DPSX_EUNSUPPORTED;        // (the caller asked resize_step_draws_in_kernel first)
+    } else {
+        const unsigned grid = (unsigned)a.planes * blocks;
+        const size_t lds = fwd_lds(d, d.fwd_rows, d.tp);
+        if (vec) return launch_lds<k_resize_fwd<POST, RESID, true>>(grid, RT, lds, s, a, d);
+        return launch_lds<k_resize_fwd<POST, RESID, false>>(grid, RT, lds, s, a, d);
     }
-    if (vec) RZ_LAUNCH((k_resize_fwd<POST, RESID, true>), grid, lds, s, a, d);
-    RZ_LAUNCH((k_resize_fwd<POST, RESID, false>), grid, lds, s, a, d);
 }
 
 template <bool EPI>
@@ -1089,18 +1068,14 @@ static int launch_adj(const dpsx_op *op, const ResizeArgs &a, bool vec, hipStrea
         d.ti = d.ti2; d.adj_rows = d.adj_rows2; d.max_he = d.max_he2; d.ablk_lo = d.ablk_lo2; d.ablk_cnt = d.ablk_cnt2;
     }
     const unsigned grid = (unsigned)(a.planes * ((d.in_h + d.ti - 1) / d.ti));
-    const size_t lds = ((size_t)(d.adj_rows + d.ti) * d.out_w + 2 * (size_t)(d.ell_w * d.in_w + d.max_he) + d.ti + 8) * 4;
-    if (vec) RZ_LAUNCH((k_resize_adj<EPI, true>), grid, lds, s, a, d);
-    RZ_LAUNCH((k_resize_adj<EPI, false>), grid, lds, s, a, d);
+    const size_t lds = adj_lds(d, d.adj_rows, d.ti, d.max_he);
+    if (vec) return launch_lds<k_resize_adj<EPI, true>>(grid, RT, lds, s, a, d);
+    return launch_lds<k_resize_adj<EPI, false>>(grid, RT, lds, s, a, d);
 }
 
-static bool rz_vec(const dpsx_op *op, std::initializer_list<const void *> ptrs)
-{
-    if (op->in_w % 4 != 0) return false;
-    for (const void *p : ptrs)
-        if (p && !aligned16(p)) return false;
-    return true;
-}
+// the 16-byte form of a resize launch (common.h: vec_ok): whole float4 units per input row, and the buffers a launch
+// tests -- resize_forward leaves y, resize_adjoint u, resize_score y unchecked, as they always did
+static bool rz_vec(const dpsx_op *op, std::initializer_list<const void *> ptrs) { return vec_ok(op->resize->in_w, ptrs); }
 
 int resize_forward(const dpsx_op *op, const float *x, float *y, int64_t planes, hipStream_t s)
 {
@@ -1128,12 +1103,11 @@ int resize_step_fwd(const dpsx_op *op, const StepFwdArgs &f, hipStream_t s)
     a.tail.counters = f.tail.counters; a.tail.partials = f.tail.partials; a.tail.parts = f.tail.parts;
     a.tail.out = f.tail.out; a.tail.n = (int)f.n;
     a.tail.blocks_per_particle = (int)resize_fwd_blocks_per_particle(op, f.c, f.n * f.c);
-    const bool vec = rz_vec(op, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) &&
-                     (reinterpret_cast<uintptr_t>(f.inside) & 3u) == 0;
+    const bool vec = rz_vec(op, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) && aligned4(f.inside);
     if (f.use_rng) {
         if (!vec || !resize_step_draws_in_kernel(op)) return DPSX_EUNSUPPORTED;      // nothing launched
         a.rng = f.rng;
-        return launch_fwd_rows_rng(op, a, s);
+        return launch_fwd<true, true, true>(op, a, true, s);
     }
     return launch_fwd<true, true>(op, a, vec, s);
 }
@@ -1145,7 +1119,7 @@ int resize_step_bwd(const dpsx_op *op, const StepBwdArgs &b, hipStream_t s)
     a.x = b.resid; a.norm_in = b.norm; a.norm_partials = b.partials; a.norm_parts = b.parts; a.norm_out = b.norm_out;
     a.inside_r = b.inside; a.g_extra = b.g_extra; a.g_model_out = b.g_model_out;
     a.scale = b.scale; a.power = b.power; a.c = (int)b.c; a.planes = (int)(b.n * b.c); a.k = b.k;
-    const bool vec = rz_vec(op, {b.g_model_out, b.g_extra}) && (reinterpret_cast<uintptr_t>(b.inside) & 3u) == 0;
+    const bool vec = rz_vec(op, {b.g_model_out, b.g_extra}) && aligned4(b.inside);
     return launch_adj<true>(op, a, vec, s);
 }
 
