@@ -119,6 +119,9 @@ SIGNATURES = {
     "dpsx_repulse_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "dpsx_pairwise_sqdist_f32": (c_int, [_f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_repulse_f32": (c_int, [c_float, c_float, _f, _f, _f, _f, _f, _p, _i64, _i64, _i64, _p, _i64, _p]),
+    "dpsx_ensemble_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "dpsx_ensemble_f32": (c_int, [_f, _f, _f, _i64, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
+    "dpsx_ensemble_ex_f32": (c_int, [_f, _f, _f, _i64, _f, _f, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

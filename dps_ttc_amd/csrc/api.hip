@@ -720,6 +720,41 @@ int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float
     return repulse(true, c, bandwidth, x, out, d2, w, info, applied, n, chw, segments, workspace, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ ensemble statistics (ensemble.hip)
+static int ensemble_shape(int64_t n, int64_t d, int64_t images)
+{
+    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
+    if (n / images > kEnsMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
+    return DPSX_OK;
+}
+
+int64_t dpsx_ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images)
+{
+    const int rc = ensemble_shape(n, d, images);
+    return rc != DPSX_OK ? rc : ensemble_workspace_bytes(n, d, images);
+}
+
+int dpsx_ensemble_ex_f32(const float *x, const float *y, const float *neg_log_w, int64_t count0, float *mean, float *var,
+                         float *mean_lo, float *var_lo, float *curve, float *info, int64_t n, int64_t d, int64_t images,
+                         void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!x || !mean || !var || !info || !workspace || !mean_lo != !var_lo) return DPSX_EINVAL;
+    if (count0 < 0 || (neg_log_w && count0 > 0) || (curve && !y)) return DPSX_EINVAL;
+    const int rc = ensemble_shape(n, d, images);
+    if (rc != DPSX_OK) return rc;
+    if (workspace_bytes < ensemble_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    return ensemble(x, y, neg_log_w, count0, mean, var, mean_lo, var_lo, curve, info, n, d, images, workspace,
+                    (hipStream_t)stream);
+}
+
+int dpsx_ensemble_f32(const float *x, const float *y, const float *neg_log_w, int64_t count0, float *mean, float *var,
+                      float *curve, float *info, int64_t n, int64_t d, int64_t images, void *workspace,
+                      int64_t workspace_bytes, void *stream)
+{
+    return dpsx_ensemble_ex_f32(x, y, neg_log_w, count0, mean, var, nullptr, nullptr, curve, info, n, d, images, workspace,
+                                workspace_bytes, stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

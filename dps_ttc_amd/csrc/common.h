@@ -53,7 +53,7 @@ inline bool vec_ok(int64_t size, std::initializer_list<const void *> ptrs)
 // has its own flag.  launch_lds<k_name<...>>(grid, threads, lds_bytes, stream, kernel arguments...)
 constexpr int kMaxDynamicLds = 144 * 1024;
 template <auto Kernel, class... Args>
-int launch_lds(unsigned grid, unsigned threads, size_t lds, hipStream_t s, const Args &...args)
+int launch_lds(dim3 grid, unsigned threads, size_t lds, hipStream_t s, const Args &...args)
 {
     static bool attr_done = false;
     if (!attr_done) {
@@ -61,7 +61,7 @@ int launch_lds(unsigned grid, unsigned threads, size_t lds, hipStream_t s, const
                                          kMaxDynamicLds));
         attr_done = true;
     }
-    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, args...);
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, s, args...);
     return check_launch();
 }
 
@@ -732,6 +732,14 @@ constexpr int kRepulseMaxK = 512;
 int64_t repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments);
 int repulse(bool apply, float c, float bandwidth, const float *x, float *out, float *d2, float *w, float *info,
             uint8_t *applied, int64_t n, int64_t chw, int64_t segments, void *workspace, hipStream_t s);
+
+// ensemble.hip: mean, variance, mean-of-n curve and info of every image's particles (the definition is stated in
+// include/dpsx.h); the caller checked the arguments (images | n, 1 <= n / images <= kEnsMaxK) and the workspace size.
+// y, e, curve: nullable; count0 > 0: mean / var hold the prior; mean_lo, var_lo: both or neither, the low parts (in/out)
+constexpr int kEnsMaxK = 4096;
+int64_t ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int ensemble(const float *x, const float *y, const float *e, int64_t count0, float *mean, float *var, float *mean_lo,
+             float *var_lo, float *curve, float *info, int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s);
 
 // phase.hip
 int phase_create(dpsx_op *op, const PhaseOp &shape);

@@ -1123,6 +1123,83 @@ def repulse(x, strength, images=1, bandwidth=None, out=None, want_info=False, st
     return (out, rec) if want_info else out
 
 
+# ------------------------------------------------------------------ ensemble statistics (include/dpsx.h: "ensemble statistics")
+ENSEMBLE_MAX_K = 4096    # particles per image (DPSX_EUNSUPPORTED above)
+ENSEMBLE_INFO = ("ess", "mean_var", "mse", "count")      # the columns of info [M, 4]
+_ensemble_ws = {}        # (device, n, d, images) -> the call's workspace, as _metrics_ws
+
+
+def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, stream=None):
+    """Mean, per-pixel variance and mean-of-n curve of every image's particles, one device call (dpsx_ensemble_ex_f32, at
+    most three launches): x [N, C, H, W] image-major, `images` images of K = N / images <= 4096 particles; x is not written.
+    label: [C, H, W], [1, ...] or [images, ...] (None: no curve).  neg_log_weights [N]: SMC's negative log-weights (None:
+    uniform); a non-finite entry is weight 0, an image with none finite takes the uniform form.  prior: an earlier group of
+    the same images, merged in (not together with weights): (count0, mean0, var0), (count0, mean0, var0, mean_lo, var_lo)
+    or the dict an earlier call returned (the count being the same for every image).  mean0 and var0 are fp32; the low
+    parts are what that rounding dropped, and with them groups merged call after call come out as one call over all of
+    them would.  The prior's tensors are not written.
+    -> {"mean", "var", "mean_lo", "var_lo": [M, C, H, W], "info": [M, 4] (ENSEMBLE_INFO), "count": T} and, with a label,
+    "curve": [M, K] (curve[m][n - 1]: mse of the mean of the first n paths) and "final_mse": [M] (the returned mean's).
+    No host read; the workspace is cached per shape and serves one stream at a time."""
+    x = f32c(x, "particles")
+    if x.dim() != 4:
+        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
+    n, images = int(x.shape[0]), int(images)
+    if images < 1 or n < 1 or n % images:
+        raise ValueError(f"{n} particles do not split into {images} images")
+    k, d = n // images, int(x[0].numel())
+    shape = (images,) + tuple(x.shape[1:])
+    if label is not None:
+        label = _label_rows(label, x)
+        if label.shape[0] == 1 and images > 1:
+            label = label.expand(shape).contiguous()
+        if label.shape[0] != images:
+            raise ValueError(f"{label.shape[0]} labels given for {images} images")
+    e = None
+    if neg_log_weights is not None:
+        if prior is not None:
+            raise ValueError("neg_log_weights cannot be combined with a prior: two calls share no reference level")
+        e = f32c(neg_log_weights, "neg_log_weights").reshape(-1)
+        if e.numel() != n or e.device != x.device:
+            raise ValueError(f"neg_log_weights must hold {n} values on {x.device}")
+    count0 = 0
+    new = lambda: torch.empty(shape, dtype=torch.float32, device=x.device)
+    if prior is not None:
+        if isinstance(prior, dict):
+            prior = (prior["count"], prior["mean"], prior["var"], prior.get("mean_lo"), prior.get("var_lo"))
+        count0, mean0, var0, lo_m, lo_v = tuple(prior) + (None, None) * (len(prior) == 3)
+        if isinstance(count0, bool) or int(count0) != count0 or count0 < 0:
+            raise ValueError(f"the prior's count must be an integer >= 0 (got {count0!r})")
+        if (lo_m is None) != (lo_v is None):
+            raise ValueError("the prior's low parts come as a pair: mean_lo and var_lo")
+        count0, given = int(count0), [("mean0", mean0), ("var0", var0)] + ([("mean_lo", lo_m), ("var_lo", lo_v)] if lo_m is not None else [])
+        for name, t in given:
+            if tuple(t.shape) != shape or t.device != x.device:
+                raise ValueError(f"the prior's {name} must be {shape} on {x.device} (got {tuple(t.shape)} on {t.device})")
+        # in/out: the caller's prior stays
+        mean, var = f32c(mean0, "mean0").clone(), f32c(var0, "var0").clone()
+        mean_lo, var_lo = (f32c(lo_m, "mean_lo").clone(), f32c(lo_v, "var_lo").clone()) if lo_m is not None else \
+            (torch.zeros_like(mean), torch.zeros_like(var))
+    else:
+        mean, var, mean_lo, var_lo = new(), new(), new(), new()
+    key = (x.device, n, d, images)
+    ws = _ensemble_ws.get(key)
+    if ws is None:
+        need = lib().dpsx_ensemble_workspace_bytes(n, d, images)
+        if need < 0:
+            check(int(need), "dpsx_ensemble_workspace_bytes")
+        ws = _ensemble_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    curve = torch.empty((images, k + 1), dtype=torch.float32, device=x.device) if label is not None else None
+    info = torch.empty((images, 4), dtype=torch.float32, device=x.device)
+    check(lib().dpsx_ensemble_ex_f32(ptr(x), ptr(label), ptr(e), count0, ptr(mean), ptr(var), ptr(mean_lo), ptr(var_lo),
+                                     ptr(curve), ptr(info), n, d, images, ptr(ws), ws.numel(), _stream_arg(stream, x)),
+          "dpsx_ensemble_ex_f32")
+    res = {"mean": mean, "var": var, "mean_lo": mean_lo, "var_lo": var_lo, "info": info, "count": count0 + k}
+    if curve is not None:
+        res["curve"], res["final_mse"] = curve[:, :k], curve[:, k]
+    return res
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,

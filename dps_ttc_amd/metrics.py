@@ -39,6 +39,34 @@ def pathwise_metrics(refs, samples, n_images=1):
     return kernels.image_metrics(samples.detach(), refs)
 
 
+def mean_of_n_psnr(curve, refs):
+    """10 log10(L^2 / curve) for curve [M, K] (the mse of the mean of the first n paths, kernels.ensemble_stats) against
+    refs [M, C, H, W]: the PSNR of the mean-of-n estimate, L = max - min of each label as compute_psnr defines it"""
+    flat = refs.float().reshape(refs.shape[0], -1)
+    data_range = (flat.max(dim=1).values - flat.min(dim=1).values).reshape(-1, 1)
+    return 10.0 * torch.log10(data_range ** 2 / curve)
+
+
+def posterior_summary(refs, samples, n_images=1, neg_log_weights=None, prior=None):
+    """What the particles say together: samples [N, C, H, W] (image-major, n_images images) against refs [n_images, C, H, W]
+    -> {"mean", "std" [M, C, H, W] (std = sqrt of the biased per-pixel variance), "mean_psnr", "mean_ssim", "ess" [M],
+    "mean_of_n_psnr" [M, K], and the call's "var", "mean_lo", "var_lo", "info", "count" (so that the dict is the `prior` of the next particle
+    group of the same images: the groups are merged, the curve continues)}.  neg_log_weights: SMC's (uniform if None).
+    Two device calls (kernels.ensemble_stats, then kernels.image_metrics on the M means, each one "particle" of its own
+    label), no host read."""
+    from . import kernels
+    if refs.dim() == 3:
+        refs = refs.unsqueeze(0)
+    if refs.shape[0] != n_images:
+        raise ValueError(f"{refs.shape[0]} reference images given for n_images = {n_images}")
+    st = kernels.ensemble_stats(samples.detach(), images=n_images, label=refs, neg_log_weights=neg_log_weights, prior=prior)
+    pm = kernels.image_metrics(st["mean"], refs, want=("psnr", "ssim"))
+    return {"mean": st["mean"], "std": torch.sqrt(st["var"]), "var": st["var"], "mean_lo": st["mean_lo"],
+            "var_lo": st["var_lo"], "info": st["info"], "count": st["count"],
+            "mean_psnr": pm["psnr"], "mean_ssim": pm["ssim"], "ess": st["info"][:, 0],
+            "mean_of_n_psnr": mean_of_n_psnr(st["curve"], refs)}
+
+
 def best_of_n_curve(distances, metric):
     """curve[n - 1] = metric[argmin(distances[:n])] for n = 1 .. len: the metric of the best-of-n pick over the first n
     paths.  The pick is np.argmin's: a NaN distance first, then the smallest, the first index among equals -- the

@@ -584,6 +584,62 @@ int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float
                      uint8_t *applied, int64_t n, int64_t chw, int64_t segments,
                      void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- ensemble statistics: what an image's K particles say together -- the posterior mean (the MMSE estimate), the
+ * per-pixel variance (the uncertainty map), the mean-of-n curve against the label (the companion of the best-of-n curve)
+ * and one record per image.  Evaluation only: nothing here steers a sampler.  tests/ensemble_ref.py restates the
+ * definition in float64.
+ *   x [n, d] particles, image-major: M = images images of K = n / M particles each, d = c h w.  y [M, d] the label
+ *   (nullable).  E [n] negative log-weights with SMC's sign convention (nullable: w_i = 1).  A prior (count0 > 0, with
+ *   mean [M, d] and var [M, d] holding mean0 and var0 on entry) stands for count0 earlier particles of the same images.
+ *   Everything below is per image and uses the image's own particles only.
+ *   weights  with E: a non-finite E_i gives w_i = 0; E_min over the finite entries; w_i = exp(-(E_i - E_min)), the
+ *            difference one fp32 subtraction, the exponential in double; W = sum w in double in index order; the
+ *            normalised weight w_i / W is rounded to fp32 once.  ESS = W^2 / sum w^2 in double, rounded once.  An image
+ *            with no finite E_i takes the uniform form below (ESS = K).  Without E, ESS = T.
+ *   sums     per element e, particles in index order: c = mean0[e] with a prior, else the image's first particle's x[e];
+ *            S1 = sum w (x - c), S2 = sum w (x - c)^2 in double (x - c formed in double; each term of S2 one fma).
+ *   uniform  T = count0 + K:  mean = c + S1 / T;  M2 = var0 count0 + S2 - S1^2 / T;  var = max(M2 / T, 0)
+ *   weighted (normalised fp32 weights):  mean = c + S1;  var = max(S2 - S1^2, 0)
+ *            mean and var are each rounded to fp32 once.  The variance is the biased one; NaN passes through the max; an
+ *            image of equal particles has var = +0.0 exactly.
+ *   curve    only with y.  For n = 1 .. K: pm_n = c + (sum_{i <= n} (x_i - c)) r_n with r_n = 1 / (count0 + n) rounded to
+ *            double once (with a prior c is mean0, so the prior adds 0 to the sum); curve[m][n - 1] = mean over e of
+ *            (pm_n - y)^2, each squared error formed in double and rounded to fp32.  Always the uniform prefix in path
+ *            order, whatever E is.  Column K holds the same error for the final (possibly weighted) mean, taken before
+ *            its rounding to fp32.  The sum over e: a lane adds its elements serially in fp32, then a fixed tree per block;
+ *            the finisher adds an image's cg_slots(d) block partials in double in a fixed order, divides by d and rounds
+ *            once.
+ *   info [M, 4] = (ESS, mean over e of the fp32 var, column K of the curve or NaN without y, T).
+ * K <= 4096.  At most three launches on `stream`: the weights (only with E; one block per image), the stream over the
+ * particles (grid (cg_slots(d), M); float4 units where d % 4 == 0 and x, y, mean, var are 16-byte aligned, else the scalar
+ * instantiation of the same body; mean and var are the same bits in both forms) and the finisher.  No atomics, no fence,
+ * no allocation, no host read (graph-capturable).  Slot counts depend on d only: an image's numbers depend on neither M
+ * nor its place in the batch.  A NaN or Inf in a particle reaches its own elements of its own image's mean and var, and
+ * the curve entries of its image from that particle on; nothing else changes a bit.  x is not written.
+ *   low parts (dpsx_ensemble_ex_f32 only; mean_lo, var_lo [M, d], both or neither).  A prior is fp32, and mean0's rounding
+ *            alone (2^-25 |mean0|) can exceed what a merged number may be off by -- where two groups' means nearly cancel,
+ *            or the variance is tiny against the mean.  On return mean_lo = mean - fp32(mean) and var_lo = var - fp32(var),
+ *            each rounded to fp32 (0 where the fp32 value is not finite).  With a prior they are read first, as ml and vl
+ *            of the prior: its particles then count as count0 ml in S1 (and in the curve's prefix) and as
+ *            count0 (var0 + vl + ml^2) in place of var0 count0.  Zero low parts, or dpsx_ensemble_f32, give the fp32 triple
+ *            alone, exactly as stated above.  They are arguments like the others: a call's results depend on its
+ *            arguments only.
+ * mean, var [M, d] (in/out with a prior); curve [M, K + 1] nullable (null without y); info [M, 4].  The workspace
+ * (dpsx_ensemble_workspace_bytes: the partial sums and the weights; nothing in it outlives the call) serves one stream
+ * at a time.
+ * DPSX_EINVAL: a null x, mean, var, info or workspace; one of mean_lo / var_lo without the other; n < 1, d < 1, images < 1, n not divisible by images; count0 < 0;
+ * E together with a prior (two calls share no reference level for their weights); curve without y.
+ * DPSX_EUNSUPPORTED: K > 4096 (more than 65535 images, d >= 2^31).  DPSX_EWORKSPACE: a short workspace.  All of them
+ * return before anything is launched. */
+int64_t dpsx_ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int dpsx_ensemble_f32(const float *x, const float *y /* nullable */, const float *neg_log_weights /* nullable */,
+                      int64_t count0, float *mean, float *var, float *curve /* nullable */, float *info,
+                      int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
+int dpsx_ensemble_ex_f32(const float *x, const float *y /* nullable */, const float *neg_log_weights /* nullable */,
+                         int64_t count0, float *mean, float *var, float *mean_lo /* nullable */,
+                         float *var_lo /* nullable */, float *curve /* nullable */, float *info,
+                         int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

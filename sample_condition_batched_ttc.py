@@ -152,6 +152,14 @@ def parse_args(argv=None):
     p.add_argument('--path_diversity', action='store_true',
                    help='write {fname}_path_diversity.npy: per particle group the [mean, min] RMS per-element distance '
                         'between its final samples (min 0: duplicates); one rank only')
+    p.add_argument('--posterior_summary', action='store_true',
+                   help='per image write posterior_mean/{fname}.png, {fname}_posterior_std.npy (per-pixel std of the paths), '
+                        '{fname}_mean_of_n_psnr.npy (PSNR of the mean of the first n paths, in the path order of '
+                        '{fname}_pathwise_distances.npy) and {fname}_posterior_summary.npy = [mean PSNR, mean SSIM, ESS, '
+                        'mean std]; one device call per particle group; one rank only')
+    p.add_argument('--posterior_weights', type=str, default='uniform', choices=('uniform', 'smc'),
+                   help='--posterior_summary: uniform, or smc: the final importance weights of sampler smc_ddpm '
+                        '(one particle group only)')
     args = p.parse_args(argv)
     if args.path_diversity and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         raise SystemExit("--path_diversity runs on one rank only: the per-group distances are not gathered between ranks "
@@ -322,6 +330,52 @@ def path_diversity(sample, images=1):
     return torch.sqrt(info[:, 2:4] / sample[0].numel()).cpu().numpy()
 
 
+def check_posterior_summary(args, sampler_name, world=1):
+    """--posterior_summary / --posterior_weights: reject what they do not support, before any GPU work (one-line message)"""
+    if not args.posterior_summary:
+        if args.posterior_weights != 'uniform':
+            raise SystemExit(f"--posterior_weights {args.posterior_weights} needs --posterior_summary")
+        return
+    if world > 1:
+        raise SystemExit("--posterior_summary runs on one rank only: the particles of an image are not gathered between "
+                         f"ranks (WORLD_SIZE={world})")
+    if args.batch_size > 4096:
+        raise SystemExit(f"--posterior_summary takes at most 4096 paths per particle group (--batch_size {args.batch_size})")
+    if args.posterior_weights == 'smc':
+        if sampler_name != 'smc_ddpm':
+            raise SystemExit("--posterior_weights smc reads the weights of sampler smc_ddpm (the diffusion config names "
+                             f"{sampler_name})")
+        if args.n_paths // args.batch_size != 1:
+            raise SystemExit("--posterior_weights smc takes one particle group: the weights of two groups share no reference "
+                             f"level (n_paths / batch_size = {args.n_paths // args.batch_size})")
+
+
+class PosteriorSummary:
+    """--posterior_summary: the particle groups of the same images merged one by one (metrics.posterior_summary with the
+    previous group as the prior) and, at the end, the four files per image"""
+
+    def __init__(self, refs, weights='uniform'):
+        self.refs, self.weights, self.last, self.curves = refs, weights, None, []
+
+    def add(self, sample, sampler=None):
+        from dps_ttc_amd.metrics import posterior_summary
+        e = sampler.last_neg_log_weights if self.weights == 'smc' else None
+        self.last = posterior_summary(self.refs, sample, n_images=self.refs.shape[0], neg_log_weights=e, prior=self.last)
+        self.curves.append(self.last["mean_of_n_psnr"])
+
+    def save(self, out_path, fnames):
+        s = self.last
+        os.makedirs(os.path.join(out_path, 'posterior_mean'), exist_ok=True)
+        curve = torch.cat(self.curves, dim=1).cpu().numpy()              # [M, n_paths]: group-major, the path order
+        rec = torch.stack([s["mean_psnr"], s["mean_ssim"], s["ess"], s["std"].flatten(1).mean(dim=1)], dim=1).cpu().numpy()
+        std = s["std"].cpu().numpy()
+        for b, fname in enumerate(fnames):
+            imsave(os.path.join(out_path, 'posterior_mean', fname + '.png'), clear_color(s["mean"][b:b + 1]))
+            np.save(os.path.join(out_path, f'{fname}_posterior_std.npy'), std[b])
+            np.save(os.path.join(out_path, f'{fname}_mean_of_n_psnr.npy'), curve[b])
+            np.save(os.path.join(out_path, f'{fname}_posterior_summary.npy'), rec[b])
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
@@ -340,6 +394,8 @@ def main(argv=None):
         check_repulsion(args, sampler_name, world)
     if args.images_per_batch != 1:
         check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
+    if args.posterior_summary or args.posterior_weights != 'uniform':
+        check_posterior_summary(args, sampler_name, world)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1)
@@ -487,6 +543,7 @@ def main(argv=None):
         distances, finals = [], []
         device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
         diversity = []
+        posterior = PosteriorSummary(ref_img, args.posterior_weights) if args.posterior_summary else None
         for g in my_groups:
             x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
@@ -500,6 +557,8 @@ def main(argv=None):
             finals.append(sample)
             if args.path_diversity:
                 diversity.append(path_diversity(sample)[0])
+            if posterior is not None:
+                posterior.add(sample, sampler)
             if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
                 pm = pathwise_metrics(ref_img, sample)
                 pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -532,6 +591,8 @@ def main(argv=None):
                                   np.concatenate(path_ssim))
             if args.path_diversity:  # one rank (parse_args): [groups, 2]
                 np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack(diversity))
+            if posterior is not None:  # one rank (check_posterior_summary)
+                posterior.save(out_path, [fname])
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -572,6 +633,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
     distances, finals = [], []
     device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
     diversity = []
+    posterior = PosteriorSummary(refs, args.posterior_weights) if args.posterior_summary else None
     for g in range(groups):
         x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
@@ -585,6 +647,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
         finals.append(sample)
         if args.path_diversity:
             diversity.append(path_diversity(sample, images=B))
+        if posterior is not None:
+            posterior.add(sample, sampler)
         if device_metrics:            # one device call and one copy for the group's B x K particles
             pm = pathwise_metrics(refs, sample, n_images=B)
             pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -623,6 +687,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
                               np.concatenate([v[b] for v in path_ssim]))
         if args.path_diversity:  # [groups][B, 2] -> image b's [groups, 2]
             np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack([v[b] for v in diversity]))
+    if posterior is not None:
+        posterior.save(out_path, fnames)
 
 
 if __name__ == '__main__':

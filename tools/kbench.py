@@ -47,6 +47,12 @@ three launches), (c) the same mathematics as torch ops (torch.cdist on the flatt
 same N for scale.  (a) and (b) are stated against both floors by shape arithmetic -- bytes at 8 TB/s with every particle moved
 once, fp32 operations at the vector peak -- with the one that binds and how often the tiling fetches a particle.  The three
 launches apart come from a kernel trace (rocprofv3 --kernel-trace) of the same call in a run of its own.
+    python tools/kbench.py --ensemble                                                 (ensemble statistics, 256^2)
+--ensemble: [M K, 3, 256, 256] particles and M labels, M = 4 x K = 16, M = 1 x K = 64 and M = 1 x K = 512, 3 x --reps
+repetitions alternated in one process: (a) kernels.ensemble_stats with the label (stream + finisher) and (a') with weights too
+(all three launches), (b) torch ops giving the same outputs (var_mean; cumsum / n - y, squared, mean), (c) the byte floor
+((K + 1) D 4 read + 2 D 4 written per image at 8 TB/s), (d) K3 at the same N for scale: (a)'s rate against its floor's bytes
+is also stated as a fraction of K3's rate in the same run.
 """
 import argparse
 import os
@@ -76,7 +82,10 @@ def main():
     ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
     ap.add_argument("--metrics", action="store_true", help="time per-path PSNR / SSIM: host loop / torch ops / image_metrics")
     ap.add_argument("--repulse", action="store_true", help="time particle repulsion: the distances / the whole call / torch ops / K3")
+    ap.add_argument("--ensemble", action="store_true", help="time the ensemble statistics: the call / torch ops / the byte floor / K3")
     args = ap.parse_args()
+    if args.ensemble:
+        return ensemble_step(args)
     if args.repulse:
         return repulse_step(args)
     if args.metrics:
@@ -632,6 +641,80 @@ def repulse_step(args):
             print(f"repulse 256^2 M={M} K={k:3d} {name:38s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
                   flush=True)
         del x, out, buf, g_unet, base
+
+
+def ensemble_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    c, h, w = 3, 256, 256
+    D, P = c * h * w, c * h * w * 4
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for M, k in ((4, 16), (1, 64), (1, 512)):
+        n = M * k
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        y = torch.randn(M, c, h, w, device=dev, generator=gen)
+        x = (np.sqrt(0.5) * y[:, None] + np.sqrt(0.5) * torch.randn(M, k, c, h, w, device=dev, generator=gen)).reshape(n, c, h, w)
+        x = x.contiguous()
+        e = 3.0 * torch.randn(n, device=dev, generator=gen)
+        g_unet = 1e-3 * torch.randn(n, c, h, w, device=dev, generator=gen)
+        buf = kernels.StepBuffers(None, n, c, h, w, dev)
+        buf.sample.copy_(x)
+        cnt = torch.arange(1, k + 1, device=dev, dtype=torch.float32).view(1, k, 1)
+
+        def a_call(i):
+            kernels.ensemble_stats(x, images=M, label=y)
+
+        def a_weighted(i):
+            kernels.ensemble_stats(x, images=M, label=y, neg_log_weights=e)
+
+        def b_torch(i):
+            xf = x.view(M, k, D)
+            var, mean = torch.var_mean(xf, dim=1, unbiased=False)
+            curve = ((torch.cumsum(xf, dim=1) / cnt - y.view(M, 1, D)) ** 2).mean(dim=2)
+            return mean, var, curve, var.mean(dim=1)
+
+        def d_k3(i):
+            kernels.step_update(buf, g_unet, ck)
+
+        forms = (("a ensemble_stats (stream + finisher)", a_call), ("a' ensemble_stats with weights (3 launches)", a_weighted),
+                 ("b torch var_mean + cumsum curve", b_torch), ("d K3 (step_update) for scale", d_k3))
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        floor_bytes = M * ((k + 1) * P + 2 * P)
+        t_k3 = float(np.concatenate(res["d K3 (step_update) for scale"]).mean())
+        k3_rate = 4 * P * n / t_k3
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            note = ""
+            if name[0] == "a":
+                rate = floor_bytes / ts.mean()
+                note = (f"  c floor {floor_bytes / 8e6:.1f} us ({floor_bytes / 8e6 / ts.mean():.2f} of it); {rate / 1e3:.0f} GB/s = "
+                        f"{rate / k3_rate:.2f} x K3's rate")
+            elif name[0] == "d":
+                note = f"  {k3_rate / 1e3:.0f} GB/s (4 P/particle)"
+            print(f"ensemble 256^2 M={M} K={k:3d} {name:44s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
+                  flush=True)
+        del x, y, e, buf, g_unet
 
 
 def noise_draw(args):
