@@ -5,7 +5,7 @@ point.  If the shared object is missing or a call fails, this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPSX_LIB: development aid to A/B an experimental build of the same library (tools/abl.sh)
@@ -122,6 +122,8 @@ SIGNATURES = {
     "dpsx_ensemble_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "dpsx_ensemble_f32": (c_int, [_f, _f, _f, _i64, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_ensemble_ex_f32": (c_int, [_f, _f, _f, _i64, _f, _f, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
+    "dpsx_quantiles_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "dpsx_quantiles_f32": (c_int, [_f, _f, POINTER(c_double), _i64, _f, _p, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

@@ -755,6 +755,34 @@ int dpsx_ensemble_f32(const float *x, const float *y, const float *neg_log_w, in
                                 workspace_bytes, stream);
 }
 
+// ------------------------------------------------------------------ order statistics (quantile.hip)
+static int quantiles_shape(int64_t n, int64_t d, int64_t images)
+{
+    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
+    if (n / images > kQuantMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
+    return DPSX_OK;
+}
+
+int64_t dpsx_quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images)
+{
+    const int rc = quantiles_shape(n, d, images);
+    return rc != DPSX_OK ? rc : quantiles_workspace_bytes(n, d, images);
+}
+
+int dpsx_quantiles_f32(const float *x, const float *y, const double *probs, int64_t q, float *quant, int32_t *hist,
+                       float *info, int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes,
+                       void *stream)
+{
+    if (!x || !quant || !info || !workspace || !probs || (hist && !y)) return DPSX_EINVAL;
+    if (q < 1 || q > kQuantMaxQ) return DPSX_EINVAL;
+    for (int64_t i = 0; i < q; ++i)
+        if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return DPSX_EINVAL;       // NaN fails both
+    const int rc = quantiles_shape(n, d, images);
+    if (rc != DPSX_OK) return rc;
+    if (workspace_bytes < quantiles_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    return quantiles(x, y, probs, q, quant, hist, info, n, d, images, workspace, (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

@@ -741,6 +741,16 @@ int64_t ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images);
 int ensemble(const float *x, const float *y, const float *e, int64_t count0, float *mean, float *var, float *mean_lo,
              float *var_lo, float *curve, float *info, int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s);
 
+// quantile.hip: per-element quantiles, the label's rank histogram and the CRPS of every image's particles (the definition
+// is stated in include/dpsx.h); the caller checked the arguments (images | n, 1 <= n / images <= kQuantMaxK, 1 <= q <=
+// kQuantMaxQ, probs in [0, 1]) and the workspace size.  y, hist: nullable.  K <= kQuantRegK sorts in registers, above in LDS
+constexpr int kQuantMaxK = 512;
+constexpr int kQuantMaxQ = 8;
+constexpr int kQuantRegK = 64;
+int64_t quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int quantiles(const float *x, const float *y, const double *probs, int64_t q, float *quant, int32_t *hist, float *info,
+              int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op, const PhaseOp &shape);
 void phase_destroy(dpsx_op *op);

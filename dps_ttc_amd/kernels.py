@@ -1200,6 +1200,73 @@ def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, st
     return res
 
 
+# ------------------------------------------------------------------ order statistics (include/dpsx.h: "order statistics")
+QUANTILE_MAX_K = 512     # particles per image (DPSX_EUNSUPPORTED above)
+QUANTILE_MAX_Q = 8       # probabilities per call
+QUANTILE_INFO = ("crps", "width", "invalid", "count")    # the columns of info [M, 4]
+_quantile_ws = {}        # (device, n, d, images) -> the call's workspace, as _metrics_ws
+
+
+def quantile_probs(probs):
+    """the probabilities of an order_stats call as the library takes them: 1 .. 8 floats in [0, 1] (ValueError otherwise)"""
+    try:
+        p = [float(v) for v in probs]
+    except TypeError:
+        p = [float(probs)]
+    if not 1 <= len(p) <= QUANTILE_MAX_Q:
+        raise ValueError(f"between 1 and {QUANTILE_MAX_Q} probabilities are taken (got {len(p)})")
+    if any(not (0.0 <= v <= 1.0) for v in p):
+        raise ValueError(f"probabilities must lie in [0, 1] (got {p})")
+    return p
+
+
+def order_stats(x, images=1, probs=(0.05, 0.5, 0.95), label=None, stream=None):
+    """Per-pixel quantiles of every image's particles and, with a label, the rank histogram and the CRPS, one device call
+    (dpsx_quantiles_f32, two launches): x [N, C, H, W] image-major, `images` images of K = N / images <= 512 particles; x
+    is not written.  probs: 1 .. 8 probabilities in [0, 1] (linear interpolation between the order statistics, numpy's
+    default).  label: [C, H, W], [1, ...] or [images, ...].
+    -> {"quantiles": [M, q, C, H, W], "info": [M, 4] (QUANTILE_INFO)} and, with a label, "hist": [M, K + 2] int32 (bin r:
+    the elements whose label exceeds exactly r particles; bin K + 1: a NaN in the label or a particle) and "crps": [M].
+    An element with a NaN particle is NaN in all q maps.  The library's refusals are raised as ValueError before any
+    launch.  No host read; the workspace is cached per shape and serves one stream at a time."""
+    x = f32c(x, "particles")
+    if x.dim() != 4:
+        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
+    n, images = int(x.shape[0]), int(images)
+    if images < 1 or n < 1 or n % images:
+        raise ValueError(f"{n} particles do not split into {images} images")
+    k, d = n // images, int(x[0].numel())
+    if k > QUANTILE_MAX_K:
+        raise ValueError(f"order statistics take at most {QUANTILE_MAX_K} particles per image (got {k})")
+    if d < 1 or images > 65535 or d >= 2 ** 31:
+        raise ValueError(f"order statistics take 1 <= C H W < 2^31 and at most 65535 images (got {d}, {images})")
+    p = quantile_probs(probs)
+    q = len(p)
+    shape = (images,) + tuple(x.shape[1:])
+    if label is not None:
+        label = _label_rows(label, x)
+        if label.shape[0] == 1 and images > 1:
+            label = label.expand(shape).contiguous()
+        if label.shape[0] != images:
+            raise ValueError(f"{label.shape[0]} labels given for {images} images")
+    key = (x.device, n, d, images)
+    ws = _quantile_ws.get(key)
+    if ws is None:
+        need = lib().dpsx_quantiles_workspace_bytes(n, d, images)
+        if need < 0:
+            check(int(need), "dpsx_quantiles_workspace_bytes")
+        ws = _quantile_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    quant = torch.empty((images, q) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    hist = torch.empty((images, k + 2), dtype=torch.int32, device=x.device) if label is not None else None
+    info = torch.empty((images, 4), dtype=torch.float32, device=x.device)
+    check(lib().dpsx_quantiles_f32(ptr(x), ptr(label), (ctypes.c_double * q)(*p), q, ptr(quant), ptr(hist), ptr(info), n, d,
+                                   images, ptr(ws), ws.numel(), _stream_arg(stream, x)), "dpsx_quantiles_f32")
+    res = {"quantiles": quant, "info": info}
+    if label is not None:
+        res["hist"], res["crps"] = hist, info[:, 0]
+    return res
+
+
 # ------------------------------------------------------------------ particle groups on streams
 class ParticleGroups:
     """The N particles of a fused DPS loop as `groups` independent sub-batches, each with its own operator handle,

@@ -67,6 +67,36 @@ def posterior_summary(refs, samples, n_images=1, neg_log_weights=None, prior=Non
             "mean_of_n_psnr": mean_of_n_psnr(st["curve"], refs)}
 
 
+def posterior_quantiles(refs, samples, n_images=1, probs=(0.05, 0.5, 0.95)):
+    """The order statistics of the particles: samples [N, C, H, W] (image-major, n_images images of K <= 512 particles)
+    against refs [n_images, C, H, W] -> {"quantiles" [M, q, C, H, W] (probs in [0, 1], at most 8), "hist" [M, K + 2] int32
+    (the rank histogram of the label among the particles; bin K + 1: NaN), "crps" [M], "info" [M, 4] = (mean CRPS, mean
+    width quantiles[-1] - quantiles[0], invalid elements, K)}.  One device call (kernels.order_stats), no host read."""
+    from . import kernels
+    if refs.dim() == 3:
+        refs = refs.unsqueeze(0)
+    if refs.shape[0] != n_images:
+        raise ValueError(f"{refs.shape[0]} reference images given for n_images = {n_images}")
+    return kernels.order_stats(samples.detach(), images=n_images, probs=probs, label=refs)
+
+
+def interval_coverage(hist, lo_rank, hi_rank):
+    """The fraction of an image's valid elements whose label's rank lies in lo_rank .. hi_rank (both included): hist
+    [M, K + 2] or [K + 2] integer rank histograms (bin K + 1, the invalid elements, is left out of the divisor) -> [M] or a
+    scalar, float64.  Host arithmetic on integers: with ranks 1 .. K - 1 this is how often the label fell strictly inside
+    the particles' range; a calibrated set of K particles gives (hi_rank - lo_rank + 1) / (K + 1)."""
+    h = np.asarray(hist.cpu() if torch.is_tensor(hist) else hist)
+    if not np.issubdtype(h.dtype, np.integer) or h.ndim not in (1, 2) or h.shape[-1] < 3:
+        raise ValueError(f"hist must be an integer [M, K + 2] or [K + 2] array (got {h.dtype} {h.shape})")
+    k = h.shape[-1] - 2
+    lo_rank, hi_rank = int(lo_rank), int(hi_rank)
+    if not 0 <= lo_rank <= hi_rank <= k:
+        raise ValueError(f"ranks must satisfy 0 <= lo_rank <= hi_rank <= {k} (got {lo_rank}, {hi_rank})")
+    h = h.astype(np.int64)
+    inside, valid = h[..., lo_rank:hi_rank + 1].sum(axis=-1), h[..., :k + 1].sum(axis=-1)
+    return inside / valid
+
+
 def best_of_n_curve(distances, metric):
     """curve[n - 1] = metric[argmin(distances[:n])] for n = 1 .. len: the metric of the best-of-n pick over the first n
     paths.  The pick is np.argmin's: a NaN distance first, then the smallest, the first index among equals -- the

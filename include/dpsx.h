@@ -640,6 +640,46 @@ int dpsx_ensemble_ex_f32(const float *x, const float *y /* nullable */, const fl
                          float *var_lo /* nullable */, float *curve /* nullable */, float *info,
                          int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- order statistics: what an image's K particles say per element without assuming a shape -- quantiles (the median,
+ * a credible band), the rank histogram of the label among the particles (the Talagrand diagram) and the CRPS, all from
+ * one per-element sort across the particles.  Evaluation only: nothing here steers a sampler.  tests/quantile_ref.py
+ * restates the definition in float64.
+ *   x [n, d] particles, image-major: M = images images of K = n / M particles each.  y [M, d] the label (nullable).
+ *   probs [q]: a HOST array of doubles, read before the first launch (the call stays graph-capturable); 1 <= q <= 8,
+ *   each in [0, 1].  Everything below is per image and per element e and uses that image's own K values only.
+ *   order    the non-NaN values of an element are ordered by IEEE comparison with -0.0 before +0.0: signed comparison of
+ *            s ^ ((s >> 31) & 0x7fffffff) on the bit pattern s.  A total order: the sorted sequence
+ *            x_(0) <= ... <= x_(K-1) is determined bit for bit.
+ *   quant [M, q, d]: h = probs[i] (K - 1) in double, lo = floor(h), f = h - lo, both formed on the host, once;
+ *            a = x_(lo), b = x_(min(lo + 1, K - 1)).  f == 0 or a == b: the output is a, its bits kept.  Otherwise
+ *            (float)(a + f (b - a)): the subtraction, the product and the sum one rounding in double each, no fma; the
+ *            result is rounded to fp32 once.  +-Inf behave as IEEE gives them; an interpolation that is NaN (-Inf
+ *            against +Inf) is the canonical quiet NaN 0x7fc00000.  If any of the element's K values is NaN, all q
+ *            outputs of the element are 0x7fc00000.
+ *   hist [M, K + 2] int32, only with y (nullable): rank_e = #{j : x_j[e] < y[e]}, strict IEEE comparison, 0 .. K; an
+ *            element whose label or any of whose particles is NaN goes to bin K + 1.  The bins of an image sum to d.
+ *            Exact: integer counts per block, added per column by the finisher.
+ *   info [M, 4] = (mean CRPS, mean of quant[q - 1] - quant[0] (one fp32 subtraction) over the elements where it is
+ *            finite, number of invalid elements, K).  The first is NaN and the third 0 without y.  Per element, in
+ *            double, i 0-based over the sorted values, both sums in sorted order:
+ *                crps_e = (sum_i |x_(i) - y|) / K - (sum_i (2 i - K + 1) x_(i)) / K^2
+ *            rounded to fp32 once.  Invalid elements (bin K + 1) contribute 0 and are left out of the divisor.  The sum
+ *            over e: a lane adds its elements serially in fp32, then a fixed tree per block, one partial per block; the
+ *            finisher adds an image's partials in double in a fixed order and divides once.  The width likewise.
+ * K <= 512.  K <= 64 sorts in registers (a fixed network on K padded to a power of two), 64 < K <= 512 in LDS.  Two
+ * launches on `stream`: the element pass (a lane owns an element; the block count per image is a function of (d, K) only)
+ * and the finisher.  No global atomics, no fence, no allocation, no host read, no memset (graph-capturable; results
+ * depend on the arguments only).  An image's numbers depend neither on M nor on its place in the batch, bit for bit.  A
+ * NaN reaches its own element of its own image only.  x is not written and may have any 4-byte alignment.  The workspace
+ * (dpsx_quantiles_workspace_bytes: the per-block partials; nothing in it outlives the call) serves one stream at a time.
+ * DPSX_EINVAL: a null x, quant, info, workspace or probs; q outside 1 .. 8; a prob outside [0, 1] or NaN; hist without y;
+ * n < 1, d < 1, images < 1, n not divisible by images.  DPSX_EUNSUPPORTED: K > 512 (more than 65535 images, d >= 2^31).
+ * DPSX_EWORKSPACE: a short workspace.  All of them return before anything is launched. */
+int64_t dpsx_quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int dpsx_quantiles_f32(const float *x, const float *y /* nullable */, const double *probs /* host */, int64_t q,
+                       float *quant /* [M, q, d] */, int32_t *hist /* nullable, [M, K + 2] */, float *info /* [M, 4] */,
+                       int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

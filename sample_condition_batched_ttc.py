@@ -160,6 +160,12 @@ def parse_args(argv=None):
     p.add_argument('--posterior_weights', type=str, default='uniform', choices=('uniform', 'smc'),
                    help='--posterior_summary: uniform, or smc: the final importance weights of sampler smc_ddpm '
                         '(one particle group only)')
+    p.add_argument('--posterior_quantiles', type=str, default=None, metavar='P1,P2,...',
+                   help='percentages in [0, 100], at most 8 (e.g. 5,50,95): per image write {fname}_posterior_quantiles.npy '
+                        '[q, C, H, W] (per-pixel quantiles of the paths), posterior_median/{fname}.png (with 50 among them), '
+                        '{fname}_rank_hist.npy (rank histogram of the label among the paths, [K + 2]) and '
+                        '{fname}_quantile_summary.npy = [mean CRPS, mean width, invalid pixels, K]; one particle group of at '
+                        'most 512 paths; one rank only')
     args = p.parse_args(argv)
     if args.path_diversity and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         raise SystemExit("--path_diversity runs on one rank only: the per-group distances are not gathered between ranks "
@@ -376,6 +382,60 @@ class PosteriorSummary:
             np.save(os.path.join(out_path, f'{fname}_posterior_summary.npy'), rec[b])
 
 
+def quantile_percentages(text):
+    """--posterior_quantiles: 'P1,P2,...' -> the percentages as floats (ValueError for anything that is not a number)"""
+    return [float(v) for v in str(text).split(',') if v.strip() != '']
+
+
+def check_posterior_quantiles(args, sampler_name, world=1):
+    """--posterior_quantiles: reject what it does not support, before any GPU work (one-line message)"""
+    if args.posterior_quantiles is None:
+        return
+    try:
+        pct = quantile_percentages(args.posterior_quantiles)
+    except ValueError:
+        raise SystemExit(f"--posterior_quantiles takes percentages separated by commas (got {args.posterior_quantiles!r})")
+    if not 1 <= len(pct) <= 8:
+        raise SystemExit(f"--posterior_quantiles takes between 1 and 8 percentages (got {len(pct)})")
+    if any(not (0.0 <= v <= 100.0) for v in pct):
+        raise SystemExit(f"--posterior_quantiles takes percentages in [0, 100] (got {args.posterior_quantiles})")
+    if world > 1:
+        raise SystemExit("--posterior_quantiles runs on one rank only: the particles of an image are not gathered between "
+                         f"ranks (WORLD_SIZE={world})")
+    if sampler_name == 'search_ddpm':
+        raise SystemExit("--posterior_quantiles needs a particle set: sampler search_ddpm keeps one state per image")
+    if args.n_paths != args.batch_size:
+        raise SystemExit("--posterior_quantiles takes one particle group per image: the order statistics of two groups do not "
+                         f"merge (n_paths {args.n_paths}, batch_size {args.batch_size})")
+    if args.batch_size > 512:
+        raise SystemExit(f"--posterior_quantiles takes at most 512 paths per image (--batch_size {args.batch_size})")
+
+
+class PosteriorQuantiles:
+    """--posterior_quantiles: the order statistics of the one particle group (metrics.posterior_quantiles) and the files
+    per image"""
+
+    def __init__(self, refs, text):
+        self.refs, self.pct, self.last = refs, quantile_percentages(text), None
+
+    def add(self, sample):
+        from dps_ttc_amd.metrics import posterior_quantiles
+        self.last = posterior_quantiles(self.refs, sample, n_images=self.refs.shape[0], probs=[v / 100.0 for v in self.pct])
+
+    def save(self, out_path, fnames):
+        s = self.last
+        quant, hist, info = s["quantiles"].cpu().numpy(), s["hist"].cpu().numpy(), s["info"].cpu().numpy()
+        if 50.0 in self.pct:
+            os.makedirs(os.path.join(out_path, 'posterior_median'), exist_ok=True)
+        for b, fname in enumerate(fnames):
+            np.save(os.path.join(out_path, f'{fname}_posterior_quantiles.npy'), quant[b])
+            np.save(os.path.join(out_path, f'{fname}_rank_hist.npy'), hist[b])
+            np.save(os.path.join(out_path, f'{fname}_quantile_summary.npy'), info[b])
+            if 50.0 in self.pct:
+                imsave(os.path.join(out_path, 'posterior_median', fname + '.png'),
+                       clear_color(s["quantiles"][b:b + 1, self.pct.index(50.0)]))
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
@@ -396,6 +456,8 @@ def main(argv=None):
         check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
     if args.posterior_summary or args.posterior_weights != 'uniform':
         check_posterior_summary(args, sampler_name, world)
+    if args.posterior_quantiles is not None:
+        check_posterior_quantiles(args, sampler_name, world)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1)
@@ -544,6 +606,7 @@ def main(argv=None):
         device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
         diversity = []
         posterior = PosteriorSummary(ref_img, args.posterior_weights) if args.posterior_summary else None
+        quantiles = PosteriorQuantiles(ref_img, args.posterior_quantiles) if args.posterior_quantiles is not None else None
         for g in my_groups:
             x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
@@ -559,6 +622,8 @@ def main(argv=None):
                 diversity.append(path_diversity(sample)[0])
             if posterior is not None:
                 posterior.add(sample, sampler)
+            if quantiles is not None:  # one group (check_posterior_quantiles)
+                quantiles.add(sample)
             if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
                 pm = pathwise_metrics(ref_img, sample)
                 pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -593,6 +658,8 @@ def main(argv=None):
                 np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack(diversity))
             if posterior is not None:  # one rank (check_posterior_summary)
                 posterior.save(out_path, [fname])
+            if quantiles is not None:  # one rank (check_posterior_quantiles)
+                quantiles.save(out_path, [fname])
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -634,6 +701,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
     device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
     diversity = []
     posterior = PosteriorSummary(refs, args.posterior_weights) if args.posterior_summary else None
+    quantiles = PosteriorQuantiles(refs, args.posterior_quantiles) if args.posterior_quantiles is not None else None
     for g in range(groups):
         x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
@@ -649,6 +717,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
             diversity.append(path_diversity(sample, images=B))
         if posterior is not None:
             posterior.add(sample, sampler)
+        if quantiles is not None:
+            quantiles.add(sample)
         if device_metrics:            # one device call and one copy for the group's B x K particles
             pm = pathwise_metrics(refs, sample, n_images=B)
             pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -689,6 +759,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
             np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack([v[b] for v in diversity]))
     if posterior is not None:
         posterior.save(out_path, fnames)
+    if quantiles is not None:
+        quantiles.save(out_path, fnames)
 
 
 if __name__ == '__main__':

@@ -53,6 +53,12 @@ repetitions alternated in one process: (a) kernels.ensemble_stats with the label
 (all three launches), (b) torch ops giving the same outputs (var_mean; cumsum / n - y, squared, mean), (c) the byte floor
 ((K + 1) D 4 read + 2 D 4 written per image at 8 TB/s), (d) K3 at the same N for scale: (a)'s rate against its floor's bytes
 is also stated as a fraction of K3's rate in the same run.
+    python tools/kbench.py --quantiles                                                (order statistics, 256^2)
+--quantiles: the same three shapes, 3 x --reps repetitions alternated in one process: (a) kernels.order_stats with the label
+(quantiles 5 / 50 / 95 %, rank histogram, CRPS: element pass + finisher) and (a') without the label and with one probability
+(the loads and the sort alone, so the difference to (a) is the sweep's and the emit's), (b) the same outputs as torch ops
+(torch.sort along the particle axis, the gathers and the interpolation, the rank count, the sorted-order CRPS), (c) the byte
+floor ((K + 1) D 4 read once per image at 8 TB/s), (d) K3 at the same N for scale.
 """
 import argparse
 import os
@@ -83,7 +89,10 @@ def main():
     ap.add_argument("--metrics", action="store_true", help="time per-path PSNR / SSIM: host loop / torch ops / image_metrics")
     ap.add_argument("--repulse", action="store_true", help="time particle repulsion: the distances / the whole call / torch ops / K3")
     ap.add_argument("--ensemble", action="store_true", help="time the ensemble statistics: the call / torch ops / the byte floor / K3")
+    ap.add_argument("--quantiles", action="store_true", help="time the order statistics: the call / torch ops / the byte floor / K3")
     args = ap.parse_args()
+    if args.quantiles:
+        return quantiles_step(args)
     if args.ensemble:
         return ensemble_step(args)
     if args.repulse:
@@ -715,6 +724,87 @@ def ensemble_step(args):
             print(f"ensemble 256^2 M={M} K={k:3d} {name:44s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
                   flush=True)
         del x, y, e, buf, g_unet
+
+
+def quantiles_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    c, h, w = 3, 256, 256
+    D, P = c * h * w, c * h * w * 4
+    probs = (0.05, 0.5, 0.95)
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for M, k in ((4, 16), (1, 64), (1, 512)):
+        n = M * k
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        y = torch.randn(M, c, h, w, device=dev, generator=gen)
+        x = (np.sqrt(0.5) * y[:, None] + np.sqrt(0.5) * torch.randn(M, k, c, h, w, device=dev, generator=gen)).reshape(n, c, h, w)
+        x = x.contiguous()
+        g_unet = 1e-3 * torch.randn(n, c, h, w, device=dev, generator=gen)
+        buf = kernels.StepBuffers(None, n, c, h, w, dev)
+        buf.sample.copy_(x)
+        pos = [(int(np.floor(p * (k - 1))), min(int(np.floor(p * (k - 1))) + 1, k - 1), p * (k - 1) - np.floor(p * (k - 1)))
+               for p in probs]
+        coef = (2.0 * torch.arange(k, device=dev, dtype=torch.float64) - k + 1).view(1, k, 1)
+
+        def a_call(i):
+            kernels.order_stats(x, images=M, probs=probs, label=y)
+
+        def a_sort(i):
+            kernels.order_stats(x, images=M, probs=(0.5,))
+
+        def b_torch(i):
+            xf, yf = x.view(M, k, D), y.view(M, 1, D)
+            xs = torch.sort(xf, dim=1).values
+            quant = torch.stack([(xs[:, lo].double() + f * (xs[:, hi].double() - xs[:, lo].double())).float()
+                                 for lo, hi, f in pos], dim=1)
+            rank = (xf < yf).sum(dim=1)
+            hist = torch.zeros(M, k + 2, device=dev, dtype=torch.int64).scatter_add_(1, rank, torch.ones_like(rank))
+            xd = xs.double()
+            crps = ((xd - yf.double()).abs().sum(dim=1) / k - (coef * xd).sum(dim=1) / (k * k)).float().mean(dim=1)
+            return quant, hist, crps, (quant[:, -1] - quant[:, 0]).mean(dim=1)
+
+        def d_k3(i):
+            kernels.step_update(buf, g_unet, ck)
+
+        forms = (("a order_stats with the label (pass + finisher)", a_call), ("a' order_stats, no label, one probability", a_sort),
+                 ("b torch sort + gathers + rank count + CRPS", b_torch), ("d K3 (step_update) for scale", d_k3))
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        floor_bytes = M * (k + 1) * P
+        t_k3 = float(np.concatenate(res["d K3 (step_update) for scale"]).mean())
+        k3_rate = 4 * P * n / t_k3
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            note = ""
+            if name[0] == "a":
+                rate = floor_bytes / ts.mean()
+                note = (f"  c floor {floor_bytes / 8e6:.1f} us ({floor_bytes / 8e6 / ts.mean():.2f} of it); {rate / 1e3:.0f} GB/s = "
+                        f"{rate / k3_rate:.2f} x K3's rate")
+            elif name[0] == "d":
+                note = f"  {k3_rate / 1e3:.0f} GB/s (4 P/particle)"
+            print(f"quantiles 256^2 M={M} K={k:3d} {name:48s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
+                  flush=True)
+        del x, y, buf, g_unet
 
 
 def noise_draw(args):
