@@ -124,6 +124,8 @@ SIGNATURES = {
     "dpsx_ensemble_ex_f32": (c_int, [_f, _f, _f, _i64, _f, _f, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_quantiles_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "dpsx_quantiles_f32": (c_int, [_f, _f, POINTER(c_double), _i64, _f, _p, _f, _i64, _i64, _i64, _p, _i64, _p]),
+    "dpsx_pca_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "dpsx_pca_f32": (c_int, [_f, _i64, _f, _f, _f, _f, _f, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_pack_champion_f32": (c_int, [_f, _f, _p, _f, _f, _i64, _i64, _p]),
     "dpsx_select_champion_f32": (c_int, [_f, _i64, _i64, _f, _i64, _p, _p, _p]),
 }

@@ -783,6 +783,31 @@ int dpsx_quantiles_f32(const float *x, const float *y, const double *probs, int6
     return quantiles(x, y, probs, q, quant, hist, info, n, d, images, workspace, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ principal components (pca.hip)
+static int pca_shape(int64_t n, int64_t d, int64_t images)
+{
+    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
+    if (n / images > kPcaMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
+    return DPSX_OK;
+}
+
+int64_t dpsx_pca_workspace_bytes(int64_t n, int64_t d, int64_t images)
+{
+    const int rc = pca_shape(n, d, images);
+    return rc != DPSX_OK ? rc : pca_workspace_bytes(n, d, images);
+}
+
+int dpsx_pca_f32(const float *x, int64_t q, float *dirs, float *evals, float *coords, float *info, float *d2, int64_t n,
+                 int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!x || !dirs || !evals || !coords || !info || !workspace) return DPSX_EINVAL;
+    if (q < 1 || q > kPcaMaxQ) return DPSX_EINVAL;
+    const int rc = pca_shape(n, d, images);
+    if (rc != DPSX_OK) return rc;
+    if (workspace_bytes < pca_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    return pca(x, q, dirs, evals, coords, info, d2, n, d, images, workspace, (hipStream_t)stream);
+}
+
 int dpsx_update_f32(const float *sample, const float *g_a, const float *g_b, float *out, int64_t count,
                     void *stream)
 {

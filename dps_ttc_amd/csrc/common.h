@@ -751,6 +751,15 @@ int64_t quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images);
 int quantiles(const float *x, const float *y, const double *probs, int64_t q, float *quant, int32_t *hist, float *info,
               int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s);
 
+// pca.hip: the top q principal components of every image's particles (the definition is stated in include/dpsx.h); the
+// caller checked the arguments (images | n, 1 <= n / images <= kPcaMaxK, 1 <= q <= kPcaMaxQ) and the workspace size.
+// d2: nullable (the workspace holds it).  G and V of the eigensolver live in LDS: two kPcaMaxK x (kPcaMaxK + 1) fp32 matrices
+constexpr int kPcaMaxK = 128;
+constexpr int kPcaMaxQ = 8;
+int64_t pca_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int pca(const float *x, int64_t q, float *dirs, float *evals, float *coords, float *info, float *d2, int64_t n, int64_t d,
+        int64_t images, void *workspace, hipStream_t s);
+
 // phase.hip
 int phase_create(dpsx_op *op, const PhaseOp &shape);
 void phase_destroy(dpsx_op *op);

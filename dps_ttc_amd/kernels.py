@@ -4,6 +4,7 @@ Every function here enqueues hand-written HIP kernels on torch's current
 stream; tensors are only the owners of device memory.  Nothing in this module
 computes with torch ops.
 """
+import contextlib
 import ctypes
 from ctypes import byref, c_int64, c_void_p
 
@@ -1264,6 +1265,63 @@ def order_stats(x, images=1, probs=(0.05, 0.5, 0.95), label=None, stream=None):
     res = {"quantiles": quant, "info": info}
     if label is not None:
         res["hist"], res["crps"] = hist, info[:, 0]
+    return res
+
+
+# ------------------------------------------------------------------ principal components (include/dpsx.h: "principal components")
+PCA_MAX_K = 128          # particles per image (DPSX_EUNSUPPORTED above): the eigensolver's matrices live in LDS
+PCA_MAX_Q = 8            # components per call
+PCA_INFO = ("trace", "rank", "sweeps", "count")          # the columns of info [M, 4]
+_pca_ws = {}             # (device, n, d, images) -> the call's workspace, as _metrics_ws
+
+
+def pca_components(value, what="components"):
+    """the component count of a particle_pca call as the library takes it: an integer in 1 .. 8 (ValueError otherwise)"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= PCA_MAX_Q:
+        raise ValueError(f"{what} must be an integer in 1 .. {PCA_MAX_Q} (got {value!r})")
+    return int(value)
+
+
+def particle_pca(x, images=1, components=4, want_d2=False, stream=None):
+    """The principal components of every image's particles, one device call (dpsx_pca_f32, four launches): x [N, C, H, W]
+    image-major, `images` images of K = N / images <= 128 particles; x is not written.  components: q in 1 .. 8.
+    -> {"dirs": [M, q, C, H, W] (unit directions u_j, descending variance), "evals": [M, q] (eigenvalues of the centred
+    Gram matrix), "var": [M, q] (evals / K: the biased variance along u_j), "explained": [M, q] (evals / trace),
+    "coords": [M, K, q] (the score of particle i along u_j), "info": [M, 4] (PCA_INFO)} and, with want_d2, "d2": [M, K, K]
+    (kernels.pairwise_sqdist's bits).  A component below the solver's resolution is all zero; an image of equal particles
+    is all zero with rank 0 (its `explained` is 0 / 0 = NaN); an image with a NaN / Inf in it is NaN with rank -1.  The
+    library's refusals are raised as ValueError before any launch.  No host read; the workspace is cached per shape and
+    serves one stream at a time."""
+    x = f32c(x, "particles")
+    if x.dim() != 4:
+        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
+    n, images = int(x.shape[0]), int(images)
+    if images < 1 or n < 1 or n % images:
+        raise ValueError(f"{n} particles do not split into {images} images")
+    k, d = n // images, int(x[0].numel())
+    if k > PCA_MAX_K:
+        raise ValueError(f"principal components take at most {PCA_MAX_K} particles per image (got {k})")
+    if d < 1 or images > 65535 or d >= 2 ** 31:
+        raise ValueError(f"principal components take 1 <= C H W < 2^31 and at most 65535 images (got {d}, {images})")
+    q = pca_components(components)
+    key = (x.device, n, d, images)
+    ws = _pca_ws.get(key)
+    if ws is None:
+        need = lib().dpsx_pca_workspace_bytes(n, d, images)
+        if need < 0:
+            check(int(need), "dpsx_pca_workspace_bytes")
+        ws = _pca_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    f = dict(dtype=torch.float32, device=x.device)
+    dirs = torch.empty((images, q) + tuple(x.shape[1:]), **f)
+    evals, coords, info = torch.empty((images, q), **f), torch.empty((images, k, q), **f), torch.empty((images, 4), **f)
+    d2 = torch.empty((images, k, k), **f) if want_d2 else None
+    check(lib().dpsx_pca_f32(ptr(x), q, ptr(dirs), ptr(evals), ptr(coords), ptr(info), ptr(d2), n, d, images, ptr(ws),
+                             ws.numel(), _stream_arg(stream, x)), "dpsx_pca_f32")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():    # the derived columns follow the launches
+        var, explained = evals / float(k), evals / info[:, 0:1]
+    res = {"dirs": dirs, "evals": evals, "var": var, "explained": explained, "coords": coords, "info": info}
+    if want_d2:
+        res["d2"] = d2
     return res
 
 

@@ -80,6 +80,24 @@ def posterior_quantiles(refs, samples, n_images=1, probs=(0.05, 0.5, 0.95)):
     return kernels.order_stats(samples.detach(), images=n_images, probs=probs, label=refs)
 
 
+def posterior_pca(samples, n_images=1, components=4):
+    """The principal directions of the particles' posterior uncertainty: samples [N, C, H, W] (image-major, n_images images
+    of K <= 128 particles) -> {"dirs" [M, q, C, H, W], "evals", "var", "explained" [M, q], "coords" [M, K, q], "info"
+    [M, 4] = (trace, rank, sweeps, K)}.  One device call (kernels.particle_pca), no host read."""
+    from . import kernels
+    return kernels.particle_pca(samples.detach(), images=n_images, components=components)
+
+
+def pc_panels(mean, dirs, var, n_sigma=2.0):
+    """(minus, plus) = mean -+ n_sigma sqrt(var_j) u_j: mean [M, C, H, W], dirs [M, q, C, H, W], var [M, q] -> two
+    [M, q, C, H, W] tensors, the panels that show what component j changes in the image.  Device ops, no host read."""
+    if dirs.dim() != 5 or tuple(mean.shape) != (dirs.shape[0],) + tuple(dirs.shape[2:]) or tuple(var.shape) != tuple(dirs.shape[:2]):
+        raise ValueError(f"mean [M, C, H, W], dirs [M, q, C, H, W] and var [M, q] are taken (got {tuple(mean.shape)}, "
+                         f"{tuple(dirs.shape)}, {tuple(var.shape)})")
+    step = (float(n_sigma) * torch.sqrt(var)).reshape(*var.shape, 1, 1, 1) * dirs
+    return mean.unsqueeze(1) - step, mean.unsqueeze(1) + step
+
+
 def interval_coverage(hist, lo_rank, hi_rank):
     """The fraction of an image's valid elements whose label's rank lies in lo_rank .. hi_rank (both included): hist
     [M, K + 2] or [K + 2] integer rank histograms (bin K + 1, the invalid elements, is left out of the divisor) -> [M] or a

@@ -680,6 +680,63 @@ int dpsx_quantiles_f32(const float *x, const float *y /* nullable */, const doub
                        float *quant /* [M, q, d] */, int32_t *hist /* nullable, [M, K + 2] */, float *info /* [M, 4] */,
                        int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- principal components: in which directions an image's K particles vary together -- the top q eigenvectors of their
+ * sample covariance (shown as mean +- 2 sigma_j u_j), the variance along each and every particle's score along it.  With
+ * K << d this is a K x K problem: the eigenpairs of the centred Gram matrix, projected back to image space.  Evaluation
+ * only: nothing here steers a sampler.  tests/pca_ref.py restates the definition in float64.
+ *   x [n, d] particles, image-major: M = images images of K = n / M particles each; 1 <= q <= 8 components.  Everything
+ *   below is per image and uses the image's own particles only.
+ *   d2       [K, K], exactly what dpsx_pairwise_sqdist_f32 defines: the same two launches, the same bits.
+ *   G        the centred Gram matrix, G_ij = (x_i - mean) . (x_j - mean) = -1/2 (d2_ij - r_i - r_j + t) with
+ *            r_i = (sum_j d2_ij) / K and t = (sum_i r_i) / K, both in double over the fp32 entries in index order;
+ *            G_ij = (float)(-0.5 (((d2_ij - r_lo) - r_hi) + t)) with lo = min(i, j), hi = max(i, j), every operation one
+ *            rounding in double: symmetric bit for bit.  trace = sum_i G_ii in double over the fp32 entries in index order
+ *            (= sum_i |x_i - mean|^2).
+ *   eigenpairs  G = V L V^T by the cyclic Jacobi method in fp32, the rotations of a sweep in a fixed (round-robin) order
+ *            that depends on K only.  A rotation is skipped where |g_pq| <= 2^-24 sqrt(|g_pp g_qq|).  After every sweep:
+ *            off = the sum of the squared off-diagonal entries, total = that of all entries, in double in a fixed order;
+ *            the sweeps end when off <= K 2^-46 total (an off-diagonal norm of sqrt(K) 2^-23 |G|_F: above the rounding
+ *            floor of the rotations, which sits near sqrt(K) 2^-26) or after 24 sweeps.  l_i = the diagonal; the order is
+ *            descending, the lower index first among equal values.
+ *   null     component j is null if j >= K or l_j <= K 2^-23 l_0 (the product formed in fp32, K 2^-23 first) or
+ *            l_j <= 0: below the resolution of an fp32 Jacobi method on a K x K matrix, negative round-off included.
+ *            A null component has evals = +0.0 and all-zero dirs and coords.
+ *   centring every non-null v_j among the first q is centred and renormalised: v_ij <- (v_ij - m_j) / |v_j - m_j| with m_j
+ *            the mean of its entries, in double in index order, each entry rounded to fp32 once.  An eigenvector of a
+ *            non-zero eigenvalue of G is orthogonal to the constant vector; the part along it that fp32 rounding leaves
+ *            (about 2^-23 l_0 / l_j) would enter dirs multiplied by (mean - x_0) / sqrt(l_j).  The eigenvalue reported
+ *            for it is the Rayleigh quotient of the unit vector, l_j <- (float)(l_j / |v_j - m_j|^2) (the accumulated
+ *            rotations leave |v_j| within about 1e-5 of 1 at K = 128, and the diagonal is v_j^T G v_j of that v_j); the
+ *            order, the null rule and rank use the diagonal as the sweeps left it.
+ *   sign     in every non-null v_j the entry of largest magnitude is then positive (the lowest index wins ties).
+ *   evals [M, q] = l_j (0 for a null component).  coords [M, K, q]: c_ij = sqrt(l_j) v_ij (one fp32 square root, one product): the score of
+ *            particle i along component j.
+ *   dirs [M, q, d]: u_j[e] = S_j[e] (1 / l_j), S_j[e] = sum_i c_ij (x_i[e] - x_0[e]): i = 0 .. K - 1 in index order, each
+ *            term one fp32 subtraction and one fp32 fma into the sum; 1 / l_j one fp32 division, the product one rounding.
+ *            (The scores of a component sum to zero, so any common offset drops out; x_0 keeps the differences small.)
+ *            Unit norm and mutually orthogonal up to rounding.
+ *   info [M, 4] = (trace, rank, sweeps, K): rank = the number of non-null eigenvalues among all K; sweeps = the sweeps
+ *            performed.  The variance along component j is l_j / K (the biased one, as dpsx_ensemble_f32's: trace / K is the
+ *            sum over the elements of its var), its share of the total l_j / trace.
+ *   degenerate images, decided inside the launches with no host read.  K = 1, or t exactly 0 (all particles equal): every
+ *            output is +0.0, rank 0, no rotation is performed.  t not finite (a NaN or Inf anywhere in the image): evals,
+ *            dirs, coords and info[0] are the canonical quiet NaN 0x7fc00000, rank is -1, sweeps 0; the flag reaches that
+ *            image only.  24 sweeps without convergence: rank is -2, the other outputs are what the last sweep left.
+ * K <= 128: G and V live in the 160 KiB of LDS of one compute unit (two fp32 matrices of 128 x 129 words); more particles
+ * need a blocked or global-memory solver.  Four launches on `stream`: the two distance launches, the eigensolver (one
+ * workgroup per image, instantiated for K <= 32 / 64 / 128) and the projection (lanes across elements, float4 units where
+ * d % 4 == 0 and x / dirs are 16-byte aligned, else the scalar instantiation of the same body).  No atomics, no fence, no
+ * allocation, no host read, no memset (graph-capturable).  An image's numbers depend neither on M nor on its place in the
+ * batch, bit for bit.  x is not written.  d2 [M, K, K] is a nullable output.  The workspace (dpsx_pca_workspace_bytes:
+ * the distance launches' partials and d2; nothing in it outlives the call) serves one stream at a time.
+ * DPSX_EINVAL: a null x, dirs, evals, coords, info or workspace; q outside 1 .. 8; n < 1, d < 1, images < 1, n not
+ * divisible by images.  DPSX_EUNSUPPORTED: K > 128, more than 65535 images, d >= 2^31.  DPSX_EWORKSPACE: a short workspace.
+ * All of them return before anything is launched. */
+int64_t dpsx_pca_workspace_bytes(int64_t n, int64_t d, int64_t images);
+int dpsx_pca_f32(const float *x, int64_t q, float *dirs /* [M, q, d] */, float *evals /* [M, q] */,
+                 float *coords /* [M, K, q] */, float *info /* [M, 4] */, float *d2 /* nullable, [M, K, K] */,
+                 int64_t n, int64_t d, int64_t images, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- the device half of the multi-GPU champion exchange (best-of-N across ranks: gaussian_diffusion.py:626-633 and
  * best_of_n_simple.py:32-40 over a sharded particle set).  The collective itself stays with the caller's communicator
  * (RCCL through torch.distributed); these two launches replace the seven small device ops around it -- argmin, copy,

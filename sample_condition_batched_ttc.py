@@ -166,6 +166,12 @@ def parse_args(argv=None):
                         '{fname}_rank_hist.npy (rank histogram of the label among the paths, [K + 2]) and '
                         '{fname}_quantile_summary.npy = [mean CRPS, mean width, invalid pixels, K]; one particle group of at '
                         'most 512 paths; one rank only')
+    p.add_argument('--posterior_pca', type=int, default=None, metavar='Q',
+                   help='1 <= Q <= 8 principal components of the paths per image: write {fname}_posterior_pcs.npy [Q, C, H, W] '
+                        '(unit directions), {fname}_pca_summary.npy [Q, 2] = (variance along it, share of the total variance), '
+                        '{fname}_pca_coords.npy [K, Q] (the score of every path) and '
+                        'posterior_pca/{fname}_pc{j}_{minus,plus}.png = mean -+ 2 sigma_j u_j; one particle group of at most '
+                        '128 paths; one rank only')
     args = p.parse_args(argv)
     if args.path_diversity and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         raise SystemExit("--path_diversity runs on one rank only: the per-group distances are not gathered between ranks "
@@ -436,6 +442,53 @@ class PosteriorQuantiles:
                        clear_color(s["quantiles"][b:b + 1, self.pct.index(50.0)]))
 
 
+def check_posterior_pca(args, sampler_name, world=1):
+    """--posterior_pca: reject what it does not support, before any GPU work (one-line message)"""
+    if args.posterior_pca is None:
+        return
+    if not 1 <= args.posterior_pca <= 8:
+        raise SystemExit(f"--posterior_pca takes between 1 and 8 components (got {args.posterior_pca})")
+    if world > 1:
+        raise SystemExit("--posterior_pca runs on one rank only: the particles of an image are not gathered between "
+                         f"ranks (WORLD_SIZE={world})")
+    if sampler_name == 'search_ddpm':
+        raise SystemExit("--posterior_pca needs a particle set: sampler search_ddpm keeps one state per image")
+    if args.n_paths != args.batch_size:
+        raise SystemExit("--posterior_pca takes one particle group per image: the components of two groups do not "
+                         f"merge (n_paths {args.n_paths}, batch_size {args.batch_size})")
+    if args.batch_size > 128:
+        raise SystemExit(f"--posterior_pca takes at most 128 paths per image (--batch_size {args.batch_size})")
+
+
+class PosteriorPca:
+    """--posterior_pca: the principal components of the one particle group (metrics.posterior_pca), the panels around the
+    group's mean (kernels.ensemble_stats) and the files per image"""
+
+    def __init__(self, n_images, components):
+        self.n_images, self.q, self.last, self.panels = n_images, components, None, None
+
+    def add(self, sample):
+        from dps_ttc_amd import kernels
+        from dps_ttc_amd.metrics import pc_panels, posterior_pca
+        self.last = posterior_pca(sample, n_images=self.n_images, components=self.q)
+        mean = kernels.ensemble_stats(sample.detach(), images=self.n_images)["mean"]
+        self.panels = pc_panels(mean, self.last["dirs"], self.last["var"])
+
+    def save(self, out_path, fnames):
+        s = self.last
+        dirs, coords = s["dirs"].cpu().numpy(), s["coords"].cpu().numpy()
+        rec = torch.stack([s["var"], s["explained"]], dim=2).cpu().numpy()
+        os.makedirs(os.path.join(out_path, 'posterior_pca'), exist_ok=True)
+        for b, fname in enumerate(fnames):
+            np.save(os.path.join(out_path, f'{fname}_posterior_pcs.npy'), dirs[b])
+            np.save(os.path.join(out_path, f'{fname}_pca_summary.npy'), rec[b])
+            np.save(os.path.join(out_path, f'{fname}_pca_coords.npy'), coords[b])
+            for j in range(self.q):
+                for side, panel in zip(('minus', 'plus'), self.panels):
+                    imsave(os.path.join(out_path, 'posterior_pca', f'{fname}_pc{j}_{side}.png'),
+                           clear_color(panel[b:b + 1, j]))
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
@@ -458,6 +511,8 @@ def main(argv=None):
         check_posterior_summary(args, sampler_name, world)
     if args.posterior_quantiles is not None:
         check_posterior_quantiles(args, sampler_name, world)
+    if args.posterior_pca is not None:
+        check_posterior_pca(args, sampler_name, world)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1)
@@ -607,6 +662,7 @@ def main(argv=None):
         diversity = []
         posterior = PosteriorSummary(ref_img, args.posterior_weights) if args.posterior_summary else None
         quantiles = PosteriorQuantiles(ref_img, args.posterior_quantiles) if args.posterior_quantiles is not None else None
+        pca = PosteriorPca(1, args.posterior_pca) if args.posterior_pca is not None else None
         for g in my_groups:
             x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
             sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
@@ -624,6 +680,8 @@ def main(argv=None):
                 posterior.add(sample, sampler)
             if quantiles is not None:  # one group (check_posterior_quantiles)
                 quantiles.add(sample)
+            if pca is not None:        # one group (check_posterior_pca)
+                pca.add(sample)
             if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
                 pm = pathwise_metrics(ref_img, sample)
                 pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -660,6 +718,8 @@ def main(argv=None):
                 posterior.save(out_path, [fname])
             if quantiles is not None:  # one rank (check_posterior_quantiles)
                 quantiles.save(out_path, [fname])
+            if pca is not None:        # one rank (check_posterior_pca)
+                pca.save(out_path, [fname])
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -702,6 +762,7 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
     diversity = []
     posterior = PosteriorSummary(refs, args.posterior_weights) if args.posterior_summary else None
     quantiles = PosteriorQuantiles(refs, args.posterior_quantiles) if args.posterior_quantiles is not None else None
+    pca = PosteriorPca(B, args.posterior_pca) if args.posterior_pca is not None else None
     for g in range(groups):
         x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
         sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
@@ -719,6 +780,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
             posterior.add(sample, sampler)
         if quantiles is not None:
             quantiles.add(sample)
+        if pca is not None:
+            pca.add(sample)
         if device_metrics:            # one device call and one copy for the group's B x K particles
             pm = pathwise_metrics(refs, sample, n_images=B)
             pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
@@ -761,6 +824,8 @@ def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_n
         posterior.save(out_path, fnames)
     if quantiles is not None:
         quantiles.save(out_path, fnames)
+    if pca is not None:
+        pca.save(out_path, fnames)
 
 
 if __name__ == '__main__':

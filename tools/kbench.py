@@ -59,6 +59,13 @@ is also stated as a fraction of K3's rate in the same run.
 (the loads and the sort alone, so the difference to (a) is the sweep's and the emit's), (b) the same outputs as torch ops
 (torch.sort along the particle axis, the gathers and the interpolation, the rank count, the sorted-order CRPS), (c) the byte
 floor ((K + 1) D 4 read once per image at 8 TB/s), (d) K3 at the same N for scale.
+    python tools/kbench.py --pca [--pca-shape I]                                      (principal components, 256^2)
+--pca: M = 4 x K = 16, K = 64, K = 128 (or shape I of them alone), q = 4, particles = base + 6 planted directions + noise,
+3 x --reps repetitions alternated in one process: (a) kernels.particle_pca (four launches), (b) kernels.pairwise_sqdist (its
+first two), (c) the same computation as torch ops (centre, X X^T, torch.linalg.eigh, the top q, one matmul), (d) K3 at the
+same N for scale.  The launches apart come from a kernel trace of the same run (rocprofv3 --kernel-trace -d DIR -- ...):
+    python tools/kbench.py --pca-trace DIR --pca-shape I
+prints every launch's average and the projection's rate against its (K + q) D 4 bytes per image beside K3's 4 P per particle.
 """
 import argparse
 import os
@@ -90,7 +97,14 @@ def main():
     ap.add_argument("--repulse", action="store_true", help="time particle repulsion: the distances / the whole call / torch ops / K3")
     ap.add_argument("--ensemble", action="store_true", help="time the ensemble statistics: the call / torch ops / the byte floor / K3")
     ap.add_argument("--quantiles", action="store_true", help="time the order statistics: the call / torch ops / the byte floor / K3")
+    ap.add_argument("--pca", action="store_true", help="time the principal components: the call / the distances / torch ops / K3")
+    ap.add_argument("--pca-shape", type=int, default=None, help="--pca / --pca-trace: one of the three shapes (0, 1, 2)")
+    ap.add_argument("--pca-trace", default=None, metavar="DIR", help="the per-launch table from a kernel trace of a --pca run")
     args = ap.parse_args()
+    if args.pca_trace:
+        return pca_trace(args)
+    if args.pca:
+        return pca_step(args)
     if args.quantiles:
         return quantiles_step(args)
     if args.ensemble:
@@ -805,6 +819,106 @@ def quantiles_step(args):
             print(f"quantiles 256^2 M={M} K={k:3d} {name:48s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
                   flush=True)
         del x, y, buf, g_unet
+
+
+PCA_SHAPES = ((4, 16), (1, 64), (1, 128))      # M, K at 3 x 256^2
+PCA_Q = 4
+
+
+def pca_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    c, h, w = 3, 256, 256
+    D, P, q = c * h * w, c * h * w * 4, PCA_Q
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    shapes = PCA_SHAPES if args.pca_shape is None else (PCA_SHAPES[args.pca_shape],)
+    for M, k in shapes:
+        n = M * k
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        base = torch.rand(M, 1, D, device=dev, generator=gen) * 2 - 1
+        u = torch.linalg.qr(torch.randn(M, D, 6, device=dev, generator=gen)).Q
+        amp = 0.2 * np.sqrt(D) * 0.5 ** torch.arange(6, device=dev)
+        x = base + (torch.randn(M, k, 6, device=dev, generator=gen) * amp) @ u.transpose(1, 2) + \
+            0.05 * torch.randn(M, k, D, device=dev, generator=gen)
+        x = x.reshape(n, c, h, w).contiguous()
+        g_unet = 1e-3 * torch.randn(n, c, h, w, device=dev, generator=gen)
+        buf = kernels.StepBuffers(None, n, c, h, w, dev)
+        buf.sample.copy_(x)
+
+        def a_call(i):
+            return kernels.particle_pca(x, images=M, components=q)
+
+        def b_dist(i):
+            return kernels.pairwise_sqdist(x, images=M)
+
+        def c_torch(i):
+            xf = x.view(M, k, D)
+            mean = xf.mean(dim=1, keepdim=True)
+            xc = xf - mean
+            lam, v = torch.linalg.eigh(xc @ xc.transpose(1, 2))
+            lam, v = lam[:, -q:].flip(1), v[:, :, -q:].flip(2)
+            coords = v * lam.clamp_min(0).sqrt().unsqueeze(1)
+            return (coords.transpose(1, 2) @ xc) / lam.unsqueeze(2), lam, coords
+
+        def d_k3(i):
+            kernels.step_update(buf, g_unet, ck)
+
+        sweeps = a_call(0)["info"][:, 2].cpu().numpy()
+        forms = (("a particle_pca (distances + eigensolver + projection)", a_call), ("b pairwise_sqdist (the distances alone)", b_dist),
+                 ("c torch centre + X X^T + eigh + matmul", c_torch), ("d K3 (step_update) for scale", d_k3))
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for name, fn in forms:
+                res.setdefault(name, []).append(timed(fn))
+        t_k3 = float(np.concatenate(res["d K3 (step_update) for scale"]).mean())
+        for name, _ in forms:
+            ts = np.concatenate(res[name])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[name])
+            note = f"  sweeps {sweeps.tolist()}" if name[0] == "a" else (f"  {4 * P * n / t_k3 / 1e3:.0f} GB/s (4 P/particle)" if name[0] == "d" else "")
+            print(f"pca 256^2 M={M} K={k:3d} q={q} {name:54s} avg {ts.mean():9.1f} us  min {ts.min():9.1f}  (runs {runs}){note}",
+                  flush=True)
+        del x, buf, g_unet
+
+
+def pca_trace(args):
+    """the launches of a traced `--pca --pca-shape I` run, by kernel and grid; rates by shape arithmetic"""
+    import collections
+    import csv
+    import glob
+    import re
+    M, k = PCA_SHAPES[args.pca_shape]
+    P = 3 * 256 * 256 * 4
+    acc = collections.defaultdict(list)
+    for f in glob.glob(f"{args.pca_trace}/**/*kernel_trace.csv", recursive=True):
+        for r in csv.DictReader(open(f)):
+            name = re.sub(r"\(.*", "", r["Kernel_Name"].replace("(anonymous namespace)::", "")).replace("void dpsx::", "")
+            if re.search(r"k_pca|k_repulse|k_step_update", name):
+                acc[name].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, v in sorted(acc.items()):
+        v = np.array(v)
+        note = ""
+        if "k_pca_project" in name:
+            note = f"  {M * (k + PCA_Q) * P / v.mean() / 1e3:.0f} GB/s ((K + q) D 4 bytes per image)"
+        elif "k_step_update" in name:
+            note = f"  {4 * P * M * k / v.mean() / 1e3:.0f} GB/s (4 P/particle)"
+        print(f"pca 256^2 M={M} K={k:3d} q={PCA_Q} launch {name:44s} calls {v.size:4d}  avg {v.mean():9.1f} us  min {v.min():9.1f}{note}")
 
 
 def noise_draw(args):
