@@ -495,6 +495,8 @@ static int step_fwd_impl(dpsx_op *op, const float *x_t, const float *model_out, 
                                a.tail);
         break;
     case OP_PHASE:
+        // resid is the transforms' own buffer here (padded image + half spectrum, complex words): 16 bytes like a workspace
+        if (!aligned16(resid)) return DPSX_EUNSUPPORTED;
         rc = phase_step_fwd(op, a, static_cast<float *>(resid), s);      // S1 + staging + R2C + residual / cotangent
         break;
     default: return DPSX_EUNSUPPORTED;
@@ -556,6 +558,7 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     const Coefs k = to_coefs(coefs_host);
     const int64_t chw = c * h * w;
     const int parts = step_parts(op, c, h, w);
+    if (op->kind == OP_PHASE && !aligned16(resid)) return DPSX_EUNSUPPORTED;       // as in the forward half
     if (op->kind == OP_IDENT || op->kind == OP_PHASE) {
         // (the hand-written spectral phase step finalises the norm in its backward launch's prologue)
         if (!norm && !(op->kind == OP_PHASE && phase_norm_in_bwd(op))) {     // no fused prologue: finalise with the small kernel
@@ -573,7 +576,7 @@ int dpsx_step_bwd_extra_f32(dpsx_op *op, const void *resid, const float *norm, f
     case OP_RESIZE: return resize_step_bwd(op, b, s);
     case OP_MASK:
         if (!x0_hat || !y || !rows_ok(y_n, n)) return DPSX_EINVAL;
-        if (!mask_fused_ok(op, c, h, w, {x0_hat, y, g_model_out}) || !aligned4(inside))
+        if (!mask_fused_ok(op, c, h, w, {x0_hat, y, g_model_out, g_x0_extra}) || !aligned4(inside))
             return DPSX_EUNSUPPORTED;
         return mask_step_bwd(op, b, s);
     case OP_IDENT:
@@ -676,7 +679,7 @@ int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float 
     if (!(data_range >= 0.0f) || !std::isfinite(data_range)) return DPSX_EINVAL;           // NaN included
     if (ssim && (h < 11 || w < 11)) return DPSX_EINVAL;
     if (n > 65535 || !metrics_shape_ok(c, h, w)) return DPSX_EUNSUPPORTED;
-    if (workspace_bytes < metrics_workspace_bytes(n, m, c, h, w)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < metrics_workspace_bytes(n, m, c, h, w) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return image_metrics(x, label, m, data_range, mse, psnr, ssim, n, c, h, w, workspace, (hipStream_t)stream);
 }
 
@@ -700,7 +703,7 @@ int dpsx_pairwise_sqdist_f32(const float *x, float *d2, float *info, int64_t n, 
     if (!x || !d2 || !workspace) return DPSX_EINVAL;
     const int rc = repulse_shape(n, chw, segments);
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return repulse(false, 0.0f, 0.0f, x, nullptr, d2, nullptr, info, nullptr, n, chw, segments, workspace,
                    (hipStream_t)stream);
 }
@@ -716,7 +719,7 @@ int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float
     const char *xb = reinterpret_cast<const char *>(x), *ob = reinterpret_cast<const char *>(out);
     const int64_t bytes = n * chw * (int64_t)sizeof(float);
     if (xb < ob + bytes && ob < xb + bytes) return DPSX_EINVAL;       // every particle reads all K: out must not overlap x
-    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return repulse(true, c, bandwidth, x, out, d2, w, info, applied, n, chw, segments, workspace, (hipStream_t)stream);
 }
 
@@ -742,7 +745,7 @@ int dpsx_ensemble_ex_f32(const float *x, const float *y, const float *neg_log_w,
     if (count0 < 0 || (neg_log_w && count0 > 0) || (curve && !y)) return DPSX_EINVAL;
     const int rc = ensemble_shape(n, d, images);
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < ensemble_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < ensemble_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return ensemble(x, y, neg_log_w, count0, mean, var, mean_lo, var_lo, curve, info, n, d, images, workspace,
                     (hipStream_t)stream);
 }
@@ -779,7 +782,7 @@ int dpsx_quantiles_f32(const float *x, const float *y, const double *probs, int6
         if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return DPSX_EINVAL;       // NaN fails both
     const int rc = quantiles_shape(n, d, images);
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < quantiles_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < quantiles_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return quantiles(x, y, probs, q, quant, hist, info, n, d, images, workspace, (hipStream_t)stream);
 }
 
@@ -804,7 +807,7 @@ int dpsx_pca_f32(const float *x, int64_t q, float *dirs, float *evals, float *co
     if (q < 1 || q > kPcaMaxQ) return DPSX_EINVAL;
     const int rc = pca_shape(n, d, images);
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < pca_workspace_bytes(n, d, images)) return DPSX_EWORKSPACE;
+    if (workspace_bytes < pca_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return pca(x, q, dirs, evals, coords, info, d2, n, d, images, workspace, (hipStream_t)stream);
 }
 

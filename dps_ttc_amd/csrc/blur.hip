@@ -1518,8 +1518,9 @@ static int launch_taps_fwd(const BlurOp &op, BlurArgs a, bool vec, hipStream_t s
 
 int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h, int64_t w)
 {
-    // the padded-domain buffer of the two-launch adjoint; the separable 16-byte path does not need it
-    if (op->kind == OP_SEP && w % 4 == 0 && (h * w) % 4 == 0) return 0;
+    // the padded-domain buffer of the two-launch adjoint.  The size query knows no pointer, so it covers every placement:
+    // the separable 16-byte path does not touch the buffer, but one buffer off the 16-byte grid (blur_vec) sends the same
+    // shape through launch_taps_adj, which does
     const int64_t r4 = op->blur->t.radius4;
     return ((planes * (h + 2 * r4) * (w + 2 * r4) * 4 + 255) / 256) * 256;
 }

@@ -20,6 +20,31 @@
  *   - a measurement `y` is [y_n, ...] with y_n dividing n: particle p reads row p / (n / y_n).  y_n = 1
  *     broadcasts one measurement, y_n = n gives one per particle, and y_n = M serves a multi-image batch of
  *     M images x n / M particles in image-major order (particles [m K, (m + 1) K) belong to image m).
+ *
+ * Buffer placement.  An fp32 (or int32) buffer needs 4-byte alignment, an int64 buffer 8, the byte gate `inside` and the
+ * other uint8 buffers none; a workspace needs 16.  Every launcher runs its 16-byte (float4) form where the size allows it
+ * and every buffer of the call is 16-byte aligned (`inside`: 4), else a scalar form: results agree within the bounds
+ * stated per entry point -- bit for bit where the entry says so or computes each output element on its own (S1, the
+ * normals, the updates' x_next, gather / replicate, selects and resampling ids); a sum whose lanes own float4 units adds
+ * its terms in another order than the scalar form -- and no call writes outside the buffers as sized here, whichever form
+ * runs.  The exceptions, each returned before anything is launched or written:
+ *   - DPSX_EWORKSPACE: a workspace off the 16-byte grid or shorter than its query, from every call that uses one
+ *     (dpsx_op_forward_f32 uses it for phase retrieval only, dpsx_op_adjoint_f32 for the blurs and phase retrieval; the
+ *     other operators ignore the two arguments there).  A NULL workspace is the same code from the operator, CG and
+ *     residual-norm entries and DPSX_EINVAL from the analysis entries, as each of them states.
+ *     dpsx_residual_norm_f32 has no query: its workspace holds min(256, max(1, ceil(m / 4096))) fp32 partial sums per
+ *     particle (n * 256 * 4 bytes always suffice) and needs 4-byte alignment only.
+ *   - DPSX_EUNSUPPORTED from the fused step of an inpainting operator (16-byte form only): dpsx_step_fwd_f32 / _rng with
+ *     x_t, model_out, noise, y, x0_hat or sample off the 16-byte grid or `inside` off the 4-byte grid; dpsx_step_bwd_f32 /
+ *     _extra with x0_hat, y, g_model_out, g_x0_extra or `inside` so.
+ *   - DPSX_EUNSUPPORTED from the fused step of a phase-retrieval operator: `resid` off the 16-byte grid (it is the
+ *     transforms' own buffer: complex words); at the hand-written 384-point geometry also x_t, model_out, noise, x0_hat,
+ *     sample (forward) or g_model_out, g_x0_extra (backward) off the 16-byte grid, or `inside` off the 4-byte grid.
+ *   - DPSX_EUNSUPPORTED from dpsx_step_fwd_rng_f32 of a blur or resize operator with a buffer off the grid: the draw
+ *     inside the launch exists in the 16-byte form (see dpsx_step_draws_in_kernel); the caller fills a noise buffer.
+ *   - DPSX_EUNSUPPORTED from dpsx_pack_champion_f32 (particles, out) and dpsx_select_champion_f32 (table, dst).
+ * The size queries (dpsx_op_workspace_bytes, dpsx_step_resid_bytes, dpsx_cg_workspace_bytes, dpsx_*_workspace_bytes)
+ * know no pointer: a workspace of the queried size serves every placement of the other buffers.
  */
 #ifndef DPSX_H
 #define DPSX_H
@@ -39,7 +64,7 @@ enum {
     DPSX_EUNSUPPORTED = -2,
     DPSX_ELAUNCH = -3,    /* HIP reported a launch/runtime error */
     DPSX_ENOMEM = -4,
-    DPSX_EWORKSPACE = -5  /* caller workspace too small */
+    DPSX_EWORKSPACE = -5  /* caller workspace too small or off the 16-byte grid */
 };
 
 int dpsx_abi_version(void);
