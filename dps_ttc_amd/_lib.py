@@ -114,6 +114,7 @@ SIGNATURES = {
     "dpsx_smc_accum_f32": (c_int, [_f, _f, _f, _f, c_int, _p, _i64, _i64, c_float, c_int, c_float, _p]),
     "dpsx_step_update_dsg_f32": (c_int, [_f, _f, _f, _f, _f, POINTER(RngRec), c_float, _f, _f, _i64, _i64, POINTER(Coefs),
                                          _p]),
+    "dpsx_step_update_ms_f32": (c_int, [_f, _f, _f, _f, _f, c_float, _f, _i64, _i64, POINTER(Coefs), _p]),
     "dpsx_metrics_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
     "dpsx_image_metrics_f32": (c_int, [_f, _f, _i64, c_float, _f, _f, _f, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_repulse_workspace_bytes": (_i64, [_i64, _i64, _i64]),

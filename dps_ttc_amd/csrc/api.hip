@@ -661,6 +661,19 @@ int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, cons
                            stats, n, chw, to_coefs(coefs_host), (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ the multistep update (dpmpp.hip)
+int dpsx_step_update_ms_f32(const float *sample, const float *g_model_out, const float *g_unet, const float *x0_cur,
+                            const float *x0_prev, float c, float *x_next, int64_t n, int64_t chw,
+                            const dpsx_coefs *coefs_host, void *stream)
+{
+    if (!sample || !g_model_out || !x_next || !coefs_host || n < 0 || chw < 1) return DPSX_EINVAL;
+    if (coefs_host->b == 0.0f || !std::isfinite(c)) return DPSX_EINVAL;
+    if (c != 0.0f && (!x0_cur || !x0_prev)) return DPSX_EINVAL;
+    if (n > 65535) return DPSX_EUNSUPPORTED;                       // particles are the grid's y dimension
+    return step_update_ms(sample, g_model_out, g_unet, x0_cur, x0_prev, c, x_next, n, chw, to_coefs(coefs_host),
+                          (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------ image metrics (metrics.hip)
 int64_t dpsx_metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w)
 {

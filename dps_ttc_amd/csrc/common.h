@@ -718,6 +718,11 @@ int step_update_dsg(const float *sample, const float *g_mo, const float *g_unet,
                     bool use_rng, const RngK &r, float rate, float *x_next, float *stats, int64_t n, int64_t chw,
                     const Coefs &k, hipStream_t s);
 
+// dpmpp.hip: K3 plus the multistep term c (x0_cur - x0_prev), one launch (the expression is stated in dpmpp.hip's header);
+// c == 0: neither history is read (both may be null) and x_next has step_update's bits
+int step_update_ms(const float *sample, const float *g_mo, const float *g_unet, const float *x0_cur, const float *x0_prev,
+                   float c, float *x_next, int64_t n, int64_t chw, const Coefs &k, hipStream_t s);
+
 // metrics.hip: per-particle mse / psnr / ssim against the particle's label row (the definition is stated in include/dpsx.h);
 // the caller checked the arguments and the workspace size
 bool metrics_shape_ok(int64_t c, int64_t h, int64_t w);      // the index arithmetic fits

@@ -1,4 +1,4 @@
-// The per-particle slotted pass of cg.hip, smc.hip, dsg.hip and metrics.hip (repulse.hip, whose blocks own particle tiles, takes
+// The per-particle slotted pass of cg.hip, smc.hip, dsg.hip, dpmpp.hip and metrics.hip (repulse.hip, whose blocks own particle tiles, takes
 // the units, the loads, the block range and the host rules from here; no other translation unit includes this header).
 //
 // Grid (slots, n): block (q, p) owns one contiguous range of particle p's work items and leaves its partial sums in slot
@@ -74,7 +74,7 @@ template <class F> int dispatch(bool vec, bool use_rng, F &&f)
     return dispatch(vec, [&](auto V) { return dispatch(use_rng, [&](auto R) { return f(V, R); }); });
 }
 
-// ------------------------------------------------------------------ the update streams (smc.hip, dsg.hip)
+// ------------------------------------------------------------------ the update streams (smc.hip, dsg.hip, dpmpp.hip)
 // K3's inputs as the launches in K3's place read them.  Per element e of particle p, every operation one fp32 rounding:
 //     s_e  = ratio g_eps_e + g_unet_e                    g_unet absent: + 0.0f
 //     sd_e = __expf(0.5f post_logvar(v_e))               DDPM record (S1's device functions); DDIM record: sd_e = min_log

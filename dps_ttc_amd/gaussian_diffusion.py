@@ -56,14 +56,22 @@ def get_sampler(name: str):
 
 
 def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_type, dynamic_threshold,
-                   clip_denoised, rescale_timesteps, timestep_respacing="", eta=None):
+                   clip_denoised, rescale_timesteps, timestep_respacing="", eta=None, solver_order=None):
     """eta (not in the reference, whose DDIM loops never pass it): the DDIM samplers' `eta` attribute -- sigma's scale,
-    0 the deterministic sampler, 1 the DDPM-like one the `dsg` method wants; a sampler without that attribute refuses it"""
+    0 the deterministic sampler, 1 the DDPM-like one the `dsg` method wants; a sampler without that attribute refuses it.
+    solver_order (not in the reference): the DDIM samplers' `solver_order` attribute, 1 (the DDIM rule) or 2 (the
+    DPM-Solver++(2M) multistep update, eta 0 or 1 only); any other sampler refuses it.
+    timestep_respacing "logsnr{n}" (not in the reference): at most n timesteps uniform in log-SNR (logsnr_timesteps);
+    every other spec is space_timesteps'."""
     cls = get_sampler(name=sampler)
     betas = get_named_beta_schedule(noise_schedule, steps)
     if not timestep_respacing:
         timestep_respacing = [steps]
-    smp = cls(use_timesteps=space_timesteps(steps, timestep_respacing), betas=betas,
+    if isinstance(timestep_respacing, str) and timestep_respacing.startswith("logsnr"):
+        use_timesteps = logsnr_timesteps(betas, int(timestep_respacing[len("logsnr"):]))
+    else:
+        use_timesteps = space_timesteps(steps, timestep_respacing)
+    smp = cls(use_timesteps=use_timesteps, betas=betas,
               model_mean_type=model_mean_type, model_var_type=model_var_type,
               dynamic_threshold=dynamic_threshold, clip_denoised=clip_denoised,
               rescale_timesteps=rescale_timesteps)
@@ -73,6 +81,11 @@ def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_ty
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1] (got {eta!r})")
         smp.eta = float(eta)
+    if solver_order is not None:
+        if not isinstance(smp, DDIM):
+            raise ValueError(f"solver_order is an option of the ddim samplers (got sampler {sampler!r})")
+        smp.solver_order = solver_order
+        smp._check_solver_order()
     return smp
 
 
@@ -117,6 +130,22 @@ def space_timesteps(num_timesteps, section_counts):
             pos += stride
         start += size
     return set(kept)
+
+
+def logsnr_timesteps(betas, n):
+    """The base timesteps kept by "logsnr{n}": with lambda_t = 0.5 ln(abar_t / (1 - abar_t)) over the base schedule, n
+    values uniform from lambda_0 to lambda_{T-1} inclusive, each replaced by the base index with the nearest lambda (a
+    tie: the lower index), plus indices 0 and T - 1, duplicates dropped -- so AT MOST n timesteps (where the base
+    schedule is coarse in lambda, neighbouring values share an index).  n < 2 raises ValueError."""
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"logsnr{n}: a log-SNR spacing needs at least 2 timesteps")
+    abar = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64))
+    lam = 0.5 * np.log(abar / (1.0 - abar))
+    kept = {0, len(lam) - 1}
+    for v in np.linspace(lam[0], lam[-1], n):
+        kept.add(int(np.argmin(np.abs(lam - v))))          # argmin: the first of equal minima
+    return kept
 
 
 # ------------------------------------------------------------------ base class
@@ -217,6 +246,63 @@ class GaussianDiffusion:
         self.repulsion_bandwidth = None
         self.repulsion_stop = 0.0
         self._repulse_out = None
+        #: "unit" (the reference: every kept step shifts by scale * gradient) or "span": the fused step's scale is
+        #: multiplied by the base steps the kept step covers (timestep_map[i] - timestep_map[i - 1]; timestep_map[0] + 1
+        #: at i = 0), so a respaced loop guides as much in total as the full schedule with the same scale.  A heuristic:
+        #: the quality it gives is not pinned by any test.  Fused plans only; dsg has no scale and refuses it.
+        self.guidance_gain = "unit"
+
+    #: the order of the update (DDIM.solver_order); every other sampler steps at first order
+    solver_order = 1
+
+    def _step_span(self, idx):
+        """the base timesteps the kept step at loop index idx covers"""
+        tm = getattr(self, "timestep_map", None)
+        if tm is None:
+            return 1
+        return int(tm[idx] - tm[idx - 1]) if idx > 0 else int(tm[0]) + 1
+
+    def _check_solver(self, measurement_cond_fn, x_start, project, plan=False):
+        """solver_order = 2 and guidance_gain = "span" run only where every step of the loop is the fused step with K3's
+        update: anything else is refused here, from the host's knowledge alone, before the first step (and before the model
+        or the device is asked for anything).  plan: the loop's fusion plan once it has one (None: refused whatever the
+        reason), as in _check_dsg."""
+        gain = self.guidance_gain
+        if gain not in ("unit", "span"):
+            raise ValueError(f"guidance_gain must be 'unit' or 'span' (got {gain!r})")
+        order = self._check_solver_order()
+        if gain == "unit" and order == 1:
+            return
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        what = "solver_order = 2" if order == 2 else "guidance_gain = 'span'"
+        why = None
+        if isinstance(method, ConjugateGradientConsistency):
+            why = "the cg step has no fused plan (it replaces x0_hat by x0_hat + d and has its own update)"
+        elif isinstance(method, SphericalGaussianGuidance):
+            why = "dsg puts x_next on a sphere: it has no step size to scale and no update to add a history term to"
+        else:
+            why = {"sampler": "no fused plan: it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised "
+                              "posterior (a fixed-variance model has no fused step)",
+                   "method": "no fused plan: it needs a ps-type conditioning method (per-op methods have no fused step) with "
+                             f"a Gaussian noiser (got {getattr(getattr(method, 'noiser', None), '__name__', None)!r})",
+                   "mask": "no fused plan: inpainting needs its mask bound to the conditioning function",
+                   }.get(self._no_plan_reason(method, kw))
+        if why is None and method.operator.name == 'inpainting' and not kernels.OpHandle._mask_fuses(*x_start.shape[-2:]):
+            why = (f"no fused plan: the fused inpainting step exists on the float4 grid only, H * W a multiple of 4 (got "
+                   f"{x_start.shape[-2]} x {x_start.shape[-1]})")
+        if why is None and plan is None:
+            why = f"no fused plan: {type(method.operator).__name__} has no fused step at {tuple(x_start.shape)}"
+        if why is None and order == 2 and project:
+            why = "a DiffStateGrad projection (project=True) takes the per-op path on its steps, which keeps no x0_hat history"
+        if why is None and order == 2 and getattr(self, "global_resample", False):
+            why = "with global (multi-rank) resampling the history would have to travel between ranks with the particles"
+        if why is not None:
+            raise NotImplementedError(f"{what} is not supported here: {why}")
+
+    def _check_solver_order(self):
+        if self.solver_order != 1:
+            raise ValueError(f"solver_order is an option of the ddim samplers (sampler {type(self).__name__})")
+        return 1
 
     def _check_repulsion(self, n=None, measurement=None, n_images=False):
         """The repulsion options, checked from the host's knowledge alone before the first step (and before the device is
@@ -494,13 +580,17 @@ class GaussianDiffusion:
 
     def _step_spec(self, idx, method, cond_kw, loop_kw):
         """the method's fused_spec at loop index idx.  loop_kw: see _loop_kw"""
-        return method.fused_spec(**self._loop_kw(idx, loop_kw), **cond_kw)
+        spec = method.fused_spec(**self._loop_kw(idx, loop_kw), **cond_kw)
+        if self.guidance_gain == "span" and spec is not None and "scale" in spec:
+            spec = dict(spec, scale=spec["scale"] * self._step_span(idx))
+        return spec
 
     def _fused_step(self, model, x_prev, idx, y, spec, handle, buf, stream, noise, rng, want_x0, corr_state=None):
         """The fused DPS step of one chain of particles -- model call, K1, [semantic term], K2, model VJP, K3 -- on `stream`
         (None: torch's current stream).  x_prev, noise, y and rng are the chain's own (already sliced); -> (x_next, the
         semantic term's distance or None).  K3 is kernels.step_update, step_update_dsg where the spec says "dsg" (refused
-        with corr_state: _check_dsg), or step_update_corr with corr_state."""
+        with corr_state: _check_dsg), step_update_ms with solver_order = 2 (the ddim samplers; K1 then stores x0_hat on
+        every step beside the previous step's), or step_update_corr with corr_state."""
         x_prev = x_prev.detach().requires_grad_()
         with torch.enable_grad():
             model_out = self._call_model(model, x_prev, idx)
@@ -510,10 +600,13 @@ class GaussianDiffusion:
         coefs = self.sample_coefs(idx)
         if noise is None and rng is None:
             noise = self._randn(x_prev)
+        multistep = self.solver_order == 2
+        if multistep:                     # K1 writes this step's x0_hat beside the previous step's (no copy)
+            buf.advance_x0()
         # x0_hat is consumed inside K1 (A(x0_hat), the clamp gate): the image itself is written out only when something
-        # reads it afterwards -- the semantic term's embedder, a progress snapshot (want_x0)
+        # reads it afterwards -- the semantic term's embedder, a progress snapshot (want_x0), the multistep update
         kernels.step_fwd(handle, buf, kernels.f32c(x_prev.detach(), "x_t"), mo, noise, y, coefs,
-                         want_x0=want_x0 or "semantic" in spec, stream=stream, rng=rng)
+                         want_x0=want_x0 or multistep or "semantic" in spec, stream=stream, rng=rng)
         g_sem = sem = None
         if "semantic" in spec:            # embedder forward + VJP on x0_hat (torch), between the two HIP halves
             g_sem, sem = spec["semantic"](buf.x0_hat)
@@ -525,6 +618,8 @@ class GaussianDiffusion:
         if "dsg" in spec:                 # the point on the sphere in K3's place
             x_next, _ = kernels.step_update_dsg(buf, g_unet, coefs, mo, spec["dsg"], noise=noise, rng=rng,
                                                 stats=buf.dsg_stats(), stream=stream)
+        elif multistep:                   # K3 + c (x0_hat - the previous step's), c = 0 on the first and the last step
+            x_next = kernels.step_update_ms(buf, g_unet, coefs, self.solver_coef(idx), stream=stream)
         elif corr_state is None:
             x_next = kernels.step_update(buf, g_unet, coefs, stream=stream)
         else:
@@ -701,10 +796,12 @@ class GaussianDiffusion:
         img = x_start.detach()
         n = img.shape[0]
         self._check_dsg(measurement_cond_fn, img)
+        self._check_solver(measurement_cond_fn, img, project)
         self._check_repulsion(n, measurement, n_images)
         kernels.require_cuda(img, "x_start")
         plan = self._fusion_plan(measurement_cond_fn, img)
         self._check_dsg(measurement_cond_fn, img, plan)
+        self._check_solver(measurement_cond_fn, img, project, plan)
         cg = self._cg_plan(measurement_cond_fn)
         method, _ = self._unwrap_cond_fn(measurement_cond_fn)
         if n_images is False:
@@ -866,6 +963,40 @@ class DDIM(SpacedDiffusion):
         # one-rank RCCL group: 234 us of host time per step instead of 29)
         for t in range(self.num_timesteps):
             self.sample_coefs(t)
+        self._solver_c = {0.0: self._solver_table(1.0), 1.0: self._solver_table(2.0)}
+
+    #: 1: the DDIM rule; 2: DPM-Solver++(2M) (Lu et al. 2022) -- the DDIM step (its first-order form: eta = 0 the ODE, eta = 1
+    #: the SDE) plus solver_coef(idx) * (x0_hat - the previous step's x0_hat), one launch in K3's place
+    #: (kernels.step_update_ms).  Order 2 runs under a fused plan only, with eta 0 or 1; the loops refuse the rest.
+    solver_order = 1
+
+    def _solver_table(self, m):
+        """c_i of the 2M step for every loop index, float64 rounded to fp32 once: with lambda = 0.5 ln(abar / (1 - abar)),
+        h_i = lambda_{i-1} - lambda_i (the step from i lands on abar_{i-1}) and r_i = h_{i+1} / h_i,
+            c_i = sqrt(abar_{i-1}) (1 - e^{-m h_i}) / (2 r_i)        m = 1: eta = 0 (ODE), m = 2: eta = 1 (SDE)
+        and c = 0 at i = n - 1 (no history) and i = 0 (the step onto the clean image is first order)"""
+        n, abar = self.num_timesteps, self.alphas_cumprod
+        lam = 0.5 * np.log(abar / (1.0 - abar))
+        c = np.zeros(n, dtype=np.float64)
+        for i in range(1, n - 1):
+            h, h_prev = lam[i - 1] - lam[i], lam[i] - lam[i + 1]
+            c[i] = np.sqrt(abar[i - 1]) * (1.0 - np.exp(-m * h)) / (2.0 * (h_prev / h))
+        return [float(np.float32(v)) for v in c]
+
+    def _check_solver_order(self):
+        order = self.solver_order
+        if isinstance(order, bool) or order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2 (got {order!r})")
+        if order == 2 and float(self.eta) not in (0.0, 1.0):
+            raise ValueError(f"solver_order = 2 is defined for eta = 0 (the ODE form) and eta = 1 (the SDE form), got eta = "
+                             f"{self.eta}")
+        return int(order)
+
+    def solver_coef(self, idx):
+        """the host scalar c of the multistep update at loop index idx (fp32-rounded; 0 at order 1)"""
+        if self._check_solver_order() == 1:
+            return 0.0
+        return self._solver_c[float(self.eta)][idx]
 
     def sample_coefs(self, idx, eta=None):
         eta = self.eta if eta is None else eta
@@ -1109,6 +1240,7 @@ class TTC_DDIM(DDIM):
     resample_every = 10
     _resample_segments = 1
     _resample_opts = None
+    _drawn_ids = None
 
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root, **kwargs):
         self._check_metric_trace(base_loop=False)
@@ -1143,6 +1275,11 @@ class TTC_DDIM(DDIM):
             img = self._repulse(img, idx, segments)
             if idx % resample_every_steps == 0:
                 img, distance = self._resample(img, distance, resample_scale)
+                ids = self._drawn_ids
+                if self.solver_order == 2 and ids is not None:
+                    # the x0_hat the next step reads as its history moves with the particles: this resampling's ids
+                    buf = self._bufs[1]
+                    buf.set_x0_history(kernels.gather(buf.x0_hat, ids, validate=False))
         return img.clone(), distance.clone()
 
     @staticmethod
@@ -1158,28 +1295,34 @@ class TTC_DDIM(DDIM):
         return every
 
     def _resample(self, img, distance, resample_scale):
+        """_resample_block -> (particles, distances); the ids THIS call drew (None where it drew none: a skipped
+        resampling leaves last_resample_ids as it was) are handed back in `_drawn_ids`"""
+        img, distance, self._drawn_ids = self._resample_block(img, distance, resample_scale)
+        return img, distance
+
+    def _resample_block(self, img, distance, resample_scale):
         """the resampling block (:685-698): w = exp(-d / 100), multinomial with replacement, skipped when all
         weights are equal.  By default the draw is torch.multinomial (RNG parity) and the particle gather is HIP; with
         resample_draw = "device" the draw and both gathers are one launch (_device_resample), and with global_resample
-        the ranks' exchange draws."""
+        the ranks' exchange draws.  -> (particles, distances, the ids this call drew or None where it drew none)"""
         n = len(distance)
         if self.global_resample:
             from . import distributed as dd
             img, distance, ids = dd.global_resample(img, distance, resample_scale, self.resample_generator,
                                                      fetch=self.resample_fetch)
             self.last_resample_ids = ids if ids is not None else self.last_resample_ids
-            return img, distance
+            return img, distance, ids
         if self.resample_draw == "device":
             # one launch: per-image draw + both gathers.  img / distance are views of the persistent step buffers on the
             # fused route (the launch's src / d), the results are fresh tensors
             return self._device_resample(n, distance, self._resample_segments, 1.0 / resample_scale, self._resample_opts,
-                                         src=img)[:2]
+                                         src=img)[:3]
         if n <= 1:
-            return img, distance
+            return img, distance, None
         weights = torch.exp(-distance / resample_scale)
         if self.rng_parity:                      # replay of the reference's host RNG stream (tests)
             if weights.max() == weights.min():
-                return img, distance
+                return img, distance, None
             ids = torch.multinomial(weights.cpu(), n, replacement=True).to(img.device)
         else:
             # no host read: when all weights are equal the draw is replaced by the identity on the device
@@ -1188,7 +1331,8 @@ class TTC_DDIM(DDIM):
             drawn = torch.multinomial(torch.where(flat, torch.ones_like(weights), weights), n, replacement=True)
             ids = torch.where(flat, torch.arange(n, device=img.device), drawn)
         self.last_resample_ids = ids
-        return kernels.gather(img, ids, validate=False), kernels.gather(distance.reshape(n, 1), ids, validate=False).reshape(n)
+        return (kernels.gather(img, ids, validate=False),
+                kernels.gather(distance.reshape(n, 1), ids, validate=False).reshape(n), ids)
 
 
 @register_sampler(name='smc_ddpm', extension=True)

@@ -743,6 +743,43 @@ class StepBuffers:
         self.flip = 0
         self._noise = None
         self._dsg_stats = None
+        # the multistep update's history (step_update_ms): the second x0_hat buffer exists from the first advance_x0() on
+        self._parent, self._offset = parent, offset
+        self._x0_pair, self._x0_at = None, 0
+        self._x0_moved = None
+        self.x0_prev = None
+
+    def _x0_buffers(self):
+        """the two buffers x0_hat alternates between (the second one allocated on first use; a group's are its slices of
+        the parent's pair)"""
+        if self._x0_pair is None:
+            if self._parent is None:
+                self._x0_pair = [self.x0_hat, torch.empty_like(self.x0_hat)]
+            else:
+                sl = slice(self._offset, self._offset + self.shape[0])
+                self._x0_pair = [v[sl] for v in self._parent._x0_buffers()]
+        return self._x0_pair
+
+    def advance_x0(self):
+        """A step that keeps the previous step's x0_hat as history starts here: x0_hat becomes the other buffer of the
+        pair (K1 writes the new x0_hat over the one no longer needed, nothing is copied) and x0_prev what it was -- or the
+        tensor set_x0_history() put in its place.  Everything that reads buf.x0_hat during or after the step reads the
+        current one; a parent's x0_hat follows its groups (which advance together)."""
+        pair = self._x0_buffers()
+        self.x0_prev = pair[self._x0_at] if self._x0_moved is None else self._x0_moved
+        self._x0_moved = None
+        self._x0_at ^= 1
+        self.x0_hat = pair[self._x0_at]
+        if self._parent is not None:
+            self._parent.x0_hat = self._parent._x0_buffers()[self._x0_at]
+        return self.x0_prev
+
+    def set_x0_history(self, x0):
+        """the next advance_x0() hands out `x0` [n, c, h, w] as x0_prev instead of the current x0_hat (a resampling moved
+        the particles: the history moves with them)"""
+        if tuple(x0.shape) != tuple(self.shape):
+            raise ValueError(f"history of shape {tuple(x0.shape)} for step buffers of shape {self.shape}")
+        self._x0_moved = f32c(x0, "x0 history")
 
     def dsg_stats(self):
         """[n, corr_slots, 4] partial sums of step_update_dsg, the buffers' own (allocated on first use)"""
@@ -866,6 +903,24 @@ def step_update(buf, g_unet, coefs, stream=None):
     buf.flip ^= 1
     check(lib().dpsx_step_update_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), ptr(out), n, c * h * w,
                                      byref(coefs), _stream_arg(stream, buf.sample)), "dpsx_step_update_f32")
+    return out
+
+
+def step_update_ms(buf, g_unet, coefs, c, stream=None):
+    """step_update's twin for a multistep (DPM-Solver++ 2M) step, one launch (dpsx_step_update_ms_f32):
+    x_next = sample - s + c (buf.x0_hat - buf.x0_prev), c a host scalar (DDIM.solver_coef).  c == 0: the histories are
+    not read (buf.x0_prev may be None) and x_next has step_update's bits.  buf.x0_prev is what buf.advance_x0() left at
+    the start of the step; x_next flips as in step_update."""
+    n, ch, h, w = buf.shape
+    c = float(c)
+    if c != 0.0 and buf.x0_prev is None:
+        raise ValueError("step_update_ms with c != 0 needs the previous step's x0_hat (buf.advance_x0() before K1)")
+    hist = (ptr(buf.x0_hat), ptr(buf.x0_prev)) if c != 0.0 else (None, None)
+    out = buf.x_next[buf.flip]
+    buf.flip ^= 1
+    check(lib().dpsx_step_update_ms_f32(ptr(buf.sample), ptr(buf.g_model_out), ptr(g_unet), *hist, c, ptr(out), n,
+                                        ch * h * w, byref(coefs), _stream_arg(stream, buf.sample)),
+          "dpsx_step_update_ms_f32")
     return out
 
 

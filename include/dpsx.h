@@ -526,6 +526,30 @@ int dpsx_step_update_dsg_f32(const float *sample, const float *g_model_out, cons
                              float guidance_rate, float *x_next, float *stats /* [n, slots, 4] */,
                              int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream);
 
+/* ---- the multistep update of DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of
+ * Diffusion Probabilistic Models"; not in the reference): K3's place on a DDIM step of second order.  The first-order
+ * DPM-Solver++ step is the DDIM record K1 already runs (eta = 0: the ODE form, eta = 1: the SDE form), so the 2M step is
+ * dpsx_step_update_f32 plus one term in the difference of this step's and the previous step's x0_hat, with a host scalar
+ * c (the sampler's table: c_i = sqrt(abar_{i-1}) (1 - e^{-h_i}) / (2 r_i) for eta = 0, (1 - e^{-2 h_i}) for eta = 1).
+ * Per element, every operation one fp32 rounding:
+ *   s      = (-a/b) g_eps + g_unet                        (dpsx_step_update_f32's expression; g_unet NULL: + 0.0f)
+ *   u      = sample - s
+ *   x_next = c == 0 ? u : u + c (x0_cur - x0_prev)
+ * x0_cur, x0_prev [n, chw].  c == 0 (the step without history, the step onto the clean image): neither history pointer is
+ * read, both may be NULL, and x_next has dpsx_step_update_f32's bits, -0.0 and NaN payloads included (the call runs that
+ * entry point's launch).  Nothing crosses
+ * particles or elements: a non-finite input reaches its own element of x_next only.  x_next must not overlap an input.
+ * The float4 form runs where chw % 4 == 0 and every buffer the call reads or writes is 16-byte aligned (the histories
+ * count only when c != 0), else the scalar form of the same body: the same bits.  With c != 0 sample, the gradients and
+ * x0_prev are read for the last time of their step (non-temporal loads); x0_cur is the next step's x0_prev.
+ * Bytes per particle of P = 4 chw: 5 P read (3 P at c = 0) and 1 P written, against dpsx_step_update_f32's 3 P + 1 P.
+ * DPSX_EINVAL: a null sample / g_model_out / x_next / coefs_host, b = 0, c not finite, c != 0 with a null history pointer,
+ * n < 0 or chw < 1; DPSX_EUNSUPPORTED: n > 65535.  All of them return before anything is launched.
+ * One launch on `stream`: no partials, no atomics, no allocation, no host read (graph-capturable). */
+int dpsx_step_update_ms_f32(const float *sample, const float *g_model_out, const float *g_unet /* nullable */,
+                            const float *x0_cur, const float *x0_prev, float c,
+                            float *x_next, int64_t n, int64_t chw, const dpsx_coefs *coefs_host, void *stream);
+
 /* ---- per-particle reconstruction metrics against the label, on the device: what compute_metrics.py:77-90 (PSNR with
  * torchmetrics' default range) and the per-path loop feeding best_of_n_simple.py:20-40 compute on the host, plus SSIM
  * (Wang et al. 2004, the convention skimage and torchmetrics share).  Evaluation only: nothing here steers a sampler.

@@ -134,6 +134,12 @@ def parse_args(argv=None):
     p.add_argument('--dsg_guidance_rate', type=float, default=None,
                    help='dsg: overrides the task config\'s guidance_rate in [0, 1] (0: the drawn noise direction, 1: the '
                         'steepest-descent direction)')
+    p.add_argument('--solver_order', type=int, default=None, choices=(1, 2),
+                   help='ddim / ttc_ddim: overrides the diffusion config\'s solver_order (1: the DDIM rule, 2: the '
+                        'DPM-Solver++(2M) multistep update; eta 0 or 1, ps-type methods, one rank for ttc_ddim)')
+    p.add_argument('--guidance_gain', type=str, default=None, choices=('unit', 'span'),
+                   help='unit: every kept step shifts by scale * gradient (the reference); span: scale is multiplied by '
+                        'the base timesteps the kept step covers (a heuristic for respaced loops; not for dsg / cg)')
     p.add_argument('--beam_width', type=int, default=1,
                    help='search_ddpm: keep this many best proposals per image and step instead of one (beam search); '
                         'must divide batch_size; one rank only')
@@ -283,6 +289,27 @@ def check_dsg(args, method_name):
                          f"{method_name})")
     if not 0.0 <= g <= 1.0:
         raise SystemExit(f"--dsg_guidance_rate must be in [0, 1] (got {g})")
+
+
+def check_solver(args, sampler_name, method_name, world=1, eta=None):
+    """--solver_order / --guidance_gain: reject what the sampling loops would refuse, before any GPU work (one-line
+    message).  eta: the diffusion config's (None: the sampler's default 0)"""
+    order, gain = args.solver_order, args.guidance_gain
+    if order is not None and sampler_name not in ('ddim', 'ttc_ddim'):
+        raise SystemExit(f"--solver_order {order} is an option of samplers ddim and ttc_ddim (the diffusion config names "
+                         f"{sampler_name})")
+    if order == 2:
+        if method_name in ('cg', 'dsg'):
+            raise SystemExit(f"--solver_order 2 is not supported with conditioning method {method_name} (it has its own "
+                             "update)")
+        if float(eta or 0.0) not in (0.0, 1.0):
+            raise SystemExit(f"--solver_order 2 needs eta 0 or 1 in the diffusion config (got {eta})")
+        if sampler_name == 'ttc_ddim' and world > 1:
+            raise SystemExit("--solver_order 2 with ttc_ddim on several ranks is not supported (the history does not "
+                             "travel between ranks)")
+    if gain == 'span' and method_name in ('cg', 'dsg'):
+        raise SystemExit(f"--guidance_gain span is not supported with conditioning method {method_name} (it has no scale "
+                         "per step)")
 
 
 def check_beam_width(args, sampler_name, world):
@@ -501,6 +528,9 @@ def main(argv=None):
         check_smc(args, sampler_name, world)
     if args.dsg_guidance_rate is not None:
         check_dsg(args, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None)
+    if args.solver_order is not None or args.guidance_gain is not None:
+        check_solver(args, sampler_name, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None,
+                     world, load_yaml(args.diffusion_config).get('eta') if args.diffusion_config else None)
     if args.beam_width != 1:
         check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
     if repulsion_flags(args) or args.path_diversity:
@@ -534,6 +564,8 @@ def main(argv=None):
     task_config = load_yaml(args.task_config)
     if args.timestep_respacing is not None:
         diffusion_config['timestep_respacing'] = args.timestep_respacing
+    if args.solver_order is not None:            # check_solver: the sampler is a ddim one
+        diffusion_config['solver_order'] = args.solver_order
     if args.seed is not None:
         torch.manual_seed(args.seed + rank)
 
@@ -568,6 +600,8 @@ def main(argv=None):
     sampler.resample_every = args.ttc_resample_every
     sampler.noise_draw = args.noise_draw
     sampler.beam_width = args.beam_width
+    if args.guidance_gain is not None:
+        sampler.guidance_gain = args.guidance_gain
     sampler.repulsion_scale, sampler.repulsion_stop = args.repulsion_scale, args.repulsion_stop
     sampler.repulsion_bandwidth = args.repulsion_bandwidth
     for flag, value in smc_flags(args):          # check_smc: the sampler is smc_ddpm

@@ -35,6 +35,11 @@ against the bytes by shape arithmetic; (b) and (c) also as a fraction of K3's ra
 in one process: (a) K3 alone (4 P), (b) step_update_corr with a noise pointer (6 P), (c) step_update_dsg with a noise pointer
 (stats 4 P + apply 6 P), (d) the same with rng= (3 P + 5 P).  Per form: the time as a multiple of K3's and the rate against
 the bytes by shape arithmetic as a fraction of K3's rate, all from the same run.
+    python tools/kbench.py --dpmpp                                                    (the DPM-Solver++(2M) update, 256^2)
+--dpmpp: K3 beside kernels.step_update_ms, N = 64 and 16, Gaussian sigma = 3, 3 x --reps repetitions alternated in one
+process: (a) K3 alone (4 P), (b) step_update_ms with c != 0 (6 P), (c) the same with c = 0 (4 P), (d) K3 + the correction as
+two torch ops, and K1 without / with the x0_hat store.  (b) and (c): the time as a multiple of K3's and the rate against the
+bytes by shape arithmetic as a fraction of K3's rate, all from the same run.
     python tools/kbench.py --metrics                                                  (per-path PSNR / SSIM, 256^2)
 --metrics: the per-path metrics of [N, 3, 256, 256] particles, N = 64 with M = 1 and M = 4 labels and N = 512 with M = 1,
 3 x --reps repetitions alternated in one process: (a) the driver's per-particle metrics.compute_psnr loop with its host
@@ -93,6 +98,7 @@ def main():
     ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
     ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
     ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
+    ap.add_argument("--dpmpp", action="store_true", help="time step_update_ms (c != 0 / c = 0 / torch ops) beside K3, and K1's x0_hat store")
     ap.add_argument("--metrics", action="store_true", help="time per-path PSNR / SSIM: host loop / torch ops / image_metrics")
     ap.add_argument("--repulse", action="store_true", help="time particle repulsion: the distances / the whole call / torch ops / K3")
     ap.add_argument("--ensemble", action="store_true", help="time the ensemble statistics: the call / torch ops / the byte floor / K3")
@@ -113,6 +119,8 @@ def main():
         return repulse_step(args)
     if args.metrics:
         return metrics_step(args)
+    if args.dpmpp:
+        return dpmpp_step(args)
     if args.dsg:
         return dsg_step(args)
     if args.smc:
@@ -452,6 +460,75 @@ def dsg_step(args):
                   f"{ts.mean() / t_k3:4.2f} x K3's time  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = "
                   f"{bps / k3:4.2f} x K3's rate", flush=True)
         del buf, st, handle, op
+
+
+def dpmpp_step(args):
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddim", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="logsnr20", eta=0.0, solver_order=2)
+    ck, c = smp.sample_coefs(10), smp.solver_coef(10)
+    P = bench.P_BYTES
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for n in (64, 16):
+        op, fkw = bench.build_operator("gaussian_blur", dev, sigma=args.sigma)
+        x_t, ring, truth, meas_noise = bench.synth_inputs(n, 2, dev, 1234)
+        yy = op.forward(truth.to(dev), **fkw).detach()
+        y = (yy + meas_noise.to(dev)[..., :yy.shape[-2], :yy.shape[-1]]).contiguous()
+        handle = op.hip_handle(x_t)
+        buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+        r0 = ring[0]
+        buf.advance_x0()
+        kernels.step_fwd(handle, buf, x_t, r0["model_out"], r0["noise"], y, ck, want_x0=True)      # a history to read
+        buf.advance_x0()
+        kernels.step_fwd(handle, buf, x_t, r0["model_out"], r0["noise"], y, ck, want_x0=True)      # sample, x0_hat
+        kernels.step_bwd(handle, buf, y, 0.3, 1, ck)
+
+        def torch_ops(i):
+            x = kernels.step_update(buf, ring[i % 2]["g_unet"], ck)
+            return x.add_(buf.x0_hat - buf.x0_prev, alpha=c)
+
+        def fwd(store):
+            return lambda i: kernels.step_fwd(handle, buf, x_t, ring[i % 2]["model_out"], ring[i % 2]["noise"], y, ck,
+                                              want_x0=store)
+
+        forms = {"a K3": lambda i: kernels.step_update(buf, ring[i % 2]["g_unet"], ck),
+                 "b update_ms, c != 0": lambda i: kernels.step_update_ms(buf, ring[i % 2]["g_unet"], ck, c),
+                 "c update_ms, c = 0": lambda i: kernels.step_update_ms(buf, ring[i % 2]["g_unet"], ck, 0.0),
+                 "d K3 + two torch ops": torch_ops,
+                 "K1 without the x0_hat store": fwd(False), "K1 with the x0_hat store": fwd(True)}
+        nbytes = {"a K3": 4 * P * n, "b update_ms, c != 0": 6 * P * n, "c update_ms, c = 0": 4 * P * n}
+        res = {}
+        for rep in range(3):                           # alternated: every form sees the same box state
+            for key, fn in forms.items():
+                res.setdefault(key, []).append(timed(fn))
+        t_k3 = float(np.concatenate(res["a K3"]).mean())
+        k3 = nbytes["a K3"] / t_k3
+        for key in forms:
+            ts = np.concatenate(res[key])
+            runs = " / ".join(f"{r.mean():.1f}" for r in res[key])
+            rate = ""
+            if key in nbytes:
+                bps = nbytes[key] / ts.mean()
+                rate = (f"  {ts.mean() / t_k3:4.2f} x K3's time  {bps / 1e3:7.1f} GB/s ({nbytes[key] / n / P:.0f} P/particle) = "
+                        f"{bps / k3:4.2f} x K3's rate")
+            print(f"dpmpp 256^2 N={n:2d} {key:30s} avg {ts.mean():8.1f} us  min {ts.min():8.1f}  (runs {runs}){rate}",
+                  flush=True)
+        del buf, handle, op
 
 
 def metrics_step(args):
