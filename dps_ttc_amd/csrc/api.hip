@@ -240,8 +240,6 @@ static int score_parts(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
     return (int)parts_per_particle(op, c, h, w);
 }
 
-static inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 static int64_t meas_elems(const dpsx_op *op, int64_t c, int64_t h, int64_t w)
 {
     int64_t oh = h, ow = w;
@@ -261,35 +259,30 @@ struct Ws {
 };
 
 // carves `base` of ws_bytes (nullable: sizes only) and returns the bytes needed, or a negative DPSX_E* code
-static int64_t op_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, char *base, int64_t ws_bytes, Ws *o)
+static int64_t op_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, void *base, int64_t ws_bytes, Ws *o)
 {
     const int64_t m = meas_elems(op, c, h, w);
     if (m < 0) return DPSX_EINVAL;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    };
+    Carver cv(base);
     Ws k{};
-    k.partials = reinterpret_cast<float *>(take(align256(n * std::max<int64_t>(parts_per_particle(op, c, h, w), kResidualSlots) * 4)));
+    k.partials = cv.take<float>(n * std::max<int64_t>(parts_per_particle(op, c, h, w), kResidualSlots));
     switch (op->kind) {
     case OP_SEP:
     case OP_TAPS:
         k.priv_bytes = blur_adjoint_scratch_bytes(op, n * c, h, w);
-        k.priv = take(k.priv_bytes);
+        k.priv = cv.take<char>(k.priv_bytes);
         break;
     case OP_PHASE:
     case OP_IDENT:
     case OP_MASK:
-        k.meas = reinterpret_cast<float *>(take(align256(n * m * 4)));
-        k.img = reinterpret_cast<float *>(take(align256(n * c * h * w * 4)));
-        k.priv_bytes = ws_bytes - off;
-        k.priv = take(op->kind == OP_PHASE ? phase_workspace_bytes(op, n * c) : 0);
+        k.meas = cv.take<float>(n * m);
+        k.img = cv.take<float>(n * c * h * w);
+        k.priv_bytes = ws_bytes - cv.bytes();
+        k.priv = cv.take<char>(op->kind == OP_PHASE ? phase_workspace_bytes(op, n * c) : 0);
         break;
     }
     if (o) *o = k;
-    return off;
+    return cv.bytes();
 }
 
 int64_t dpsx_op_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
@@ -301,10 +294,7 @@ int64_t dpsx_op_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t
 // the launch path's form: the caller checked the geometry (check_geom)
 static int carve(const dpsx_op *op, void *ws, int64_t ws_bytes, int64_t n, int64_t c, int64_t h, int64_t w, Ws &o)
 {
-    const int64_t need = op_carve(op, n, c, h, w, static_cast<char *>(ws), ws_bytes, &o);
-    if (need < 0) return DPSX_EINVAL;
-    if (!ws || ws_bytes < need || !aligned16(ws)) return DPSX_EWORKSPACE;
-    return DPSX_OK;
+    return workspace_check(ws, ws_bytes, op_carve(op, n, c, h, w, ws, ws_bytes, &o));
 }
 
 // a table of `rows` entries serves n particles when rows divides n (common.h: meas_row); rows == n == 0 stays valid
@@ -692,21 +682,18 @@ int dpsx_image_metrics_f32(const float *x, const float *label, int64_t m, float 
     if (!(data_range >= 0.0f) || !std::isfinite(data_range)) return DPSX_EINVAL;           // NaN included
     if (ssim && (h < 11 || w < 11)) return DPSX_EINVAL;
     if (n > 65535 || !metrics_shape_ok(c, h, w)) return DPSX_EUNSUPPORTED;
-    if (workspace_bytes < metrics_workspace_bytes(n, m, c, h, w) || !aligned16(workspace)) return DPSX_EWORKSPACE;
+    const int rc = workspace_check(workspace, workspace_bytes, metrics_workspace_bytes(n, m, c, h, w));
+    if (rc != DPSX_OK) return rc;
     return image_metrics(x, label, m, data_range, mse, psnr, ssim, n, c, h, w, workspace, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ particle repulsion (repulse.hip)
-static int repulse_shape(int64_t n, int64_t chw, int64_t segments)
-{
-    if (n < 0 || chw < 1 || segments < 1 || n % segments) return DPSX_EINVAL;
-    if (n / segments > kRepulseMaxK || segments > 65535 || chw > INT32_MAX) return DPSX_EUNSUPPORTED;
-    return DPSX_OK;
-}
-
+// The entries over an image-major particle set (from here to the principal components) check in this order: their pointers
+// and arguments -- a null workspace is one: DPSX_EINVAL --, the set's shape (common.h: particle_set_shape; the size query
+// applies it and workspace_check passes its refusal on), the workspace.  An empty set is valid for the repulsion entries only.
 int64_t dpsx_repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments)
 {
-    const int rc = repulse_shape(n, chw, segments);
+    const int rc = particle_set_shape(n, chw, segments, kRepulseMaxK, true);
     return rc != DPSX_OK ? rc : repulse_workspace_bytes(n, chw, segments);
 }
 
@@ -714,9 +701,8 @@ int dpsx_pairwise_sqdist_f32(const float *x, float *d2, float *info, int64_t n, 
                              void *workspace, int64_t workspace_bytes, void *stream)
 {
     if (!x || !d2 || !workspace) return DPSX_EINVAL;
-    const int rc = repulse_shape(n, chw, segments);
+    const int rc = workspace_check(workspace, workspace_bytes, dpsx_repulse_workspace_bytes(n, chw, segments));
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return repulse(false, 0.0f, 0.0f, x, nullptr, d2, nullptr, info, nullptr, n, chw, segments, workspace,
                    (hipStream_t)stream);
 }
@@ -727,26 +713,20 @@ int dpsx_repulse_f32(float c, float bandwidth, const float *x, float *out, float
 {
     if (!x || !out || !workspace) return DPSX_EINVAL;
     if (!(c >= 0.0f) || !std::isfinite(c) || !(bandwidth >= 0.0f) || !std::isfinite(bandwidth)) return DPSX_EINVAL;
-    const int rc = repulse_shape(n, chw, segments);
-    if (rc != DPSX_OK) return rc;
+    const int64_t need = dpsx_repulse_workspace_bytes(n, chw, segments);
+    if (need < 0) return (int)need;
     const char *xb = reinterpret_cast<const char *>(x), *ob = reinterpret_cast<const char *>(out);
     const int64_t bytes = n * chw * (int64_t)sizeof(float);
     if (xb < ob + bytes && ob < xb + bytes) return DPSX_EINVAL;       // every particle reads all K: out must not overlap x
-    if (workspace_bytes < repulse_workspace_bytes(n, chw, segments) || !aligned16(workspace)) return DPSX_EWORKSPACE;
+    const int rc = workspace_check(workspace, workspace_bytes, need);
+    if (rc != DPSX_OK) return rc;
     return repulse(true, c, bandwidth, x, out, d2, w, info, applied, n, chw, segments, workspace, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ ensemble statistics (ensemble.hip)
-static int ensemble_shape(int64_t n, int64_t d, int64_t images)
-{
-    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
-    if (n / images > kEnsMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
-    return DPSX_OK;
-}
-
 int64_t dpsx_ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images)
 {
-    const int rc = ensemble_shape(n, d, images);
+    const int rc = particle_set_shape(n, d, images, kEnsMaxK, false);
     return rc != DPSX_OK ? rc : ensemble_workspace_bytes(n, d, images);
 }
 
@@ -756,9 +736,8 @@ int dpsx_ensemble_ex_f32(const float *x, const float *y, const float *neg_log_w,
 {
     if (!x || !mean || !var || !info || !workspace || !mean_lo != !var_lo) return DPSX_EINVAL;
     if (count0 < 0 || (neg_log_w && count0 > 0) || (curve && !y)) return DPSX_EINVAL;
-    const int rc = ensemble_shape(n, d, images);
+    const int rc = workspace_check(workspace, workspace_bytes, dpsx_ensemble_workspace_bytes(n, d, images));
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < ensemble_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return ensemble(x, y, neg_log_w, count0, mean, var, mean_lo, var_lo, curve, info, n, d, images, workspace,
                     (hipStream_t)stream);
 }
@@ -772,16 +751,9 @@ int dpsx_ensemble_f32(const float *x, const float *y, const float *neg_log_w, in
 }
 
 // ------------------------------------------------------------------ order statistics (quantile.hip)
-static int quantiles_shape(int64_t n, int64_t d, int64_t images)
-{
-    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
-    if (n / images > kQuantMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
-    return DPSX_OK;
-}
-
 int64_t dpsx_quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images)
 {
-    const int rc = quantiles_shape(n, d, images);
+    const int rc = particle_set_shape(n, d, images, kQuantMaxK, false);
     return rc != DPSX_OK ? rc : quantiles_workspace_bytes(n, d, images);
 }
 
@@ -793,23 +765,15 @@ int dpsx_quantiles_f32(const float *x, const float *y, const double *probs, int6
     if (q < 1 || q > kQuantMaxQ) return DPSX_EINVAL;
     for (int64_t i = 0; i < q; ++i)
         if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return DPSX_EINVAL;       // NaN fails both
-    const int rc = quantiles_shape(n, d, images);
+    const int rc = workspace_check(workspace, workspace_bytes, dpsx_quantiles_workspace_bytes(n, d, images));
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < quantiles_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return quantiles(x, y, probs, q, quant, hist, info, n, d, images, workspace, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ principal components (pca.hip)
-static int pca_shape(int64_t n, int64_t d, int64_t images)
-{
-    if (n < 1 || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
-    if (n / images > kPcaMaxK || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
-    return DPSX_OK;
-}
-
 int64_t dpsx_pca_workspace_bytes(int64_t n, int64_t d, int64_t images)
 {
-    const int rc = pca_shape(n, d, images);
+    const int rc = particle_set_shape(n, d, images, kPcaMaxK, false);
     return rc != DPSX_OK ? rc : pca_workspace_bytes(n, d, images);
 }
 
@@ -818,9 +782,8 @@ int dpsx_pca_f32(const float *x, int64_t q, float *dirs, float *evals, float *co
 {
     if (!x || !dirs || !evals || !coords || !info || !workspace) return DPSX_EINVAL;
     if (q < 1 || q > kPcaMaxQ) return DPSX_EINVAL;
-    const int rc = pca_shape(n, d, images);
+    const int rc = workspace_check(workspace, workspace_bytes, dpsx_pca_workspace_bytes(n, d, images));
     if (rc != DPSX_OK) return rc;
-    if (workspace_bytes < pca_workspace_bytes(n, d, images) || !aligned16(workspace)) return DPSX_EWORKSPACE;
     return pca(x, q, dirs, evals, coords, info, d2, n, d, images, workspace, (hipStream_t)stream);
 }
 
@@ -841,29 +804,21 @@ struct CgWs {
 };
 
 // carves `base` (nullable: sizes only) and returns the bytes needed, or a negative DPSX_E* code
-static int64_t cg_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, char *base, CgWs *o)
+static int64_t cg_carve(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w, void *base, CgWs *o)
 {
     const int64_t op_bytes = dpsx_op_workspace_bytes(op, n, c, h, w), m = meas_elems(op, c, h, w);
     if (op_bytes < 0 || m < 0) return DPSX_EINVAL;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        char *p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    const int64_t part = n * 256 * 4, img = n * c * h * w * 4;
+    Carver cv(base);
     CgWs k{};
-    k.op_ws = take(op_bytes);
+    k.op_ws = cv.take<char>(op_bytes);
     k.op_bytes = op_bytes;
-    float **f[] = {&k.norm_part, &k.rs[0], &k.rs[1], &k.pp, &k.tt};
-    for (float **q : f) *q = reinterpret_cast<float *>(take(part));
-    k.scal = reinterpret_cast<float *>(take(n * 4 * 4));
-    k.t = reinterpret_cast<float *>(take(n * m * 4));
-    k.ry = reinterpret_cast<float *>(take(n * m * 4));
-    float **g[] = {&k.r, &k.p, &k.s, &k.d};
-    for (float **q : g) *q = reinterpret_cast<float *>(take(img));
+    for (float **q : {&k.norm_part, &k.rs[0], &k.rs[1], &k.pp, &k.tt}) *q = cv.take<float>(n * 256);
+    k.scal = cv.take<float>(n * 4);
+    k.t = cv.take<float>(n * m);
+    k.ry = cv.take<float>(n * m);
+    for (float **q : {&k.r, &k.p, &k.s, &k.d}) *q = cv.take<float>(n * c * h * w);
     if (o) *o = k;
-    return off;
+    return cv.bytes();
 }
 
 int64_t dpsx_cg_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t h, int64_t w)
@@ -893,9 +848,8 @@ int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, cons
     }
     if (n == 0) return DPSX_OK;
     CgWs k;
-    const int64_t need = cg_carve(op, n, c, h, w, static_cast<char *>(workspace), &k);
-    if (need < 0) return (int)need;
-    if (!workspace || workspace_bytes < need || !aligned16(workspace)) return DPSX_EWORKSPACE;
+    rc = workspace_check(workspace, workspace_bytes, cg_carve(op, n, c, h, w, workspace, &k));
+    if (rc != DPSX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t e = c * h * w, m = meas_elems(op, c, h, w);
     // r_y = y - A x0_hat, dist = ||r_y||_2 (the residual-norm path), r = A^T r_y

@@ -1522,7 +1522,7 @@ int64_t blur_adjoint_scratch_bytes(const dpsx_op *op, int64_t planes, int64_t h,
     // the separable 16-byte path does not touch the buffer, but one buffer off the 16-byte grid (blur_vec) sends the same
     // shape through launch_taps_adj, which does
     const int64_t r4 = op->blur->t.radius4;
-    return ((planes * (h + 2 * r4) * (w + 2 * r4) * 4 + 255) / 256) * 256;
+    return align256(planes * (h + 2 * r4) * (w + 2 * r4) * 4);
 }
 
 template <bool EPI, int SWC>

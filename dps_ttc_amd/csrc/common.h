@@ -48,6 +48,48 @@ inline bool vec_ok(int64_t size, std::initializer_list<const void *> ptrs)
     return true;
 }
 
+// -------------------------------------------------------------------- host: workspaces and particle sets
+// Every region of a caller-provided workspace starts on a 256-byte boundary of it.
+inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+
+// Walks a workspace layout: take<T>(count) is the next region as a typed pointer and advances by align256(count * sizeof(T));
+// bytes() is the total so far.  base == nullptr: sizes only (every pointer is null).  A layout is ONE function that takes
+// its regions from a Carver, so a size query (null base) and the launch path (the caller's base) cannot disagree.
+// Owns and allocates nothing.
+class Carver {
+public:
+    explicit Carver(void *base) : base_(static_cast<char *>(base)) {}
+    template <class T> T *take(int64_t count)
+    {
+        char *p = base_ ? base_ + off_ : nullptr;
+        off_ += align256(count * (int64_t)sizeof(T));
+        return reinterpret_cast<T *>(p);
+    }
+    int64_t bytes() const { return off_; }
+
+private:
+    char *base_;
+    int64_t off_ = 0;
+};
+
+// a workspace of `bytes` at ws serves a call that needs `need`: what a size query returned, so a negative value is the
+// query's refusal (DPSX_E*) and is passed on
+inline int workspace_check(const void *ws, int64_t bytes, int64_t need)
+{
+    if (need < 0) return (int)need;
+    return !ws || bytes < need || !aligned16(ws) ? DPSX_EWORKSPACE : DPSX_OK;
+}
+
+// THE shape rule of an image-major particle set: n particles of d elements each, `images` images of K = n / images
+// consecutive particles.  images is a grid dimension and d is indexed in 32 bits; max_k is the family's limit on K;
+// allow_empty: n == 0 is a valid (empty) set.
+inline int particle_set_shape(int64_t n, int64_t d, int64_t images, int64_t max_k, bool allow_empty)
+{
+    if (n < (allow_empty ? 0 : 1) || d < 1 || images < 1 || n % images) return DPSX_EINVAL;
+    if (n / images > max_k || images > 65535 || d > INT32_MAX) return DPSX_EUNSUPPORTED;
+    return DPSX_OK;
+}
+
 // -------------------------------------------------------------------- host: launches with large dynamic LDS
 // Dynamic LDS above 64 KiB needs the attribute once per kernel symbol: the kernel is a template argument, so every symbol
 // has its own flag.  launch_lds<k_name<...>>(grid, threads, lds_bytes, stream, kernel arguments...)
@@ -260,6 +302,10 @@ __device__ __forceinline__ float wave_sum(float v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
     return v;
 }
+
+// NaN-propagating minimum / maximum: torch's min / max return NaN if any element is NaN
+__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
 
 // Deterministic block sum (fixed shuffle tree, waves added in index order).
 // Result valid in thread 0.  `scratch` holds >= blockDim.x/64 floats.

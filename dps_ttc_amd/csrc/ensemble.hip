@@ -279,39 +279,37 @@ __global__ __launch_bounds__(kWave) void k_ens_finish(const EnsArgs a)
 }
 
 // ------------------------------------------------------------------ host side
-static int64_t ens_align(int64_t v) { return (v + 255) / 256 * 256; }
-
-struct EnsWs { int64_t part_off, var_off, w_off, ess_off, flag_off, total; };
-static EnsWs ens_ws(int64_t n, int64_t d, int64_t images)
+// THE workspace layout: the stream launch's partials, then what the weights launch leaves (a.w, a.ess, a.uniform: set
+// here, kept only with E); returns the bytes (the size query and the launch path both walk it)
+static int64_t ens_layout(EnsArgs &a, Carver cv, int64_t n, int64_t d, int64_t images)
 {
     const int64_t k = n / images, slots = cg_slots(d);
-    EnsWs o;
-    o.part_off = 0;
-    o.var_off = ens_align(images * slots * (k + 1) * (int64_t)sizeof(float));
-    o.w_off = o.var_off + ens_align(images * slots * (int64_t)sizeof(float));
-    o.ess_off = o.w_off + ens_align(n * (int64_t)sizeof(float));
-    o.flag_off = o.ess_off + ens_align(images * (int64_t)sizeof(float));
-    o.total = o.flag_off + ens_align(images * (int64_t)sizeof(int));
-    return o;
+    a.part = cv.take<float>(images * slots * (k + 1));
+    a.varpart = cv.take<float>(images * slots);
+    a.w = cv.take<float>(n);
+    a.ess = cv.take<float>(images);
+    a.uniform = cv.take<int>(images);
+    return cv.bytes();
 }
 
-int64_t ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images) { return ens_ws(n, d, images).total; }
+int64_t ensemble_workspace_bytes(int64_t n, int64_t d, int64_t images)
+{
+    EnsArgs a{};
+    return ens_layout(a, Carver(nullptr), n, d, images);
+}
 
 int ensemble(const float *x, const float *y, const float *e, int64_t count0, float *mean, float *var, float *mean_lo,
              float *var_lo, float *curve, float *info, int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s)
 {
     const int64_t k = n / images;
-    const EnsWs ws = ens_ws(n, d, images);
-    char *base = static_cast<char *>(workspace);
     const bool vec = vec_ok(d, {x, y, mean, var, mean_lo, var_lo});
     const PassGeom g = pass_geom(d, vec, images);
     EnsArgs a{};
+    ens_layout(a, Carver(workspace), n, d, images);
     a.x = x;
     a.y = y;
     a.mean = mean;
     a.var = var;
-    a.part = reinterpret_cast<float *>(base + ws.part_off);
-    a.varpart = reinterpret_cast<float *>(base + ws.var_off);
     a.curve = curve;
     a.mean_lo = mean_lo;
     a.var_lo = var_lo;
@@ -321,15 +319,14 @@ int ensemble(const float *x, const float *y, const float *e, int64_t count0, flo
     a.k = (int)k;
     a.slots = cg_slots(d);
     a.count0 = (double)count0;
-    if (e) {
-        float *w = reinterpret_cast<float *>(base + ws.w_off), *ess = reinterpret_cast<float *>(base + ws.ess_off);
-        int *flag = reinterpret_cast<int *>(base + ws.flag_off);
-        k_ens_weights<<<(unsigned)images, kPassThreads, 0, s>>>(e, w, flag, ess, (int)k);
+    if (e) {                                                 // the one launch that writes what the others only read
+        k_ens_weights<<<(unsigned)images, kPassThreads, 0, s>>>(e, const_cast<float *>(a.w), const_cast<int *>(a.uniform),
+                                                                const_cast<float *>(a.ess), (int)k);
         const int rc = check_launch();
         if (rc != DPSX_OK) return rc;
-        a.w = w;
-        a.ess = ess;
-        a.uniform = flag;
+    } else {
+        a.w = a.ess = nullptr;
+        a.uniform = nullptr;
     }
     const size_t lds = (y ? k * sizeof(double) + kEnsWaves * (k + 1) * sizeof(float) : 0) + (e ? k * sizeof(float) : 0);
     int rc = dispatch(vec, y != nullptr, [&](auto V, auto C) { return launch_lds<k_ens_stream<V.value, C.value>>(g.grid, kPassThreads, lds, s, a); });

@@ -55,10 +55,7 @@ struct MetricsArgs {
 };
 
 // ------------------------------------------------------------------ the label range
-// torch's max / min return NaN if any element is NaN
-__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-
+// (common.h: nan_min / nan_max -- a NaN in the label is a NaN range, as torch's max - min)
 __device__ __forceinline__ void wave_minmax(float &mn, float &mx)
 {
 #pragma unroll
@@ -312,18 +309,16 @@ __global__ __launch_bounds__(kWave) void k_metrics_finish(const MetricsArgs a)
 static int range_slots(int64_t chw) { return (int)std::min<int64_t>(kRangeMax, cg_slots(chw)); }
 static int64_t tiles_of(int64_t extent) { return extent < kWin ? 0 : (extent - kApron + kTile - 1) / kTile; }
 static int64_t tile_count(int64_t c, int64_t h, int64_t w) { return c * tiles_of(h) * tiles_of(w); }
-static int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
-struct MetricsWs { int64_t range_off, sse_off, ssim_off, total; };
-static MetricsWs metrics_ws(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w)
+// THE workspace layout: the partials of the three launches; returns the bytes (the size query and the launch path both
+// walk it)
+static int64_t metrics_layout(MetricsArgs &a, Carver cv, int64_t n, int64_t m, int64_t c, int64_t h, int64_t w)
 {
     const int64_t chw = c * h * w;
-    MetricsWs o;
-    o.range_off = 0;
-    o.sse_off = align256(m * range_slots(chw) * 2 * (int64_t)sizeof(float));
-    o.ssim_off = o.sse_off + align256(n * cg_slots(chw) * (int64_t)sizeof(float));
-    o.total = o.ssim_off + align256(std::max<int64_t>(1, n * tile_count(c, h, w)) * (int64_t)sizeof(float));
-    return o;
+    a.range_part = cv.take<float>(m * range_slots(chw) * 2);
+    a.sse_part = cv.take<float>(n * cg_slots(chw));
+    a.ssim_part = cv.take<float>(std::max<int64_t>(1, n * tile_count(c, h, w)));
+    return cv.bytes();
 }
 
 bool metrics_shape_ok(int64_t c, int64_t h, int64_t w)
@@ -334,7 +329,8 @@ bool metrics_shape_ok(int64_t c, int64_t h, int64_t w)
 
 int64_t metrics_workspace_bytes(int64_t n, int64_t m, int64_t c, int64_t h, int64_t w)
 {
-    return metrics_ws(n, m, c, h, w).total;
+    MetricsArgs a{};
+    return metrics_layout(a, Carver(nullptr), n, m, c, h, w);
 }
 
 int image_metrics(const float *x, const float *label, int64_t m, float data_range, float *mse, float *psnr, float *ssim,
@@ -342,16 +338,16 @@ int image_metrics(const float *x, const float *label, int64_t m, float data_rang
 {
     if (n == 0) return DPSX_OK;
     const int64_t chw = c * h * w;
-    const MetricsWs ws = metrics_ws(n, m, c, h, w);
-    char *base = static_cast<char *>(workspace);
     const bool want_sse = mse || psnr, want_range = !(data_range > 0.0f) && (psnr || ssim);
     const bool vec = vec_ok(chw, {x, label});
     MetricsArgs a{};
+    metrics_layout(a, Carver(workspace), n, m, c, h, w);
+    float *range_part = const_cast<float *>(a.range_part);       // written by the range launch, read by the others
+    if (!want_range) a.range_part = nullptr;                     // a region that is not wanted is not launched on
+    if (!want_sse) a.sse_part = nullptr;
+    if (!ssim) a.ssim_part = nullptr;
     a.x = x;
     a.label = label;
-    a.range_part = want_range ? reinterpret_cast<float *>(base + ws.range_off) : nullptr;
-    a.sse_part = want_sse ? reinterpret_cast<float *>(base + ws.sse_off) : nullptr;
-    a.ssim_part = ssim ? reinterpret_cast<float *>(base + ws.ssim_off) : nullptr;
     a.mse = mse;
     a.psnr = psnr;
     a.ssim = ssim;
@@ -374,7 +370,7 @@ int image_metrics(const float *x, const float *label, int64_t m, float data_rang
     if (want_range) {
         const int64_t per = (chw + a.range_slots - 1) / a.range_slots;
         k_label_range<<<dim3((unsigned)a.range_slots, (unsigned)m), kPassThreads, 0, s>>>(
-            label, reinterpret_cast<float *>(base + ws.range_off), chw, per);
+            label, range_part, chw, per);
         int rc = check_launch();
         if (rc != DPSX_OK) return rc;
     }

@@ -337,23 +337,32 @@ __global__ __launch_bounds__(kPassThreads) void k_pca_project(const PcaArgs a)
     }
 }
 
-int64_t pca_align(int64_t v) { return (v + 255) / 256 * 256; }
+// THE workspace layout: [the distance launches' own workspace | d2 [images, K, K] when the caller keeps none]; returns the
+// bytes (the size query and the launch path both walk it).  The first region starts at the base: repulse() is handed the
+// workspace as it is
+int64_t pca_layout(float *&d2, Carver cv, int64_t n, int64_t d, int64_t images)
+{
+    const int64_t k = n / images;
+    cv.take<char>(repulse_workspace_bytes(n, d, images));
+    d2 = cv.take<float>(images * k * k);
+    return cv.bytes();
+}
 
 }  // namespace
 
-// [the distance launches' own workspace | d2 [images, K, K] when the caller keeps none]
 int64_t pca_workspace_bytes(int64_t n, int64_t d, int64_t images)
 {
-    const int64_t k = n / images;
-    return pca_align(repulse_workspace_bytes(n, d, images)) + pca_align(images * k * k * (int64_t)sizeof(float));
+    float *d2;
+    return pca_layout(d2, Carver(nullptr), n, d, images);
 }
 
 int pca(const float *x, int64_t q, float *dirs, float *evals, float *coords, float *info, float *d2, int64_t n, int64_t d,
         int64_t images, void *workspace, hipStream_t s)
 {
     const int64_t k = n / images;
-    char *base = static_cast<char *>(workspace);
-    float *dist = d2 ? d2 : reinterpret_cast<float *>(base + pca_align(repulse_workspace_bytes(n, d, images)));
+    float *dist;
+    pca_layout(dist, Carver(workspace), n, d, images);
+    if (d2) dist = d2;
     int rc = repulse(false, 0.0f, 0.0f, x, nullptr, dist, nullptr, nullptr, nullptr, n, d, images, workspace, s);
     if (rc != DPSX_OK) return rc;
 

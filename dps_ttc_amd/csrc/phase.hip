@@ -96,7 +96,7 @@ void phase_destroy(dpsx_op *op)
 int64_t phase_workspace_bytes(const dpsx_op *op, int64_t planes)
 {
     const int64_t s = op->phase->h + 2 * op->phase->pad;
-    return (planes * s * s * 8 + 255) / 256 * 256;
+    return align256(planes * s * s * 8);
 }
 
 // The fused step works on the Hermitian half: x0_hat is real, so Z[-k] = conj(Z[k]) and the s x (s/2 + 1) half
@@ -114,7 +114,7 @@ int64_t phase_parts_per_particle(const dpsx_op *op, int64_t c)
 int64_t phase_step_resid_bytes(const dpsx_op *op, int64_t planes)
 {
     const int64_t s = op->phase->h + 2 * op->phase->pad;
-    return (planes * s * s * 4 + 255) / 256 * 256 + (planes * s * (s / 2 + 1) * 8 + 255) / 256 * 256;
+    return align256(planes * s * s * 4) + align256(planes * s * (s / 2 + 1) * 8);
 }
 
 // ---------------------------------------------------------------- kernels
@@ -406,7 +406,7 @@ int phase_step_fwd(dpsx_op *op, const StepFwdArgs &f, float *resid_c, hipStream_
     const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
-                                              (planes * sz * sz * 4 + 255) / 256 * 256);
+                                              align256(planes * sz * sz * 4));
     int rc;
     // (vec_ok's size test is phase_vec4_ok's h % 4 == 0)
     const bool vec = phase_vec4_ok(op) && vec_ok(h, {f.x_t, f.model_out, f.noise, f.x0_hat, f.sample}) && aligned4(f.inside);
@@ -474,7 +474,7 @@ int phase_step_bwd_fused(dpsx_op *op, float *resid_c, const StepBwdArgs &b, hipS
     const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
-                                              (planes * sz * sz * 4 + 255) / 256 * 256);
+                                              align256(planes * sz * sz * 4));
     hipfftHandle plan;
     int rc = get_plan(op, planes, &plan, 2);
     if (rc != DPSX_OK) return rc;
@@ -491,7 +491,7 @@ int phase_step_bwd(dpsx_op *op, float *resid_c, float *g_x0, int64_t planes, hip
     const int h = (int)op->phase->h, pad = (int)op->phase->pad, sz = h + 2 * pad;
     float *real = resid_c;
     float2 *half = reinterpret_cast<float2 *>(reinterpret_cast<char *>(resid_c) +
-                                              (planes * sz * sz * 4 + 255) / 256 * 256);
+                                              align256(planes * sz * sz * 4));
     hipfftHandle plan;
     int rc = get_plan(op, planes, &plan, 2);
     if (rc != DPSX_OK) return rc;

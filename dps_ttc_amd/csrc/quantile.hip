@@ -416,21 +416,23 @@ static int quant_pad(int64_t k)
     while (kp < k) kp <<= 1;
     return kp;
 }
-static int64_t quant_align(int64_t v) { return (v + 255) / 256 * 256; }
 
-struct QuantWs { int64_t ipart_off, cpart_off, wpart_off, total; };
-static QuantWs quant_ws(int64_t n, int64_t d, int64_t images)
+// THE workspace layout: the three partial arrays of the sort launch; returns the bytes (the size query and the launch path
+// both walk it)
+static int64_t quant_layout(QuantArgs &a, Carver cv, int64_t n, int64_t d, int64_t images)
 {
     const int64_t k = n / images, slots = quant_slots(d, k);
-    QuantWs o;
-    o.ipart_off = 0;
-    o.cpart_off = quant_align(images * slots * (k + 3) * (int64_t)sizeof(int));
-    o.wpart_off = o.cpart_off + quant_align(images * slots * (int64_t)sizeof(float));
-    o.total = o.wpart_off + quant_align(images * slots * (int64_t)sizeof(float));
-    return o;
+    a.ipart = cv.take<int>(images * slots * (k + 3));
+    a.cpart = cv.take<float>(images * slots);
+    a.wpart = cv.take<float>(images * slots);
+    return cv.bytes();
 }
 
-int64_t quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images) { return quant_ws(n, d, images).total; }
+int64_t quantiles_workspace_bytes(int64_t n, int64_t d, int64_t images)
+{
+    QuantArgs a{};
+    return quant_layout(a, Carver(nullptr), n, d, images);
+}
 
 template <int KP> static int quant_launch_reg(const QuantArgs &a, dim3 grid, hipStream_t s)
 {
@@ -442,15 +444,11 @@ int quantiles(const float *x, const float *y, const double *probs, int64_t q, fl
               int64_t n, int64_t d, int64_t images, void *workspace, hipStream_t s)
 {
     const int64_t k = n / images;
-    const QuantWs ws = quant_ws(n, d, images);
-    char *base = static_cast<char *>(workspace);
     QuantArgs a{};
+    quant_layout(a, Carver(workspace), n, d, images);
     a.x = x;
     a.y = y;
     a.quant = quant;
-    a.ipart = reinterpret_cast<int *>(base + ws.ipart_off);
-    a.cpart = reinterpret_cast<float *>(base + ws.cpart_off);
-    a.wpart = reinterpret_cast<float *>(base + ws.wpart_off);
     a.hist = hist;
     a.info = info;
     a.d = d;

@@ -148,9 +148,6 @@ __global__ __launch_bounds__(kPassThreads) void k_repulse_pairs(const RepArgs a)
     }
 }
 
-// NaN-propagating minimum (a NaN distance shows in the record)
-__device__ __forceinline__ float rep_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
-
 __global__ __launch_bounds__(kRepFinishThreads) void k_repulse_finish(const RepArgs a)
 {
     constexpr int kWaves = kRepFinishThreads / kWave;
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(kRepFinishThreads) void k_repulse_finish(const RepA
     float *d2 = a.d2 + m * kk;
 
     double sum = 0.0;
-    float mn = INFINITY;
+    float mn = INFINITY;                                     // nan_min: a NaN distance shows in the record
     for (int idx = threadIdx.x; idx < kk; idx += kRepFinishThreads) {
         const int i = idx / k, j = idx - i * k;
         if (i == j) d2[idx] = 0.0f;
@@ -182,11 +179,11 @@ __global__ __launch_bounds__(kRepFinishThreads) void k_repulse_finish(const RepA
         d2[idx] = v;
         d2[j * k + i] = v;
         sum += (double)v;
-        mn = rep_min(mn, v);
+        mn = nan_min(mn, v);
     }
     wave_sum_f64(sum);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mn = rep_min(mn, __shfl_down(mn, o, kWave));
+    for (int o = 32; o > 0; o >>= 1) mn = nan_min(mn, __shfl_down(mn, o, kWave));
     if ((threadIdx.x & (kWave - 1)) == 0) {
         s_sum[threadIdx.x >> 6] = sum;
         s_min[threadIdx.x >> 6] = mn;
@@ -196,7 +193,7 @@ __global__ __launch_bounds__(kRepFinishThreads) void k_repulse_finish(const RepA
         double total = 0.0;
         for (int q = 0; q < kWaves; ++q) {
             total += s_sum[q];
-            if (q) mn = rep_min(mn, s_min[q]);
+            if (q) mn = nan_min(mn, s_min[q]);
         }
         const double mean = k > 1 ? total / (double)npairs : 0.0;
         const double h = a.bandwidth > 0.0f ? (double)a.bandwidth * (double)a.chw : mean / log((double)(k + 1));
@@ -283,7 +280,6 @@ __global__ __launch_bounds__(kPassThreads) void k_repulse_apply(const RepArgs a)
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 int rep_tiles(int64_t k) { return (int)std::max<int64_t>(1, (k + kRepTile - 1) / kRepTile); }
 int rep_fill(int64_t chw, int64_t blocks_y)      // slots that bring a launch of blocks_y blocks per range to kRepBlocks
 {
@@ -296,25 +292,25 @@ int rep_slots(int64_t chw, int64_t k)
     return rep_fill(chw, nt * (nt + 1) / 2);
 }
 
-struct RepWs { int64_t part, d2, wpad, info, applied, total; };
-RepWs rep_ws(int64_t segments, int64_t k, int64_t chw)
+// THE workspace layout: the pair partials, then what the launches need of d2, w (padded), info and applied when the
+// caller keeps none; returns the bytes (the size query and the launch path both walk it)
+int64_t rep_layout(RepArgs &a, Carver cv, int64_t segments, int64_t k, int64_t chw)
 {
     const int64_t kp = rep_tiles(k) * kRepTile, npairs = k * (k - 1) / 2;
-    RepWs o;
-    o.part = 0;
-    o.d2 = align256(std::max<int64_t>(1, segments * rep_slots(chw, k) * npairs) * 4);
-    o.wpad = o.d2 + align256(segments * k * k * 4);
-    o.info = o.wpad + align256(segments * k * kp * 4);
-    o.applied = o.info + align256(segments * 16);
-    o.total = o.applied + align256(segments);
-    return o;
+    a.part = cv.take<float>(std::max<int64_t>(1, segments * rep_slots(chw, k) * npairs));
+    a.d2 = cv.take<float>(segments * k * k);
+    a.wpad = cv.take<float>(segments * k * kp);
+    a.info = cv.take<float>(segments * 4);
+    a.applied = cv.take<uint8_t>(segments);
+    return cv.bytes();
 }
 
 }  // namespace
 
 int64_t repulse_workspace_bytes(int64_t n, int64_t chw, int64_t segments)
 {
-    return rep_ws(segments, n / segments, chw).total;
+    RepArgs a{};
+    return rep_layout(a, Carver(nullptr), segments, n / segments, chw);
 }
 
 int repulse(bool apply, float c, float bandwidth, const float *x, float *out, float *d2, float *w, float *info,
@@ -322,20 +318,18 @@ int repulse(bool apply, float c, float bandwidth, const float *x, float *out, fl
 {
     if (n == 0) return DPSX_OK;
     const int64_t k = n / segments;
-    const RepWs ws = rep_ws(segments, k, chw);
-    char *base = static_cast<char *>(workspace);
     const int nt = rep_tiles(k);
     const bool vec = vec_ok(chw, {x, out});
     const int64_t units = vec ? chw / 4 : chw;
     RepArgs a{};
+    rep_layout(a, Carver(workspace), segments, k, chw);
     a.x = x;
     a.out = out;
-    a.part = reinterpret_cast<float *>(base + ws.part);
-    a.d2 = d2 ? d2 : reinterpret_cast<float *>(base + ws.d2);
-    a.wpad = apply ? reinterpret_cast<float *>(base + ws.wpad) : nullptr;
+    if (d2) a.d2 = d2;                                       // the caller's buffers take the place of the workspace's
+    if (!apply) a.wpad = nullptr;
     a.w = apply ? w : nullptr;
-    a.info = info ? info : reinterpret_cast<float *>(base + ws.info);
-    a.applied = applied ? applied : reinterpret_cast<uint8_t *>(base + ws.applied);
+    if (info) a.info = info;
+    if (applied) a.applied = applied;
     a.chw = chw;
     a.k = (int)k;
     a.kp = nt * kRepTile;

@@ -1014,13 +1014,47 @@ def step_update_dsg(buf, g_unet, coefs, model_out, guidance_rate, noise=None, rn
     return out, stats
 
 
-# ------------------------------------------------------------------ image metrics (include/dpsx.h: "reconstruction metrics")
-METRIC_NAMES = ("mse", "psnr", "ssim")
-_metrics_ws = {}         # (device, n, m, c, h, w) -> the call's workspace, as StepBuffers keeps its buffers per shape
+# ------------------------------------------------------------------ what the analysis calls share
+# (metrics, repulsion, ensemble, order statistics, principal components): the cache of the calls' workspaces, the shape rule
+# of an image-major particle set and the labels of its images
+# (size query, device, the query's arguments) -> the call's workspace, as StepBuffers keeps its buffers per shape; the
+# query's name is in the key: two families never share a buffer
+_workspaces = {}
 
 
-def _label_rows(label, x):
-    """label as [M, C, H, W] for particles x [N, C, H, W]: [C, H, W], [1, ...] or [M, ...] with M | N"""
+def _workspace(query, device, *shape):
+    """the cached workspace of an analysis call: lib().<query>(*shape) bytes on `device` (a refusal raises under the
+    query's name); serves one stream at a time"""
+    key = (query, device) + shape
+    ws = _workspaces.get(key)
+    if ws is None:
+        need = getattr(lib(), query)(*shape)
+        if need < 0:
+            check(int(need), query)
+        ws = _workspaces[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _particle_shape(shape, images, nchw=True, allow_empty=False):
+    """the shape rule of an image-major particle set: `shape` [N, C, H, W] (nchw False: [N, ...]) splits into `images`
+    images of K = N / images consecutive particles of D elements -> (N, K, D, images).  allow_empty: N == 0 is a set"""
+    if len(shape) != 4 if nchw else len(shape) < 2:
+        raise ValueError(f"particles must be {'[N, C, H, W]' if nchw else '[N, ...]'} (got {tuple(shape)})")
+    n, images = int(shape[0]), int(images)
+    if images < 1 or n % images or (n < 1 and not allow_empty):
+        raise ValueError(f"{n} particles do not split into {images} images")
+    return n, n // images, int(np.prod(shape[1:], dtype=np.int64)), images
+
+
+def _particle_set(x, images, nchw=True, allow_empty=False):
+    """x as the library takes a particle set (contiguous float32 on the device) and its shape -> (x, N, K, D, images)"""
+    x = f32c(x, "particles")
+    return (x,) + _particle_shape(x.shape, images, nchw, allow_empty)
+
+
+def _label_rows(label, x, images=None):
+    """label as [M, C, H, W] for particles x [N, C, H, W]: [C, H, W], [1, ...] or [M, ...] with M | N.  images: the labels
+    of `images` images -- one label serves them all (expanded), otherwise the counts must match"""
     label = f32c(label, "label")
     if label.dim() == 3:
         label = label.unsqueeze(0)
@@ -1031,7 +1065,16 @@ def _label_rows(label, x):
     m = label.shape[0]
     if m < 1 or x.shape[0] % m:
         raise ValueError(f"{m} labels do not divide {x.shape[0]} particles")
+    if images is not None:
+        if m == 1 and images > 1:
+            label = label.expand((images,) + tuple(x.shape[1:])).contiguous()
+        if label.shape[0] != images:
+            raise ValueError(f"{label.shape[0]} labels given for {images} images")
     return label
+
+
+# ------------------------------------------------------------------ image metrics (include/dpsx.h: "reconstruction metrics")
+METRIC_NAMES = ("mse", "psnr", "ssim")
 
 
 def image_metrics(x, label, data_range=None, want=METRIC_NAMES, out=None, stream=None):
@@ -1043,9 +1086,7 @@ def image_metrics(x, label, data_range=None, want=METRIC_NAMES, out=None, stream
     want = tuple(want)
     if not want or any(k not in METRIC_NAMES for k in want) or len(set(want)) != len(want):
         raise ValueError(f"want must name some of {METRIC_NAMES} once each (got {want})")
-    x = f32c(x, "particles")
-    if x.dim() != 4:
-        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
+    x = _particle_set(x, 1, allow_empty=True)[0]             # the images are the label's rows: M | N is _label_rows' rule
     label = _label_rows(label, x)
     n, c, h, w = (int(v) for v in x.shape)
     m = int(label.shape[0])
@@ -1057,13 +1098,7 @@ def image_metrics(x, label, data_range=None, want=METRIC_NAMES, out=None, stream
         elif tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
             raise ValueError(f"out[{k!r}] must be a contiguous float32 [{n}] tensor on {x.device}")
         res[k] = t
-    key = (x.device, n, m, c, h, w)
-    ws = _metrics_ws.get(key)
-    if ws is None:
-        need = lib().dpsx_metrics_workspace_bytes(n, m, c, h, w)
-        if need < 0:
-            check(int(need), "dpsx_metrics_workspace_bytes")
-        ws = _metrics_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    ws = _workspace("dpsx_metrics_workspace_bytes", x.device, n, m, c, h, w)
     check(lib().dpsx_image_metrics_f32(ptr(x), ptr(label), m, 0.0 if data_range is None else float(data_range),
                                        ptr(res.get("mse")), ptr(res.get("psnr")), ptr(res.get("ssim")), n, c, h, w,
                                        ptr(ws), ws.numel(), _stream_arg(stream, x)), "dpsx_image_metrics_f32")
@@ -1104,25 +1139,11 @@ class MetricTrace:
 # ------------------------------------------------------------------ particle repulsion (include/dpsx.h: "particle repulsion")
 REPULSE_MAX_K = 512      # particles per image (DPSX_EUNSUPPORTED above)
 REPULSE_INFO = ("h", "gain", "mean", "min")      # the columns of info [M, 4]
-_repulse_ws = {}         # (device, n, chw, images) -> the call's workspace, as _metrics_ws
 
 
 def _repulse_args(x, images):
-    x = f32c(x, "particles")
-    if x.dim() < 2:
-        raise ValueError(f"particles must be [N, ...] (got {tuple(x.shape)})")
-    n, images = int(x.shape[0]), int(images)
-    if images < 1 or n % images:
-        raise ValueError(f"{n} particles do not split into {images} images")
-    chw = x[0].numel() if n else int(np.prod(x.shape[1:]))
-    key = (x.device, n, chw, images)
-    ws = _repulse_ws.get(key)
-    if ws is None:
-        need = lib().dpsx_repulse_workspace_bytes(n, chw, images)
-        if need < 0:
-            check(int(need), "dpsx_repulse_workspace_bytes")
-        ws = _repulse_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
-    return x, n, chw, images, ws
+    x, n, _, chw, images = _particle_set(x, images, nchw=False, allow_empty=True)
+    return x, n, chw, images, _workspace("dpsx_repulse_workspace_bytes", x.device, n, chw, images)
 
 
 def pairwise_sqdist(x, images=1, want_info=False, stream=None):
@@ -1182,7 +1203,6 @@ def repulse(x, strength, images=1, bandwidth=None, out=None, want_info=False, st
 # ------------------------------------------------------------------ ensemble statistics (include/dpsx.h: "ensemble statistics")
 ENSEMBLE_MAX_K = 4096    # particles per image (DPSX_EUNSUPPORTED above)
 ENSEMBLE_INFO = ("ess", "mean_var", "mse", "count")      # the columns of info [M, 4]
-_ensemble_ws = {}        # (device, n, d, images) -> the call's workspace, as _metrics_ws
 
 
 def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, stream=None):
@@ -1197,20 +1217,10 @@ def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, st
     -> {"mean", "var", "mean_lo", "var_lo": [M, C, H, W], "info": [M, 4] (ENSEMBLE_INFO), "count": T} and, with a label,
     "curve": [M, K] (curve[m][n - 1]: mse of the mean of the first n paths) and "final_mse": [M] (the returned mean's).
     No host read; the workspace is cached per shape and serves one stream at a time."""
-    x = f32c(x, "particles")
-    if x.dim() != 4:
-        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
-    n, images = int(x.shape[0]), int(images)
-    if images < 1 or n < 1 or n % images:
-        raise ValueError(f"{n} particles do not split into {images} images")
-    k, d = n // images, int(x[0].numel())
+    x, n, k, d, images = _particle_set(x, images)
     shape = (images,) + tuple(x.shape[1:])
     if label is not None:
-        label = _label_rows(label, x)
-        if label.shape[0] == 1 and images > 1:
-            label = label.expand(shape).contiguous()
-        if label.shape[0] != images:
-            raise ValueError(f"{label.shape[0]} labels given for {images} images")
+        label = _label_rows(label, x, images)
     e = None
     if neg_log_weights is not None:
         if prior is not None:
@@ -1238,13 +1248,7 @@ def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, st
             (torch.zeros_like(mean), torch.zeros_like(var))
     else:
         mean, var, mean_lo, var_lo = new(), new(), new(), new()
-    key = (x.device, n, d, images)
-    ws = _ensemble_ws.get(key)
-    if ws is None:
-        need = lib().dpsx_ensemble_workspace_bytes(n, d, images)
-        if need < 0:
-            check(int(need), "dpsx_ensemble_workspace_bytes")
-        ws = _ensemble_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    ws = _workspace("dpsx_ensemble_workspace_bytes", x.device, n, d, images)
     curve = torch.empty((images, k + 1), dtype=torch.float32, device=x.device) if label is not None else None
     info = torch.empty((images, 4), dtype=torch.float32, device=x.device)
     check(lib().dpsx_ensemble_ex_f32(ptr(x), ptr(label), ptr(e), count0, ptr(mean), ptr(var), ptr(mean_lo), ptr(var_lo),
@@ -1260,7 +1264,6 @@ def ensemble_stats(x, images=1, label=None, neg_log_weights=None, prior=None, st
 QUANTILE_MAX_K = 512     # particles per image (DPSX_EUNSUPPORTED above)
 QUANTILE_MAX_Q = 8       # probabilities per call
 QUANTILE_INFO = ("crps", "width", "invalid", "count")    # the columns of info [M, 4]
-_quantile_ws = {}        # (device, n, d, images) -> the call's workspace, as _metrics_ws
 
 
 def quantile_probs(probs):
@@ -1285,33 +1288,16 @@ def order_stats(x, images=1, probs=(0.05, 0.5, 0.95), label=None, stream=None):
     the elements whose label exceeds exactly r particles; bin K + 1: a NaN in the label or a particle) and "crps": [M].
     An element with a NaN particle is NaN in all q maps.  The library's refusals are raised as ValueError before any
     launch.  No host read; the workspace is cached per shape and serves one stream at a time."""
-    x = f32c(x, "particles")
-    if x.dim() != 4:
-        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
-    n, images = int(x.shape[0]), int(images)
-    if images < 1 or n < 1 or n % images:
-        raise ValueError(f"{n} particles do not split into {images} images")
-    k, d = n // images, int(x[0].numel())
+    x, n, k, d, images = _particle_set(x, images)
     if k > QUANTILE_MAX_K:
         raise ValueError(f"order statistics take at most {QUANTILE_MAX_K} particles per image (got {k})")
     if d < 1 or images > 65535 or d >= 2 ** 31:
         raise ValueError(f"order statistics take 1 <= C H W < 2^31 and at most 65535 images (got {d}, {images})")
     p = quantile_probs(probs)
     q = len(p)
-    shape = (images,) + tuple(x.shape[1:])
     if label is not None:
-        label = _label_rows(label, x)
-        if label.shape[0] == 1 and images > 1:
-            label = label.expand(shape).contiguous()
-        if label.shape[0] != images:
-            raise ValueError(f"{label.shape[0]} labels given for {images} images")
-    key = (x.device, n, d, images)
-    ws = _quantile_ws.get(key)
-    if ws is None:
-        need = lib().dpsx_quantiles_workspace_bytes(n, d, images)
-        if need < 0:
-            check(int(need), "dpsx_quantiles_workspace_bytes")
-        ws = _quantile_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+        label = _label_rows(label, x, images)
+    ws = _workspace("dpsx_quantiles_workspace_bytes", x.device, n, d, images)
     quant = torch.empty((images, q) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
     hist = torch.empty((images, k + 2), dtype=torch.int32, device=x.device) if label is not None else None
     info = torch.empty((images, 4), dtype=torch.float32, device=x.device)
@@ -1327,7 +1313,6 @@ def order_stats(x, images=1, probs=(0.05, 0.5, 0.95), label=None, stream=None):
 PCA_MAX_K = 128          # particles per image (DPSX_EUNSUPPORTED above): the eigensolver's matrices live in LDS
 PCA_MAX_Q = 8            # components per call
 PCA_INFO = ("trace", "rank", "sweeps", "count")          # the columns of info [M, 4]
-_pca_ws = {}             # (device, n, d, images) -> the call's workspace, as _metrics_ws
 
 
 def pca_components(value, what="components"):
@@ -1347,25 +1332,13 @@ def particle_pca(x, images=1, components=4, want_d2=False, stream=None):
     is all zero with rank 0 (its `explained` is 0 / 0 = NaN); an image with a NaN / Inf in it is NaN with rank -1.  The
     library's refusals are raised as ValueError before any launch.  No host read; the workspace is cached per shape and
     serves one stream at a time."""
-    x = f32c(x, "particles")
-    if x.dim() != 4:
-        raise ValueError(f"particles must be [N, C, H, W] (got {tuple(x.shape)})")
-    n, images = int(x.shape[0]), int(images)
-    if images < 1 or n < 1 or n % images:
-        raise ValueError(f"{n} particles do not split into {images} images")
-    k, d = n // images, int(x[0].numel())
+    x, n, k, d, images = _particle_set(x, images)
     if k > PCA_MAX_K:
         raise ValueError(f"principal components take at most {PCA_MAX_K} particles per image (got {k})")
     if d < 1 or images > 65535 or d >= 2 ** 31:
         raise ValueError(f"principal components take 1 <= C H W < 2^31 and at most 65535 images (got {d}, {images})")
     q = pca_components(components)
-    key = (x.device, n, d, images)
-    ws = _pca_ws.get(key)
-    if ws is None:
-        need = lib().dpsx_pca_workspace_bytes(n, d, images)
-        if need < 0:
-            check(int(need), "dpsx_pca_workspace_bytes")
-        ws = _pca_ws[key] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=x.device)
+    ws = _workspace("dpsx_pca_workspace_bytes", x.device, n, d, images)
     f = dict(dtype=torch.float32, device=x.device)
     dirs = torch.empty((images, q) + tuple(x.shape[1:]), **f)
     evals, coords, info = torch.empty((images, q), **f), torch.empty((images, k, q), **f), torch.empty((images, 4), **f)

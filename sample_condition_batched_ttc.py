@@ -369,15 +369,31 @@ def path_diversity(sample, images=1):
     return torch.sqrt(info[:, 2:4] / sample[0].numel()).cpu().numpy()
 
 
+def refuse_particle_set(flag, world, args=None, sampler_name=None, noun=None, max_k=None):
+    """what the flags that analyse an image's particles refuse alike (one-line messages): more than one rank and, for a
+    flag that needs the whole set in one call (noun: what it computes, max_k: the most paths it takes), sampler search_ddpm,
+    more than one particle group per image and more than max_k paths"""
+    if world > 1:
+        raise SystemExit(f"{flag} runs on one rank only: the particles of an image are not gathered between "
+                         f"ranks (WORLD_SIZE={world})")
+    if noun is None:
+        return
+    if sampler_name == 'search_ddpm':
+        raise SystemExit(f"{flag} needs a particle set: sampler search_ddpm keeps one state per image")
+    if args.n_paths != args.batch_size:
+        raise SystemExit(f"{flag} takes one particle group per image: the {noun} of two groups do not "
+                         f"merge (n_paths {args.n_paths}, batch_size {args.batch_size})")
+    if args.batch_size > max_k:
+        raise SystemExit(f"{flag} takes at most {max_k} paths per image (--batch_size {args.batch_size})")
+
+
 def check_posterior_summary(args, sampler_name, world=1):
     """--posterior_summary / --posterior_weights: reject what they do not support, before any GPU work (one-line message)"""
     if not args.posterior_summary:
         if args.posterior_weights != 'uniform':
             raise SystemExit(f"--posterior_weights {args.posterior_weights} needs --posterior_summary")
         return
-    if world > 1:
-        raise SystemExit("--posterior_summary runs on one rank only: the particles of an image are not gathered between "
-                         f"ranks (WORLD_SIZE={world})")
+    refuse_particle_set("--posterior_summary", world)
     if args.batch_size > 4096:
         raise SystemExit(f"--posterior_summary takes at most 4096 paths per particle group (--batch_size {args.batch_size})")
     if args.posterior_weights == 'smc':
@@ -432,16 +448,7 @@ def check_posterior_quantiles(args, sampler_name, world=1):
         raise SystemExit(f"--posterior_quantiles takes between 1 and 8 percentages (got {len(pct)})")
     if any(not (0.0 <= v <= 100.0) for v in pct):
         raise SystemExit(f"--posterior_quantiles takes percentages in [0, 100] (got {args.posterior_quantiles})")
-    if world > 1:
-        raise SystemExit("--posterior_quantiles runs on one rank only: the particles of an image are not gathered between "
-                         f"ranks (WORLD_SIZE={world})")
-    if sampler_name == 'search_ddpm':
-        raise SystemExit("--posterior_quantiles needs a particle set: sampler search_ddpm keeps one state per image")
-    if args.n_paths != args.batch_size:
-        raise SystemExit("--posterior_quantiles takes one particle group per image: the order statistics of two groups do not "
-                         f"merge (n_paths {args.n_paths}, batch_size {args.batch_size})")
-    if args.batch_size > 512:
-        raise SystemExit(f"--posterior_quantiles takes at most 512 paths per image (--batch_size {args.batch_size})")
+    refuse_particle_set("--posterior_quantiles", world, args, sampler_name, "order statistics", 512)
 
 
 class PosteriorQuantiles:
@@ -475,16 +482,7 @@ def check_posterior_pca(args, sampler_name, world=1):
         return
     if not 1 <= args.posterior_pca <= 8:
         raise SystemExit(f"--posterior_pca takes between 1 and 8 components (got {args.posterior_pca})")
-    if world > 1:
-        raise SystemExit("--posterior_pca runs on one rank only: the particles of an image are not gathered between "
-                         f"ranks (WORLD_SIZE={world})")
-    if sampler_name == 'search_ddpm':
-        raise SystemExit("--posterior_pca needs a particle set: sampler search_ddpm keeps one state per image")
-    if args.n_paths != args.batch_size:
-        raise SystemExit("--posterior_pca takes one particle group per image: the components of two groups do not "
-                         f"merge (n_paths {args.n_paths}, batch_size {args.batch_size})")
-    if args.batch_size > 128:
-        raise SystemExit(f"--posterior_pca takes at most 128 paths per image (--batch_size {args.batch_size})")
+    refuse_particle_set("--posterior_pca", world, args, sampler_name, "components", 128)
 
 
 class PosteriorPca:

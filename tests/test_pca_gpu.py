@@ -272,6 +272,46 @@ def test_refusals_come_as_value_errors_before_any_launch():
         kernels.particle_pca(torch.zeros(6, 16, device=DEV))
 
 
+def test_the_workspace_cache_keeps_the_families_apart():
+    """particle_pca and pairwise_sqdist on the same six particles: the same d2 bits (include/dpsx.h), from two workspaces --
+    the one cache keys on the size query's name, not on the shape alone"""
+    from dps_ttc_amd import kernels
+    x = _dev(P.make_set("planted", 1, 6, (3, 16, 16)))
+    mine = lambda query: {k: v for k, v in kernels._workspaces.items() if k[0] == query and k[2:] == (6, 768, 1)}
+    got = _run(x, 1, want_d2=True)
+    d2 = kernels.pairwise_sqdist(x, images=1)
+    torch.cuda.synchronize()
+    assert _same_bits(got["d2"], d2)
+    pca_ws, rep_ws = mine("dpsx_pca_workspace_bytes"), mine("dpsx_repulse_workspace_bytes")
+    assert len(pca_ws) == len(rep_ws) == 1
+    (a,), (b,) = pca_ws.values(), rep_ws.values()
+    assert a is not b and a.data_ptr() != b.data_ptr() and a.numel() == 1536 and b.numel() == 1280
+    again = _run(x, 1, want_d2=True)                                     # a hit: the same tensor, the same bits
+    assert [id(v) for v in mine("dpsx_pca_workspace_bytes").values()] == [id(a)]
+    assert all(_same_bits(again[k], got[k]) for k in ("d2", "dirs", "evals", "coords", "info"))
+
+
+def test_the_labels_of_the_images():
+    """kernels._label_rows(label, x, images): one label serves every image (expanded), otherwise one per image"""
+    from dps_ttc_amd import kernels
+    x = torch.zeros(6, 1, 4, 4, device=DEV)
+    one, three = torch.rand(1, 4, 4, device=DEV), torch.rand(3, 1, 4, 4, device=DEV)
+    got = kernels._label_rows(one, x, 3)
+    assert got.shape == (3, 1, 4, 4) and got.is_contiguous() and all(torch.equal(got[i], one) for i in range(3))
+    assert torch.equal(kernels._label_rows(three, x, 3), three) and kernels._label_rows(one, x, 1).shape == (1, 1, 4, 4)
+    assert kernels._label_rows(three, x).shape == (3, 1, 4, 4)            # without `images`: M | N is all that is asked
+    with pytest.raises(ValueError, match=r"^3 labels given for 2 images$"):
+        kernels._label_rows(three, x, 2)
+    with pytest.raises(ValueError, match=r"^3 labels given for 1 images$"):
+        kernels._label_rows(three, x, 1)
+    with pytest.raises(ValueError, match=r"^4 labels do not divide 6 particles$"):
+        kernels._label_rows(torch.zeros(4, 1, 4, 4, device=DEV), x, 4)
+    with pytest.raises(ValueError, match="does not match particles"):
+        kernels._label_rows(torch.zeros(1, 4, 5, device=DEV), x, 3)
+    with pytest.raises(ValueError, match="for particles on"):
+        kernels._label_rows(torch.zeros(1, 4, 4, device=DEV), x.cpu(), 3)
+
+
 def test_front_ends():
     from dps_ttc_amd import kernels, metrics
     m, k, shape = 2, 9, (3, 32, 32)
