@@ -25,6 +25,7 @@ all ranks' particles at every step and `sampler: ttc_ddim` resamples over all of
 import argparse
 import os
 from functools import partial
+from typing import NamedTuple
 
 # read by the HSA runtime when it initialises (first HIP call): must be in the environment before that, i.e. before anything
 # below touches the GPU -- the host driver only supports dmabuf IPC, RCCL fails with hipIpcGetMemHandle otherwise
@@ -37,7 +38,7 @@ import yaml  # noqa: E402
 
 from dps_ttc_amd import distributed as dd  # noqa: E402
 from dps_ttc_amd.condition_methods import get_conditioning_method  # noqa: E402
-from dps_ttc_amd.data import get_dataloader, get_dataset, to_minus1_1  # noqa: E402
+from dps_ttc_amd.data import get_dataset, to_minus1_1  # noqa: E402
 from dps_ttc_amd.gaussian_diffusion import create_sampler  # noqa: E402
 from dps_ttc_amd.img_utils import clear_color, mask_generator  # noqa: E402
 from dps_ttc_amd.measurements import get_noise, get_operator  # noqa: E402
@@ -198,6 +199,26 @@ def save_path_metrics(out_path, fname, distances, psnr, ssim):
         np.save(os.path.join(out_path, f'{fname}_best_of_n_{name}.npy'), best_of_n_curve(distances, v))
 
 
+class PathMetrics:
+    """--path_metrics device: PSNR and SSIM of a particle group in one device call and one copy with the group's distances
+    (`host` [3, B K]: rows psnr, ssim, distance of the last group, image-major: what its per-path log lines print) and, at
+    the end, save_path_metrics per image"""
+
+    def __init__(self, refs):
+        self.refs, self.host, self.groups = refs, None, []
+
+    def add(self, sample, sampler=None, dist_g=None):
+        B = self.refs.shape[0]
+        pm = pathwise_metrics(self.refs, sample, n_images=B)
+        self.host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
+        self.groups.append(self.host.reshape(3, B, -1))
+
+    def save(self, out_path, fnames):
+        rows = np.concatenate(self.groups, axis=2)        # [groups][3, B, K] -> [3, B, n_paths]: group-major, the path order
+        for b, fname in enumerate(fnames):
+            save_path_metrics(out_path, fname, rows[2, b], rows[0, b], rows[1, b])
+
+
 def start_particles(args, sampler, g, shape, device, per_image=0):
     """x_start of particle group g.  --noise_draw device: the sampler is told the group's first path id (global over the
     ranks: the groups shard contiguously) and x_start is the tag-1 draw of those paths; else torch.randn"""
@@ -237,6 +258,8 @@ def check_resample_scheme(args, sampler_name=None):
     """--resample_scheme / --resample_ess / --ttc_resample_every: reject bad combinations before any GPU work (one-line
     message); sampler_name: also reject them for a sampler whose loop never resamples, instead of ignoring them.
     smc_ddpm takes the three flags too and always draws on the device: --resample_draw need not be given for it"""
+    if (args.resample_scheme, args.resample_ess, args.ttc_resample_every) == ('multinomial', None, 10):
+        return
     if args.ttc_resample_every < 1:
         raise SystemExit(f"--ttc_resample_every must be at least 1 (got {args.ttc_resample_every})")
     if args.resample_ess is not None and not 0.0 <= args.resample_ess <= 1.0:
@@ -264,6 +287,8 @@ def smc_flags(args):
 def check_smc(args, sampler_name, world=1):
     """--smc_*: options of sampler smc_ddpm; reject them for another sampler, and what that loop does not support, before any
     GPU work (one-line message)"""
+    if not smc_flags(args) and sampler_name != 'smc_ddpm':
+        return
     for flag, value in smc_flags(args):
         if sampler_name != 'smc_ddpm':
             raise SystemExit(f"{flag} {value} is an option of sampler smc_ddpm (the diffusion config names {sampler_name})")
@@ -295,6 +320,8 @@ def check_solver(args, sampler_name, method_name, world=1, eta=None):
     """--solver_order / --guidance_gain: reject what the sampling loops would refuse, before any GPU work (one-line
     message).  eta: the diffusion config's (None: the sampler's default 0)"""
     order, gain = args.solver_order, args.guidance_gain
+    if order is None and gain is None:
+        return
     if order is not None and sampler_name not in ('ddim', 'ttc_ddim'):
         raise SystemExit(f"--solver_order {order} is an option of samplers ddim and ttc_ddim (the diffusion config names "
                          f"{sampler_name})")
@@ -339,6 +366,8 @@ def repulsion_flags(args):
 def check_repulsion(args, sampler_name, world=1):
     """--repulsion_* and --path_diversity: reject what the loops refuse, before any GPU work (one-line message)"""
     import math
+    if not repulsion_flags(args) and not args.path_diversity:
+        return
     for flag, value in repulsion_flags(args):
         if not math.isfinite(value) or value < 0.0:
             raise SystemExit(f"{flag} must be finite and not negative (got {value})")
@@ -361,12 +390,21 @@ def check_repulsion(args, sampler_name, world=1):
                          f"image's particles live on several ranks (WORLD_SIZE={world})")
 
 
-def path_diversity(sample, images=1):
-    """--path_diversity: [images, 2] (mean, min) RMS per-element distance between the particles of every image of a group's
-    final samples, one device call (kernels.pairwise_sqdist) and one copy"""
-    from dps_ttc_amd import kernels
-    _, info = kernels.pairwise_sqdist(sample.detach(), images=images, want_info=True)
-    return torch.sqrt(info[:, 2:4] / sample[0].numel()).cpu().numpy()
+class PathDiversity:
+    """--path_diversity: per particle group the (mean, min) RMS per-element distance between the final samples of every
+    image, one device call (kernels.pairwise_sqdist) and one copy; at the end {fname}_path_diversity.npy [groups, 2]"""
+
+    def __init__(self, n_images):
+        self.n_images, self.groups = n_images, []
+
+    def add(self, sample, sampler=None, dist_g=None):
+        from dps_ttc_amd import kernels
+        _, info = kernels.pairwise_sqdist(sample.detach(), images=self.n_images, want_info=True)
+        self.groups.append(torch.sqrt(info[:, 2:4] / sample[0].numel()).cpu().numpy())      # [B, 2]
+
+    def save(self, out_path, fnames):
+        for b, fname in enumerate(fnames):       # [groups][B, 2] -> image b's [groups, 2]
+            np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack([v[b] for v in self.groups]))
 
 
 def refuse_particle_set(flag, world, args=None, sampler_name=None, noun=None, max_k=None):
@@ -412,7 +450,7 @@ class PosteriorSummary:
     def __init__(self, refs, weights='uniform'):
         self.refs, self.weights, self.last, self.curves = refs, weights, None, []
 
-    def add(self, sample, sampler=None):
+    def add(self, sample, sampler=None, dist_g=None):
         from dps_ttc_amd.metrics import posterior_summary
         e = sampler.last_neg_log_weights if self.weights == 'smc' else None
         self.last = posterior_summary(self.refs, sample, n_images=self.refs.shape[0], neg_log_weights=e, prior=self.last)
@@ -458,7 +496,7 @@ class PosteriorQuantiles:
     def __init__(self, refs, text):
         self.refs, self.pct, self.last = refs, quantile_percentages(text), None
 
-    def add(self, sample):
+    def add(self, sample, sampler=None, dist_g=None):
         from dps_ttc_amd.metrics import posterior_quantiles
         self.last = posterior_quantiles(self.refs, sample, n_images=self.refs.shape[0], probs=[v / 100.0 for v in self.pct])
 
@@ -492,7 +530,7 @@ class PosteriorPca:
     def __init__(self, n_images, components):
         self.n_images, self.q, self.last, self.panels = n_images, components, None, None
 
-    def add(self, sample):
+    def add(self, sample, sampler=None, dist_g=None):
         from dps_ttc_amd import kernels
         from dps_ttc_amd.metrics import pc_panels, posterior_pca
         self.last = posterior_pca(sample, n_images=self.n_images, components=self.q)
@@ -514,33 +552,33 @@ class PosteriorPca:
                            clear_color(panel[b:b + 1, j]))
 
 
+def preflight(args, world):
+    """every refusal that needs no GPU, in one fixed order: a command line that is wrong in two ways gets the message of
+    the first check it fails; each check returns at once when its flags are not given.  -> (diffusion config, task
+    config), each file read once, None where its path is not given: the checks that need no sampler or method name
+    still run"""
+    diffusion_config = load_yaml(args.diffusion_config) if args.diffusion_config else None
+    task_config = load_yaml(args.task_config) if args.task_config else None
+    sampler_name = diffusion_config['sampler'] if args.diffusion_config else None
+    method_name = task_config['conditioning']['method'] if args.task_config else None
+    check_resample_scheme(args, sampler_name)
+    check_smc(args, sampler_name, world)
+    check_dsg(args, method_name)
+    check_solver(args, sampler_name, method_name, world, diffusion_config.get('eta') if args.diffusion_config else None)
+    check_beam_width(args, sampler_name, world)
+    check_repulsion(args, sampler_name, world)
+    check_images_per_batch(args, sampler_name, world)
+    check_posterior_summary(args, sampler_name, world)
+    check_posterior_quantiles(args, sampler_name, world)
+    check_posterior_pca(args, sampler_name, world)
+    return diffusion_config, task_config
+
+
 def main(argv=None):
     args = parse_args(argv)
     logger = get_logger()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    # the sampler's name decides what the resampling flags mean; without a config the checks that need no name still run
-    sampler_name = load_yaml(args.diffusion_config)['sampler'] if args.diffusion_config else None
-    resampling = (args.resample_scheme, args.resample_ess, args.ttc_resample_every) != ('multinomial', None, 10)
-    check_resample_scheme(args, sampler_name if resampling else None)
-    if smc_flags(args) or sampler_name == 'smc_ddpm':
-        check_smc(args, sampler_name, world)
-    if args.dsg_guidance_rate is not None:
-        check_dsg(args, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None)
-    if args.solver_order is not None or args.guidance_gain is not None:
-        check_solver(args, sampler_name, load_yaml(args.task_config)['conditioning']['method'] if args.task_config else None,
-                     world, load_yaml(args.diffusion_config).get('eta') if args.diffusion_config else None)
-    if args.beam_width != 1:
-        check_beam_width(args, load_yaml(args.diffusion_config)['sampler'], world)
-    if repulsion_flags(args) or args.path_diversity:
-        check_repulsion(args, sampler_name, world)
-    if args.images_per_batch != 1:
-        check_images_per_batch(args, load_yaml(args.diffusion_config)['sampler'], world)
-    if args.posterior_summary or args.posterior_weights != 'uniform':
-        check_posterior_summary(args, sampler_name, world)
-    if args.posterior_quantiles is not None:
-        check_posterior_quantiles(args, sampler_name, world)
-    if args.posterior_pca is not None:
-        check_posterior_pca(args, sampler_name, world)
+    diffusion_config, task_config = preflight(args, world)
     if world > 1:
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", 0)) % max(torch.cuda.device_count(), 1)
@@ -558,8 +596,6 @@ def main(argv=None):
     logger.info(f"Device set to {device}.")
 
     model_config = load_yaml(args.model_config)
-    diffusion_config = load_yaml(args.diffusion_config)
-    task_config = load_yaml(args.task_config)
     if args.timestep_respacing is not None:
         diffusion_config['timestep_respacing'] = args.timestep_respacing
     if args.solver_order is not None:            # check_solver: the sampler is a ddim one
@@ -635,230 +671,171 @@ def main(argv=None):
     for img_dir in ['input', 'recon_paths', 'label', 'best_of_n']:
         os.makedirs(os.path.join(out_path, img_dir), exist_ok=True)
 
-    data_config = task_config['data']
-    dataset = get_dataset(**data_config, transforms=to_minus1_1)
+    dataset = get_dataset(**task_config['data'], transforms=to_minus1_1)
     picks = [int(i) for i in args.ref_image_idxs.split(',')]
-    subset = torch.utils.data.Subset(dataset, [min(i, len(dataset) - 1) for i in picks])
-    loader = get_dataloader(subset, batch_size=1, num_workers=0, train=False)
-
     mask_gen = mask_generator(**measure_config['mask_opt']) if op_name == 'inpainting' else None
     if op_name == 'motion_blur' and rank == 0:
         imsave(os.path.join(out_path, f'kernel_{str(args.kernel_idx).zfill(5)}.png'), clear_color(operator.get_kernel()))
-    if args.images_per_batch > 1:
-        for batch in image_batches(picks, args.images_per_batch):
-            run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn,
-                            mask_gen, groups, diffusion_config['sampler'], out_path, sampler=sampler)
-        return
-
-    # particle groups shard contiguously over the ranks: the rank-major order of the gathered scores is the path order
-    g_lo, g_hi = dd.shard_range(groups, rank, world)
-    my_groups = range(g_lo, g_hi)
-    counts = [c * args.batch_size for c in dd.shard_counts(groups, world)]
-    for img_idx, ref_img in enumerate(loader):
-        logger.info(f"Inference for image {args.start_idx + img_idx}")
-        fname = str(picks[img_idx]).zfill(5)
-        ref_img = ref_img.to(device)
-        os.makedirs(os.path.join(out_path, 'recon_paths', fname), exist_ok=True)
-        os.makedirs(os.path.join(out_path, 'recon_paths_y', fname), exist_ok=True)
-
-        if embedder is not None and hasattr(cond_method, 'guid_image_emb'):
-            guid = ref_img
-            if args.guid_image is not None:
-                from PIL import Image
-                guid = to_minus1_1(Image.open(args.guid_image).convert('RGB')).unsqueeze(0).to(device)
-            with torch.no_grad():
-                cond_method.guid_image_emb = embedder(guid).unsqueeze(0)        # [1, n_guid = 1, D]
-        fkw = {}
-        this_sample_fn = sample_fn
-        if op_name == 'inpainting':
-            mask = mask_gen(ref_img)[:, 0, :, :].unsqueeze(dim=0).contiguous()
-            fkw = {'mask': mask}
-            this_sample_fn = partial(sample_fn, measurement_cond_fn=partial(cond_method.conditioning, mask=mask, l1=args.l1),
-                                     mask=mask)
-        if world > 1:       # every rank must see the same measurement: rank 0 draws the noise
-            gen_state = torch.random.get_rng_state()
-        with torch.no_grad():
-            y = operator.forward(ref_img, **fkw)
-            y_n = noiser(y).contiguous()
-        if world > 1:
-            import torch.distributed as dist
-            dist.broadcast(y_n, src=0)
-            torch.random.set_rng_state(gen_state)
-        C, H, W = ref_img.shape[1:]
-        if rank == 0:
-            imsave(os.path.join(out_path, 'input', fname + '.png'), clear_color(y_n))
-            imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(ref_img))
-
-        distances, finals = [], []
-        device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
-        diversity = []
-        posterior = PosteriorSummary(ref_img, args.posterior_weights) if args.posterior_summary else None
-        quantiles = PosteriorQuantiles(ref_img, args.posterior_quantiles) if args.posterior_quantiles is not None else None
-        pca = PosteriorPca(1, args.posterior_pca) if args.posterior_pca is not None else None
-        for g in my_groups:
-            x_start = start_particles(args, sampler, g, (args.batch_size, C, H, W), device)
-            sample = this_sample_fn(x_start=x_start, measurement=y_n, record=False, save_root=out_path)
-            if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances) (reference :707)
-                sample = sample[0]
-            with torch.no_grad():
-                y_space = operator.forward(sample, **fkw)                      # for the PNGs
-                handle = operator.hip_handle_for(fkw['mask']) if op_name == 'inpainting' else operator.hip_handle(sample)
-                dist_g = handle.score(sample, y_n)                             # ||y - A(x_p)||_2 per particle (HIP)
-            distances.append(dist_g)
-            finals.append(sample)
-            if args.path_diversity:
-                diversity.append(path_diversity(sample)[0])
-            if posterior is not None:
-                posterior.add(sample, sampler)
-            if quantiles is not None:  # one group (check_posterior_quantiles)
-                quantiles.add(sample)
-            if pca is not None:        # one group (check_posterior_pca)
-                pca.add(sample)
-            if device_metrics:        # one device call and one copy for the group: rows psnr, ssim, distance
-                pm = pathwise_metrics(ref_img, sample)
-                pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
-                path_psnr.append(pm_host[0])
-                path_ssim.append(pm_host[1])
-            for i in range(len(sample)):
-                path_idx = args.path_start_idx + g * args.batch_size + i
-                if device_metrics:
-                    logger.info(f"Path#{path_idx + 1} | Method:{diffusion_config['sampler']} / PSNR: {pm_host[0, i]:.4f} / "
-                                f"SSIM: {pm_host[1, i]:.4f} / distance: {pm_host[2, i]:.4f}")
-                else:
-                    psnr = compute_psnr(ref_img, sample[i].unsqueeze(0))
-                    logger.info(f"Path#{path_idx + 1} | Method:{diffusion_config['sampler']} / PSNR: {float(psnr):.4f} / "
-                                f"distance: {float(dist_g[i]):.4f}")
-                imsave(os.path.join(out_path, 'recon_paths', fname, f'path#{path_idx + 1}.png'), clear_color(sample[i].unsqueeze(0)))
-                imsave(os.path.join(out_path, 'recon_paths_y', fname, f'path#{path_idx + 1}_y_space.png'),
-                       clear_color(y_space[i].unsqueeze(0)))
-        # best-of-N over every particle of every rank: argmin of the final measurement distance.  Every rank enters
-        # (a rank without groups contributes an empty shard and still receives the winner).
-        scores_local = torch.cat(distances) if distances else torch.empty(0, device=device)
-        particles_local = torch.cat(finals) if finals else torch.empty((0, C, H, W), device=device)
-        winner, best, all_d = dd.global_best_of_n(scores_local, particles_local, counts)
-        if rank == 0:
-            logger.info(f"best-of-{all_d.numel()} = path#{args.path_start_idx + best + 1} | PSNR: "
-                        f"{float(compute_psnr(ref_img, winner)):.4f} | distance: {float(all_d[best]):.4f}")
-            imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winner))
-            np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), all_d.cpu().numpy())
-            if device_metrics:       # one rank (parse_args): the groups' order is the path order of all_d
-                save_path_metrics(out_path, fname, all_d.cpu().numpy(), np.concatenate(path_psnr),
-                                  np.concatenate(path_ssim))
-            if args.path_diversity:  # one rank (parse_args): [groups, 2]
-                np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack(diversity))
-            if posterior is not None:  # one rank (check_posterior_summary)
-                posterior.save(out_path, [fname])
-            if quantiles is not None:  # one rank (check_posterior_quantiles)
-                quantiles.save(out_path, [fname])
-            if pca is not None:        # one rank (check_posterior_pca)
-                pca.save(out_path, [fname])
+    run = Run(args, logger, device, rank, world, dataset, operator, noiser, op_name, cond_method, embedder, sample_fn,
+              mask_gen, sampler, diffusion_config['sampler'], groups, out_path)
+    for n, batch in enumerate(image_batches(picks, args.images_per_batch)):
+        run_images(run, batch, n)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
 
 
-def run_image_batch(args, logger, device, dataset, batch, operator, noiser, op_name, cond_method, sample_fn, mask_gen,
-                    groups, sampler_name, out_path, sampler=None):
-    """--images_per_batch: the B = len(batch) images of `batch` as one multi-image batch per particle group --
-    B x batch_size particles, image-major (particles [b K, (b + 1) K) belong to image b), y [B, ...] -- and the
-    per-image best-of-N (one argmin per image over its n_paths distances, on the device)."""
-    from dps_ttc_amd import kernels
+class Run(NamedTuple):
+    """what main() built once and every batch of images runs with"""
+    args: argparse.Namespace
+    logger: object
+    device: torch.device
+    rank: int
+    world: int
+    dataset: object
+    operator: object
+    noiser: object
+    op_name: str
+    cond_method: object
+    embedder: object
+    sample_fn: object
+    mask_gen: object
+    sampler: object
+    sampler_name: str
+    groups: int
+    out_path: str
+
+
+def select_winners(run, distances, finals, refs):
+    """best-of-N per image: argmin of the final measurement distance over every path of the image.  distances / finals:
+    this rank's groups' [B K] scores and [B K, C, H, W] particles (image-major) -> per image (winner [1, C, H, W], path
+    index, the image's distances in path order on the host)"""
+    B, K = refs.shape[0], run.args.batch_size
+    if run.args.images_per_batch > 1:
+        # the [groups, B, K] distances in image-major path order, one segmented argmin, one gather
+        from dps_ttc_amd import kernels
+        n_paths = run.groups * K
+        d_img = torch.stack(distances).reshape(run.groups, B, K).transpose(0, 1).reshape(B * n_paths).contiguous()
+        best = kernels.argmin_seg(d_img, B)                                   # [B]: b * n_paths + path
+        path = best - torch.arange(B, device=best.device) * n_paths
+        src = (path // K) * (B * K) + torch.arange(B, device=best.device) * K + path % K    # index into the groups' concat
+        winners = kernels.gather(torch.cat(finals).detach(), src, validate=False)
+        d_host, path_host = d_img.reshape(B, n_paths).cpu().numpy(), path.cpu().numpy()
+        return [(winners[b:b + 1], int(path_host[b]), d_host[b]) for b in range(B)]
+    # over every particle of every rank.  The groups shard contiguously: the rank-major order of the gathered scores is the
+    # path order.  Every rank enters (a rank without groups contributes an empty shard and still receives the winner).
+    counts = [c * K for c in dd.shard_counts(run.groups, run.world)]
+    scores_local = torch.cat(distances) if distances else torch.empty(0, device=run.device)
+    particles_local = torch.cat(finals) if finals else torch.empty((0,) + refs.shape[1:], device=run.device)
+    winner, best, all_d = dd.global_best_of_n(scores_local, particles_local, counts)
+    return [(winner, best, all_d.cpu().numpy())]
+
+
+def run_images(run, batch, n=0):
+    """The B = len(batch) reference images of `batch` (the n-th batch of the run) as one multi-image batch per particle
+    group -- B x batch_size particles, image-major (particles [b K, (b + 1) K) belong to image b), y [B, ...] -- their
+    analyses, the per-image best-of-N and the saves.  The default mode is batches of one image."""
+    args, logger, device, operator, op_name, out_path = run.args, run.logger, run.device, run.operator, run.op_name, run.out_path
     B, K = len(batch), args.batch_size
     fnames = [str(i).zfill(5) for i in batch]
-    logger.info(f"Inference for images {', '.join(fnames)} ({B} x {K} particles per call)")
-    refs = torch.stack([dataset[min(i, len(dataset) - 1)] for i in batch]).to(device)
+    # what differs between the modes: --images_per_batch > 1 tells the sampler and the x_start draw how many images the
+    # batch holds (n_images = 1 would take search_ddpm through its segmented entry points) and names the image on every log
+    # line; only the default mode runs on several ranks (the groups sharded over them, rank 0's measurement, rank 0 writes),
+    # with semantic guidance, and selects over all ranks (select_winners)
+    multi = args.images_per_batch > 1
+    sample_kw, start_kw = ({'n_images': B}, {'per_image': K}) if multi else ({}, {})
+    tags = [(f"Image {f} ", f"Image {f}: ") for f in fnames] if multi else [("", "")]
+    if multi:
+        logger.info(f"Inference for images {', '.join(fnames)} ({B} x {K} particles per call)")
+    else:
+        logger.info(f"Inference for image {args.start_idx + n}")
+    my_groups = range(*dd.shard_range(run.groups, run.rank, run.world))
+
+    refs = torch.stack([run.dataset[min(i, len(run.dataset) - 1)] for i in batch]).to(device)
     C, H, W = refs.shape[1:]
+    if run.embedder is not None and hasattr(run.cond_method, 'guid_image_emb'):      # B = 1 (check_images_per_batch)
+        guid = refs
+        if args.guid_image is not None:
+            from PIL import Image
+            guid = to_minus1_1(Image.open(args.guid_image).convert('RGB')).unsqueeze(0).to(device)
+        with torch.no_grad():
+            run.cond_method.guid_image_emb = run.embedder(guid).unsqueeze(0)        # [1, n_guid = 1, D]
     masks, ys = [], []
-    with torch.no_grad():
-        for b in range(B):             # per image in pick order: its mask, then its noisy measurement
-            fkw = {}
-            if op_name == 'inpainting':
-                masks.append(mask_gen(refs[b:b + 1])[:, 0, :, :].unsqueeze(dim=0).contiguous())
-                fkw = {'mask': masks[-1]}
-            ys.append(noiser(operator.forward(refs[b:b + 1], **fkw)))
+    for b in range(B):             # per image in pick order: its mask, then its noisy measurement
+        fkw = {}
+        if op_name == 'inpainting':
+            masks.append(run.mask_gen(refs[b:b + 1])[:, 0, :, :].unsqueeze(dim=0).contiguous())
+            fkw = {'mask': masks[-1]}
+        if run.world > 1:       # every rank must see the same measurement: rank 0 draws the noise
+            gen_state = torch.random.get_rng_state()
+        with torch.no_grad():
+            ys.append(run.noiser(operator.forward(refs[b:b + 1], **fkw)).contiguous())
+        if run.world > 1:
+            import torch.distributed as dist
+            dist.broadcast(ys[-1], src=0)
+            torch.random.set_rng_state(gen_state)
     y = torch.cat(ys).contiguous()
-    fkw, this_sample_fn = {}, sample_fn
+    fkw, sample_fn = {}, run.sample_fn
     if op_name == 'inpainting':
         mask = torch.cat(masks).contiguous()                     # [B, 1, H, W]: particle p uses mask p // K
         fkw = {'mask': mask}
-        this_sample_fn = partial(sample_fn, measurement_cond_fn=partial(cond_method.conditioning, mask=mask, l1=args.l1),
-                                 mask=mask)
+        sample_fn = partial(sample_fn, measurement_cond_fn=partial(run.cond_method.conditioning, mask=mask, l1=args.l1),
+                            mask=mask)
     for b, fname in enumerate(fnames):
         os.makedirs(os.path.join(out_path, 'recon_paths', fname), exist_ok=True)
         os.makedirs(os.path.join(out_path, 'recon_paths_y', fname), exist_ok=True)
-        imsave(os.path.join(out_path, 'input', fname + '.png'), clear_color(y[b:b + 1]))
-        imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(refs[b:b + 1]))
+        if run.rank == 0:
+            imsave(os.path.join(out_path, 'input', fname + '.png'), clear_color(y[b:b + 1]))
+            imsave(os.path.join(out_path, 'label', fname + '.png'), clear_color(refs[b:b + 1]))
 
+    # one rank for every analysis (parse_args, the checks); the order is the order of their device calls per group
+    metrics = PathMetrics(refs) if args.path_metrics == 'device' else None
+    outputs = [o for o in (PathDiversity(B) if args.path_diversity else None,
+                           PosteriorSummary(refs, args.posterior_weights) if args.posterior_summary else None,
+                           PosteriorQuantiles(refs, args.posterior_quantiles) if args.posterior_quantiles is not None else None,
+                           PosteriorPca(B, args.posterior_pca) if args.posterior_pca is not None else None,
+                           metrics) if o is not None]
     distances, finals = [], []
-    device_metrics, path_psnr, path_ssim = args.path_metrics == 'device', [], []
-    diversity = []
-    posterior = PosteriorSummary(refs, args.posterior_weights) if args.posterior_summary else None
-    quantiles = PosteriorQuantiles(refs, args.posterior_quantiles) if args.posterior_quantiles is not None else None
-    pca = PosteriorPca(B, args.posterior_pca) if args.posterior_pca is not None else None
-    for g in range(groups):
-        x_start = start_particles(args, sampler, g, (B * K, C, H, W), device, per_image=K)
-        sample = this_sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, n_images=B)
-        if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances)
+    for g in my_groups:
+        x_start = start_particles(args, run.sampler, g, (B * K, C, H, W), device, **start_kw)
+        sample = sample_fn(x_start=x_start, measurement=y, record=False, save_root=out_path, **sample_kw)
+        if isinstance(sample, tuple):       # ttc_ddim hands back (particles, distances) (reference :707)
             sample = sample[0]
         with torch.no_grad():
-            y_space = operator.forward(sample, **fkw)
+            y_space = operator.forward(sample, **fkw)                      # for the PNGs
             handle = operator.hip_handle_for(fkw['mask']) if op_name == 'inpainting' else operator.hip_handle(sample)
-            dist_g = handle.score(sample, y)                          # ||y_{p // K} - A(x_p)||_2 per particle
+            dist_g = handle.score(sample, y)                               # ||y_{p // K} - A(x_p)||_2 per particle (HIP)
         distances.append(dist_g)
         finals.append(sample)
-        if args.path_diversity:
-            diversity.append(path_diversity(sample, images=B))
-        if posterior is not None:
-            posterior.add(sample, sampler)
-        if quantiles is not None:
-            quantiles.add(sample)
-        if pca is not None:
-            pca.add(sample)
-        if device_metrics:            # one device call and one copy for the group's B x K particles
-            pm = pathwise_metrics(refs, sample, n_images=B)
-            pm_host = torch.stack([pm["psnr"], pm["ssim"], dist_g.reshape(-1).float()]).cpu().numpy()
-            path_psnr.append(pm_host[0].reshape(B, K))
-            path_ssim.append(pm_host[1].reshape(B, K))
+        for o in outputs:
+            o.add(sample, run.sampler, dist_g)
         for b, fname in enumerate(fnames):
             for i in range(K):
                 p, path_idx = b * K + i, args.path_start_idx + g * K + i
-                if device_metrics:
-                    logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {pm_host[0, p]:.4f} / "
-                                f"SSIM: {pm_host[1, p]:.4f} / distance: {pm_host[2, p]:.4f}")
+                if metrics is not None:
+                    psnr, ssim, d = metrics.host[:, p]
+                    logger.info(f"{tags[b][0]}Path#{path_idx + 1} | Method:{run.sampler_name} / PSNR: {psnr:.4f} / "
+                                f"SSIM: {ssim:.4f} / distance: {d:.4f}")
                 else:
                     psnr = compute_psnr(refs[b:b + 1], sample[p].unsqueeze(0))
-                    logger.info(f"Image {fname} Path#{path_idx + 1} | Method:{sampler_name} / PSNR: {float(psnr):.4f} / "
+                    logger.info(f"{tags[b][0]}Path#{path_idx + 1} | Method:{run.sampler_name} / PSNR: {float(psnr):.4f} / "
                                 f"distance: {float(dist_g[p]):.4f}")
                 imsave(os.path.join(out_path, 'recon_paths', fname, f'path#{path_idx + 1}.png'),
                        clear_color(sample[p].unsqueeze(0)))
                 imsave(os.path.join(out_path, 'recon_paths_y', fname, f'path#{path_idx + 1}_y_space.png'),
                        clear_color(y_space[p].unsqueeze(0)))
-    # best-of-N per image: the [groups, B, K] distances in image-major path order, one segmented argmin, one gather
-    n_paths = groups * K
-    d_img = torch.stack(distances).reshape(groups, B, K).transpose(0, 1).reshape(B * n_paths).contiguous()
-    best = kernels.argmin_seg(d_img, B)                                   # [B]: b * n_paths + path
-    path = best - torch.arange(B, device=best.device) * n_paths
-    src = (path // K) * (B * K) + torch.arange(B, device=best.device) * K + path % K    # index into the groups' concat
-    winners = kernels.gather(torch.cat(finals).detach(), src, validate=False)
-    d_host, path_host = d_img.reshape(B, n_paths).cpu().numpy(), path.cpu().numpy()
-    for b, fname in enumerate(fnames):
-        k = int(path_host[b])
-        logger.info(f"Image {fname}: best-of-{n_paths} = path#{args.path_start_idx + k + 1} | PSNR: "
-                    f"{float(compute_psnr(refs[b:b + 1], winners[b:b + 1])):.4f} | distance: {float(d_host[b, k]):.4f}")
-        imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winners[b:b + 1]))
-        np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), d_host[b])
-        if device_metrics:       # [groups][B, K] -> image b's n_paths values in path order (group-major), as d_host[b]
-            save_path_metrics(out_path, fname, d_host[b], np.concatenate([v[b] for v in path_psnr]),
-                              np.concatenate([v[b] for v in path_ssim]))
-        if args.path_diversity:  # [groups][B, 2] -> image b's [groups, 2]
-            np.save(os.path.join(out_path, f'{fname}_path_diversity.npy'), np.stack([v[b] for v in diversity]))
-    if posterior is not None:
-        posterior.save(out_path, fnames)
-    if quantiles is not None:
-        quantiles.save(out_path, fnames)
-    if pca is not None:
-        pca.save(out_path, fnames)
+    picked = select_winners(run, distances, finals, refs)
+    if run.rank != 0:
+        return
+    for fname, ref, tag, (winner, k, d) in zip(fnames, refs.split(1), tags, picked):
+        logger.info(f"{tag[1]}best-of-{d.size} = path#{args.path_start_idx + k + 1} | PSNR: "
+                    f"{float(compute_psnr(ref, winner)):.4f} | distance: {float(d[k]):.4f}")
+        imsave(os.path.join(out_path, 'best_of_n', fname + '.png'), clear_color(winner))
+        np.save(os.path.join(out_path, f'{fname}_pathwise_distances.npy'), d)
+    for o in outputs:
+        o.save(out_path, fnames)
 
 
 if __name__ == '__main__':
     main()
+

@@ -189,6 +189,83 @@ def test_bench_dump_outputs_dtypes_and_budget(tmp_path):
     assert all(np.array_equal(s1[k], s2[k]) for k in s1)
 
 
+@pytest.mark.parametrize("sampler,world,extra,message", [
+    # command lines that are wrong in two ways: the checks run in one fixed order, so each keeps the message of the first
+    # one it fails (recorded from the driver before its checks were gathered into preflight()); sampler None: no
+    # --diffusion_config
+    ("search_ddpm", 1, ("--beam_width", "3", "--images_per_batch", "0"),
+     "--beam_width 3 does not divide --batch_size 1, the particles per image"),
+    ("ddpm", 1, ("--posterior_pca", "9", "--posterior_quantiles", "x"),
+     "--posterior_quantiles takes percentages separated by commas (got 'x')"),
+    ("ddim", 1, ("--smc_twist_power", "2", "--resample_ess", "2"),
+     "--resample_ess is a fraction of the particle count in [0, 1] (got 2.0)"),
+    ("ddpm", 1, ("--dsg_guidance_rate", "2", "--solver_order", "2"),
+     "--dsg_guidance_rate 2.0 is an option of conditioning method dsg (the task config names ps)"),
+    ("ddpm", 1, ("--solver_order", "2", "--beam_width", "2"),
+     "--solver_order 2 is an option of samplers ddim and ttc_ddim (the diffusion config names ddpm)"),
+    ("ddpm", 1, ("--repulsion_stop", "0.5", "--images_per_batch", "2", "--embedder", "standin:toy_embedder"),
+     "--repulsion_stop 0.5 needs --repulsion_scale > 0"),
+    ("ttc_ddim", 1, ("--images_per_batch", "2", "--posterior_weights", "smc"),
+     "--images_per_batch > 1 is not supported with sampler ttc_ddim: its resampling would mix the particles of different "
+     "images (--resample_draw device draws per image)"),
+    ("ddpm", 1, ("--posterior_summary", "--posterior_weights", "smc", "--posterior_pca", "9"),
+     "--posterior_weights smc reads the weights of sampler smc_ddpm (the diffusion config names ddpm)"),
+    ("smc_ddpm", 1, ("--particle_groups", "2", "--dsg_guidance_rate", "0.5"),
+     "sampler smc_ddpm does not run with --particle_groups > 1: the weights and the resampling are over the whole "
+     "particle set"),
+    ("search_ddpm", 2, ("--posterior_quantiles", "5,50", "--posterior_pca", "2"),
+     "--posterior_quantiles runs on one rank only: the particles of an image are not gathered between ranks "
+     "(WORLD_SIZE=2)"),
+    ("ddpm", 2, ("--path_diversity", "--repulsion_scale", "-1"),
+     "--path_diversity runs on one rank only: the per-group distances are not gathered between ranks (WORLD_SIZE=2)"),
+    (None, 1, ("--resample_ess", "2", "--beam_width", "0"),
+     "--resample_ess is a fraction of the particle count in [0, 1] (got 2.0)"),
+    ("ddpm", 1, ("--beam_width", "0", "--repulsion_scale", "-1"), "--beam_width must be at least 1 (got 0)"),
+    ("ddim", 1, ("--guidance_gain", "span", "--smc_twist_scale", "0.5"),
+     "--smc_twist_scale 0.5 is an option of sampler smc_ddpm (the diffusion config names ddim)"),
+])
+def test_driver_refusal_order(tmp_path, monkeypatch, sampler, world, extra, message):
+    import sys
+    sys.path.insert(0, ROOT)
+    import sample_condition_batched_ttc as drv
+
+    def no_gpu(*a, **kw):
+        raise AssertionError("the driver touched the GPU before rejecting the arguments")
+    for fn in ("is_available", "set_device", "device_count"):
+        monkeypatch.setattr(torch.cuda, fn, no_gpu)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    if world > 1:
+        monkeypatch.setenv("WORLD_SIZE", str(world))
+    argv = ["--task_config", os.path.join(ROOT, "configs", "gaussian_deblur_config.yaml"), *extra]
+    if sampler is not None:
+        diff = yaml.load(open(os.path.join(ROOT, "configs", "diffusion_config.yaml")), Loader=yaml.FullLoader)
+        diff["sampler"] = sampler
+        yaml.dump(diff, open(tmp_path / "diffusion.yaml", "w"))
+        argv = ["--diffusion_config", str(tmp_path / "diffusion.yaml"), *argv]
+    with pytest.raises(SystemExit) as e:
+        drv.main(argv)
+    assert str(e.value) == message
+
+
+def test_driver_reads_each_config_once(tmp_path, monkeypatch):
+    """preflight reads the diffusion and the task config once each, whatever flags ask for the sampler's or the method's name"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import sample_condition_batched_ttc as drv
+    seen, orig = [], drv.load_yaml
+    monkeypatch.setattr(drv, "load_yaml", lambda p: seen.append(p) or orig(p))
+    cfg = os.path.join(ROOT, "configs")
+    dpath, tpath = os.path.join(cfg, "diffusion_config.yaml"), os.path.join(cfg, "gaussian_deblur_config_dsg.yaml")
+    args = drv.parse_args(["--diffusion_config", dpath, "--task_config", tpath, "--dsg_guidance_rate", "0.5",
+                           "--guidance_gain", "unit", "--beam_width", "1", "--posterior_summary", "--path_diversity"])
+    diffusion_config, task_config = drv.preflight(args, 1)
+    assert sorted(seen) == sorted([dpath, tpath])
+    assert diffusion_config["sampler"] == "ddpm" and task_config["conditioning"]["method"] == "dsg"
+    seen.clear()
+    assert drv.preflight(drv.parse_args(["--resample_scheme", "systematic", "--resample_draw", "device"]), 1) == (None, None)
+    assert seen == []
+
+
 def test_particle_groups_partition():
     """kernels.ParticleGroups splits N particles into contiguous groups that differ by at most one particle (host logic
     only: the constructor's partition is computed before anything touches the device)"""
