@@ -77,6 +77,8 @@ SIGNATURES = {
     "dpsx_cg_workspace_bytes": (_i64, [c_void_p, _i64, _i64, _i64, _i64]),
     "dpsx_cg_step_f32": (c_int, [c_void_p, _f, _f, _f, _i64, c_float, c_int, POINTER(Coefs), _f, _f, _f,
                                  _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    "dpsx_cg_pullback_f32": (c_int, [c_void_p, _f, _p, _f, _i64, c_float, c_int, c_float, _f, _f, _f,
+                                     _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_score_f32": (c_int, [c_void_p, _f, _f, _i64, _f, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_score_argmin_f32": (c_int, [c_void_p, _f, _f, _i64, _f, _p, _f, _i64, _i64, _i64, _i64, _p, _i64, _p]),
     "dpsx_search_step_f32": (c_int, [c_void_p, _f, _f, _f, _f, _i64, _f, _f, _p, _f, _f, _i64, _i64, _i64, _i64,

@@ -7,6 +7,7 @@
         'ps_semantic'                       -> (norm_grad, measurement_err, semantic_err)   (:190-195)
         'cg' (not in the reference)         -> (x_{t-1}, dist): needs coefs= from the loop, no autograd graph
         'dsg' (not in the reference)        -> raises: it runs inside the fused step only (kernels.step_update_dsg)
+        'pgdm' (not in the reference)       -> raises: it needs the model's graph (GaussianDiffusion.pgdm_step)
 
 Called on tensors that came out of this package's p_sample (PosteriorStepFn) and
 operator.forward (OperatorFn), `torch.autograd.grad` walks:  UNet  <-  [HIP S1 VJP]
@@ -25,28 +26,38 @@ from .measurements import LinearOperator
 __CONDITIONING_METHOD__ = {}      # the reference's methods, under the reference's names
 __EXTENSION_METHOD__ = {}         # methods the reference does not have ('cg'): same lookup, their own table
 __FUSED_ONLY_METHOD__ = {}        # extensions that exist inside the fused step only ('dsg'): conditioning() raises
+# every later extension ('pgdm' onwards), whatever route it runs on: the class says how it runs, not the table.  The three
+# tables above stay as they are; this one is open and is consulted last.
+__LATER_EXTENSION_METHOD__ = {}
+_TABLES = (__CONDITIONING_METHOD__, __EXTENSION_METHOD__, __FUSED_ONLY_METHOD__, __LATER_EXTENSION_METHOD__)
 
 
-def register_conditioning_method(name: str, extension: bool = False, fused_only: bool = False):
+def register_conditioning_method(name: str, extension: bool = False, fused_only: bool = False, later: bool = False):
     """extension=True: a method that is not in the reference; it is found by get_conditioning_method like the others
     and kept out of the table that mirrors the reference's registry.
     fused_only=True (extensions only): a method with no per-op form -- its conditioning() cannot be called, the sampling
-    loops run it through its fused_spec() -- listed apart from the extensions whose conditioning() a loop calls"""
+    loops run it through its fused_spec() -- listed apart from the extensions whose conditioning() a loop calls
+    later=True (extensions only): the open table of the extensions added after `cg` and `dsg`
+    A name is registered once across all tables."""
     if fused_only and not extension:
         raise ValueError("fused_only is an option of extension methods: every method of the reference has a per-op form")
+    if later and (fused_only or not extension):
+        raise ValueError("later is an option of extension methods, and the open table has no fused_only part")
 
     def wrapper(cls):
-        if any(t.get(name, None) for t in (__CONDITIONING_METHOD__, __EXTENSION_METHOD__, __FUSED_ONLY_METHOD__)):
+        if any(t.get(name, None) for t in _TABLES):
             raise NameError(f"Name {name} is already registered!")
-        table = __FUSED_ONLY_METHOD__ if fused_only else (__EXTENSION_METHOD__ if extension else __CONDITIONING_METHOD__)
+        table = __LATER_EXTENSION_METHOD__ if later else \
+            __FUSED_ONLY_METHOD__ if fused_only else (__EXTENSION_METHOD__ if extension else __CONDITIONING_METHOD__)
         table[name] = cls
         return cls
     return wrapper
 
 
 def get_conditioning_method(name: str, operator, noiser, **kwargs):
-    cls = __CONDITIONING_METHOD__.get(name, None) or __EXTENSION_METHOD__.get(name, None) or \
-        __FUSED_ONLY_METHOD__.get(name, None)
+    cls = None
+    for table in _TABLES:
+        cls = cls or table.get(name, None)
     if cls is None:
         raise NameError(f"Name {name} is not defined!")
     return cls(operator=operator, noiser=noiser, **kwargs)
@@ -333,3 +344,44 @@ class SphericalGaussianGuidance(ConditioningMethod):
     def conditioning(self, x_t, measurement, noisy_measurement=None, **kwargs):
         raise NotImplementedError("dsg needs the step's sd and noise, which only the fused step has: it runs inside the "
                                   "sampling loops (kernels.step_update_dsg), not through conditioning()")
+
+
+@register_conditioning_method(name='pgdm', extension=True, later=True)
+class PseudoInverseGuidance(ConditioningMethod):
+    """Pseudoinverse guidance (not in the reference; PiGDM, Song, Vahdat, Mardani, Kautz 2023) on the CG solve: the
+    measurement's noise-aware, preconditioned residual d = (A^T A + rho_t I)^-1 A^T (y - A x0_hat), rho_t = sigma_y^2 /
+    (1 - abar_t), pulled back through the model, x_{t-1} = sample + weight w_t J^T d (include/dpsx.h:
+    dpsx_cg_pullback_f32).  No per-operator step size; sigma_y is the noiser's (0 for `clean`, no floor).
+    weighting: "score" (w_t = kappa a: consistent with the guided score, first-order accurate in the step count) or "paper"
+    (w_t = sqrt(abar_prev) / a: the paper's weights).  Linear operators, `gaussian` and `clean` noisers."""
+    returns_gradient = False
+
+    def __init__(self, operator, noiser, **kwargs):
+        super().__init__(operator, noiser)
+        if not isinstance(operator, LinearOperator):
+            raise NotImplementedError(
+                f"pgdm solves a linear system in A^T A: {getattr(operator, 'name', type(operator).__name__)} is not a "
+                "linear operator")
+        kind = getattr(noiser, '__name__', None)
+        if kind not in ('gaussian', 'clean'):
+            raise NotImplementedError(f"pgdm is defined for Gaussian measurement noise (noisers `gaussian` and `clean`; got "
+                                      f"{kind!r})")
+        iters = kwargs.get('iters', 5)
+        if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= 64:
+            raise ValueError(f"pgdm: iters must be an integer in [0, 64] (got {iters!r})")
+        self.iters = iters
+        self.weighting = kwargs.get('weighting', 'score')
+        if self.weighting not in ('score', 'paper'):
+            raise ValueError(f"pgdm: weighting must be 'score' or 'paper' (got {self.weighting!r})")
+        weight = kwargs.get('weight', 1.0)
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not math.isfinite(weight):
+            raise ValueError(f"pgdm: weight must be a finite number (got {weight!r})")
+        self.weight = float(weight)
+        self.noise_sigma = float(noiser.sigma) if kind == 'gaussian' else 0.0
+        if not (self.noise_sigma >= 0 and math.isfinite(self.noise_sigma)):
+            raise ValueError(f"pgdm: the noiser's sigma must be finite and not negative (got {noiser.sigma!r})")
+        self.operator_name = operator.name
+
+    def conditioning(self, x_t, measurement, noisy_measurement=None, **kwargs):
+        raise NotImplementedError("pgdm needs the model's graph (the solve's d is pulled back through the UNet): it runs "
+                                  "inside the sampling loops (GaussianDiffusion.pgdm_step), not through conditioning()")

@@ -829,26 +829,35 @@ int64_t dpsx_cg_workspace_bytes(const dpsx_op *op, int64_t n, int64_t c, int64_t
     return cg_carve(op, n, c, h, w, nullptr, nullptr);
 }
 
-int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, const float *y, int64_t y_n, float rho,
-                     int iters, const dpsx_coefs *coefs_host, float *x_next, float *dist, float *d_out, int64_t n,
-                     int64_t c, int64_t h, int64_t w, void *workspace, int64_t workspace_bytes, void *stream)
+// the refusals both CG entries share, in dpsx_cg_step_f32's order; ptrs: the entry's own pointers are all there
+static int cg_check(const dpsx_op *op, bool ptrs, int64_t y_n, float rho, int iters, int64_t n, int64_t c, int64_t h, int64_t w)
 {
-    int rc = check_geom(op, n, c, h, w);
+    const int rc = check_geom(op, n, c, h, w);
     if (rc != DPSX_OK) return rc;
     if (op->kind == OP_PHASE) return DPSX_EUNSUPPORTED;          // no adjoint independent of the point: not a linear solve
-    if (!x0_hat || !sample || !y || !coefs_host || !x_next || !dist) return DPSX_EINVAL;
+    if (!ptrs) return DPSX_EINVAL;
     if (iters < 0 || iters > kCgMaxIters || !(rho >= 0.0f) || !std::isfinite(rho) || !rows_ok(y_n, n)) return DPSX_EINVAL;
-    if (n > 65535) return DPSX_EUNSUPPORTED;                      // particles are the grid's y dimension
-    // the slope of the sampler's `sample` in x0_hat (fp32, in this order): DDPM c1; DDIM c1 - c2 / b
-    float kappa = coefs_host->c1;
-    if (coefs_host->add_noise & 2) {
-        if (coefs_host->b == 0.0f) return DPSX_EINVAL;
-        const float q = coefs_host->c2 / coefs_host->b;
-        kappa = coefs_host->c1 - q;
-    }
-    if (n == 0) return DPSX_OK;
+    return n > 65535 ? DPSX_EUNSUPPORTED : DPSX_OK;               // particles are the grid's y dimension
+}
+
+// How a CG chain ends.  g_mo == NULL: dpsx_cg_step_f32's x_next = sample + kappa d (cg_final); else dpsx_cg_pullback_f32's
+// g_mo[:, :e] = inside ? gain d : +0 (cg_pullback).  Everything before the last launch is one chain.
+struct CgEnd {
+    const float *sample;
+    float *x_next;
+    float kappa;
+    const uint8_t *inside;
+    float *g_mo;
+    float gain;
+};
+
+// the chain of launches of both entries (arguments checked by the caller, n > 0)
+static int cg_chain(dpsx_op *op, const float *x0_hat, const float *y, int64_t y_n, float rho, int iters, const CgEnd &end,
+                    float *dist, float *d_out, int64_t n, int64_t c, int64_t h, int64_t w, void *workspace,
+                    int64_t workspace_bytes, void *stream)
+{
     CgWs k;
-    rc = workspace_check(workspace, workspace_bytes, cg_carve(op, n, c, h, w, workspace, &k));
+    int rc = workspace_check(workspace, workspace_bytes, cg_carve(op, n, c, h, w, workspace, &k));
     if (rc != DPSX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t e = c * h * w, m = meas_elems(op, c, h, w);
@@ -857,7 +866,10 @@ int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, cons
     if ((rc = dpsx_residual_norm_f32(y, y_n, k.t, k.ry, dist, n, m, k.norm_part, n * 256 * 4, stream)) != DPSX_OK) return rc;
     if ((rc = dpsx_op_adjoint_f32(op, k.ry, nullptr, k.r, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
     if (iters == 0) {
-        if (x_next != sample) DPSX_HIP_TRY(hipMemcpyAsync(x_next, sample, (size_t)(n * e) * 4, hipMemcpyDeviceToDevice, s));
+        if (end.g_mo)                                             // d = 0: the eps half of every particle's row, zeroed
+            DPSX_HIP_TRY(hipMemset2DAsync(end.g_mo, (size_t)(2 * e) * 4, 0, (size_t)e * 4, (size_t)n, s));
+        else if (end.x_next != end.sample)
+            DPSX_HIP_TRY(hipMemcpyAsync(end.x_next, end.sample, (size_t)(n * e) * 4, hipMemcpyDeviceToDevice, s));
         if (d_out) DPSX_HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)(n * e) * 4, s));
         return DPSX_OK;
     }
@@ -869,12 +881,47 @@ int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, cons
         if ((rc = dpsx_op_forward_f32(op, k.p, k.t, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
         if ((rc = dpsx_op_adjoint_f32(op, k.t, nullptr, k.s, n, c, h, w, k.op_ws, k.op_bytes, stream)) != DPSX_OK) return rc;
         if ((rc = cg_sumsq(k.t, k.tt, n, m, s)) != DPSX_OK) return rc;
-        if (it == iters - 1)
-            return cg_final(sample, d, k.p, x_next, d_out, rs_old, k.tt, pp, k.scal, rho, kappa, it == 0, n, e, m, s);
+        if (it == iters - 1) {
+            if (end.g_mo)
+                return cg_pullback(d, k.p, end.inside, end.g_mo, d_out, rs_old, k.tt, pp, k.scal, rho, end.gain, it == 0, n,
+                                   e, m, s);
+            return cg_final(end.sample, d, k.p, end.x_next, d_out, rs_old, k.tt, pp, k.scal, rho, end.kappa, it == 0, n, e,
+                            m, s);
+        }
         if ((rc = cg_update(d, k.p, k.r, k.s, rs_old, k.tt, pp, rs_new, k.scal, rho, it == 0, n, e, m, s)) != DPSX_OK) return rc;
         if ((rc = cg_pupdate(k.r, k.p, rs_old, rs_new, k.pp, k.scal, n, e, s)) != DPSX_OK) return rc;
     }
     return DPSX_OK;
+}
+
+int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, const float *y, int64_t y_n, float rho,
+                     int iters, const dpsx_coefs *coefs_host, float *x_next, float *dist, float *d_out, int64_t n,
+                     int64_t c, int64_t h, int64_t w, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const int rc = cg_check(op, x0_hat && sample && y && coefs_host && x_next && dist, y_n, rho, iters, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    // the slope of the sampler's `sample` in x0_hat (fp32, in this order): DDPM c1; DDIM c1 - c2 / b
+    float kappa = coefs_host->c1;
+    if (coefs_host->add_noise & 2) {
+        if (coefs_host->b == 0.0f) return DPSX_EINVAL;
+        const float q = coefs_host->c2 / coefs_host->b;
+        kappa = coefs_host->c1 - q;
+    }
+    if (n == 0) return DPSX_OK;
+    return cg_chain(op, x0_hat, y, y_n, rho, iters, CgEnd{sample, x_next, kappa, nullptr, nullptr, 0.0f}, dist, d_out, n, c, h,
+                    w, workspace, workspace_bytes, stream);
+}
+
+int dpsx_cg_pullback_f32(dpsx_op *op, const float *x0_hat, const uint8_t *inside, const float *y, int64_t y_n, float rho,
+                         int iters, float gain, float *g_model_out, float *dist, float *d_out, int64_t n, int64_t c,
+                         int64_t h, int64_t w, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const int rc = cg_check(op, x0_hat && inside && y && g_model_out && dist, y_n, rho, iters, n, c, h, w);
+    if (rc != DPSX_OK) return rc;
+    if (!std::isfinite(gain)) return DPSX_EINVAL;
+    if (n == 0) return DPSX_OK;
+    return cg_chain(op, x0_hat, y, y_n, rho, iters, CgEnd{nullptr, nullptr, 0.0f, inside, g_model_out, gain}, dist, d_out, n,
+                    c, h, w, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------ best-of-N

@@ -6,6 +6,7 @@
 //   k_cg_update   alpha (prologue); d += alpha p; r -= alpha (s + rho p); ||r||^2 partials
 //   k_cg_pupdate  beta (prologue);  p = r + beta p;       ||p||^2 partials (the next iteration's rho ||p||^2)
 //   k_cg_final    alpha (prologue); x_next = sample + kappa (d + alpha p)       (the last iteration: no r, p update)
+//   k_cg_pullback alpha (prologue); g_eps = inside ? gain (d + alpha p) : +0    (dpsx_cg_pullback_f32's last launch)
 //
 // Every launch is particle_pass.h's per-particle slotted pass: one fp32 partial per block (the fixed tree of block_sum) in
 // its slot; the consumer launch's prologue adds a particle's slots in double with common.h's slots_sum (lane-strided,
@@ -184,6 +185,30 @@ __global__ __launch_bounds__(kPassThreads) void k_cg_pupdate(const float *__rest
     }
 }
 
+// ------------------------------------------------------------------ the last iteration (k_cg_final, k_cg_pullback)
+// the prologue both finishers share: alpha into sc (cg_alpha_to_lds), the barrier, and the particle's scalars left by its
+// first block; -> alpha
+__device__ __forceinline__ float cg_last_alpha(const float *rs, const float *tt, const float *pp, float *scal, float *sc,
+                                               float rho, int slots, int slots_m, int64_t q)
+{
+    cg_alpha_to_lds(rs + q * slots, tt + q * slots_m, pp + q * slots, slots, slots_m, rho, sc);
+    __syncthreads();
+    const float alpha = sc[0];
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        scal[q * 4 + 0] = sc[1];
+        scal[q * 4 + 1] = sc[2];
+        scal[q * 4 + 2] = alpha;
+    }
+    return alpha;
+}
+
+// d of the last iteration: d + alpha p, two roundings (first: d is zero and was not read)
+template <class T> __device__ __forceinline__ T cg_last_d(T dv, T pv, float alpha, int first)
+{
+    const T ap = alpha * pv;
+    return first ? ap : dv + ap;
+}
+
 // ------------------------------------------------------------------ x_next = sample + kappa (d + alpha p)
 // x_next may be sample, d_out (nullable) may be d: each lane reads its unit before it writes it, so no __restrict__ there
 template <bool VEC>
@@ -206,13 +231,10 @@ __global__ __launch_bounds__(kPassThreads) void k_cg_final(const float *sample, 
         pv = ld_last<T>(p + o);
         sv = ld_last<T>(sample + o);
     }
-    cg_alpha_to_lds(rs + q * slots, tt + q * slots_m, pp + q * slots, slots, slots_m, rho, sc);
-    __syncthreads();
-    const float alpha = sc[0];
+    const float alpha = cg_last_alpha(rs, tt, pp, scal, sc, rho, slots, slots_m, q);
     while (u < g.hi) {
         const int64_t o = base + u * W;
-        const T ap = alpha * pv;
-        const T dn = first ? ap : dv + ap;
+        const T dn = cg_last_d(dv, pv, alpha, first);
         if (d_out) st<T>(d_out + o, dn);
         st<T>(x_next + o, sv + kappa * dn);
         u += kPassThreads;
@@ -223,10 +245,56 @@ __global__ __launch_bounds__(kPassThreads) void k_cg_final(const float *sample, 
             sv = ld_last<T>(sample + o2);
         }
     }
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        scal[q * 4 + 0] = sc[1];
-        scal[q * 4 + 1] = sc[2];
-        scal[q * 4 + 2] = alpha;
+}
+
+// ------------------------------------------------------------------ g_eps = inside ? gain (d + alpha p) : +0
+// The cotangent on the model's eps output in k_cg_final's place: the eps half of g_model_out [n, 2 chw] (the variance half is
+// not touched).  The gate is read 4 bytes per unit (VEC) or one byte per element; d and p are read for the last time.
+// d_out (nullable) may be d: each lane reads its unit before it writes it
+template <bool VEC> struct Gate { typedef uint8_t T; };
+template <> struct Gate<true> { typedef uchar4 T; };
+__device__ __forceinline__ float cg_gated(uint8_t in, float gain, float dn) { return in ? gain * dn : 0.0f; }
+__device__ __forceinline__ f4 cg_gated(uchar4 in, float gain, f4 dn)
+{
+    return f4{cg_gated(in.x, gain, dn.x), cg_gated(in.y, gain, dn.y), cg_gated(in.z, gain, dn.z), cg_gated(in.w, gain, dn.w)};
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kPassThreads) void k_cg_pullback(const float *d, const float *__restrict__ p,
+                                                            const uint8_t *__restrict__ inside, float *__restrict__ g_mo,
+                                                            float *d_out, const float *__restrict__ rs,
+                                                            const float *__restrict__ tt, const float *__restrict__ pp,
+                                                            float *__restrict__ scal, float rho, float gain, int first,
+                                                            int slots, int slots_m, int64_t e, int64_t per)
+{
+    using T = typename Unit<VEC>::T;
+    using G = typename Gate<VEC>::T;
+    constexpr int W = Unit<VEC>::W;
+    __shared__ float sc[3];
+    const int64_t q = blockIdx.y, base = q * e, mbase = q * 2 * e;
+    const Range g = block_range(e / W, per);
+    int64_t u = g.lo + threadIdx.x;
+    T dv = T{}, pv = T{};
+    G in = G{};
+    if (u < g.hi) {
+        const int64_t o = base + u * W;
+        if (!first) dv = ld_last<T>(d + o);
+        pv = ld_last<T>(p + o);
+        in = *reinterpret_cast<const G *>(inside + o);
+    }
+    const float alpha = cg_last_alpha(rs, tt, pp, scal, sc, rho, slots, slots_m, q);
+    while (u < g.hi) {
+        const int64_t i = u * W;
+        const T dn = cg_last_d(dv, pv, alpha, first);
+        if (d_out) st<T>(d_out + base + i, dn);
+        st<T>(g_mo + mbase + i, cg_gated(in, gain, dn));
+        u += kPassThreads;
+        if (u < g.hi) {
+            const int64_t o2 = base + u * W;
+            if (!first) dv = ld_last<T>(d + o2);
+            pv = ld_last<T>(p + o2);
+            in = *reinterpret_cast<const G *>(inside + o2);
+        }
     }
 }
 
@@ -286,6 +354,19 @@ int cg_final(const float *sample, const float *d, const float *p, float *x_next,
     return dispatch(vec, [&](auto V) {
         k_cg_final<V.value><<<g.grid, kPassThreads, 0, s>>>(sample, d, p, x_next, d_out, rs, tt, pp, scal, rho, kappa, first,
                                                             cg_slots(e), cg_slots(m), e, g.per);
+        return check_launch();
+    });
+}
+
+int cg_pullback(const float *d, const float *p, const uint8_t *inside, float *g_mo, float *d_out, const float *rs,
+                const float *tt, const float *pp, float *scal, float rho, float gain, bool first, int64_t n, int64_t e,
+                int64_t m, hipStream_t s)
+{
+    const bool vec = vec_ok(e, {d, p, g_mo, d_out}) && aligned4(inside);
+    const PassGeom g = pass_geom(e, vec, n);
+    return dispatch(vec, [&](auto V) {
+        k_cg_pullback<V.value><<<g.grid, kPassThreads, 0, s>>>(d, p, inside, g_mo, d_out, rs, tt, pp, scal, rho, gain, first,
+                                                               cg_slots(e), cg_slots(m), e, g.per);
         return check_launch();
     });
 }

@@ -748,6 +748,11 @@ int cg_pupdate(const float *r, float *p, const float *rs_old, const float *rs_ne
 int cg_final(const float *sample, const float *d, const float *p, float *x_next, float *d_out, const float *rs,
              const float *tt, const float *pp, float *scal, float rho, float kappa, bool first, int64_t n, int64_t e,
              int64_t m, hipStream_t s);
+// dpsx_cg_pullback_f32's finisher, in cg_final's place: alpha as above; g_mo[:, :e] = inside ? gain (d + alpha p) : +0 (the
+// eps half of [n, 2 e]; the other half is not touched); d_out (nullable) = d + alpha p, cg_final's bits.  d_out may be d
+int cg_pullback(const float *d, const float *p, const uint8_t *inside, float *g_mo, float *d_out, const float *rs,
+                const float *tt, const float *pp, float *scal, float rho, float gain, bool first, int64_t n, int64_t e,
+                int64_t m, hipStream_t s);
 
 // smc.hip: the particle weights' two launches (the recurrence is stated in include/dpsx.h)
 // K3 + the proposal correction's partials [n, cg_slots(chw)]; the noise is z, or with use_rng the counters of r

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import kernels
-from .condition_methods import ConditioningMethod, ConjugateGradientConsistency, SphericalGaussianGuidance
+from .condition_methods import (ConditioningMethod, ConjugateGradientConsistency, PseudoInverseGuidance,
+                                SphericalGaussianGuidance)
 from .diffstategrad_utils import apply_diffstategrad, compute_svd_and_adaptive_rank
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
@@ -155,7 +156,7 @@ class _Trajectory(NamedTuple):
     n: int                              # its particles
     method: object                      # the conditioning function's ConditioningMethod, or None
     plan: Optional[tuple]               # _fusion_plan's (method, kw, handle)
-    cg: Optional[tuple]                 # _cg_plan's (method, kw)
+    cg: Optional[tuple]                 # _cg_plan's (method, kw): the `cg` method's, or `pgdm`'s on the same route
     images: Optional[int]               # the images of the batch (the base loop: None for one)
     y: Optional[torch.Tensor]           # the measurement, contiguous fp32; None on the per-op route
 
@@ -280,6 +281,9 @@ class GaussianDiffusion:
             why = "the cg step has no fused plan (it replaces x0_hat by x0_hat + d and has its own update)"
         elif isinstance(method, SphericalGaussianGuidance):
             why = "dsg puts x_next on a sphere: it has no step size to scale and no update to add a history term to"
+        elif isinstance(method, PseudoInverseGuidance):
+            why = ("pgdm has no fused plan and its own weight (w_t follows from the step's record: there is no scale to "
+                   "multiply and no x0_hat history)")
         else:
             why = {"sampler": "no fused plan: it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised "
                               "posterior (a fixed-variance model has no fused step)",
@@ -357,6 +361,8 @@ class GaussianDiffusion:
         why = None
         if not base_loop:
             why = f"sampler {type(self).__name__} has its own loop"
+        elif cg is not None and isinstance(cg[0], PseudoInverseGuidance):
+            why = "the pgdm step has no fused plan (its x0_hat lives in no step buffer)"
         elif cg is not None:
             why = "the cg step has no fused plan (x0_hat + d is its own quantity)"
         elif plan is None:
@@ -729,10 +735,79 @@ class GaussianDiffusion:
         self._step_semantic = sems if sems else None
         return pg.x_next(), pg.full.norm
 
+    # -- pseudoinverse guidance ('pgdm'): the cg route with the model's graph ------
+    def _check_pgdm(self, measurement_cond_fn, project=False):
+        """The `pgdm` method runs on the `cg` route of the ddpm / ddim / ttc_ddim loops, one chain: anything else is refused
+        here, from the host's knowledge alone, before the first step (and before the model or the device is asked for
+        anything)."""
+        method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if not isinstance(method, PseudoInverseGuidance):
+            return
+        why = None
+        if isinstance(self, SMC_DDPM):
+            why = ("smc_ddpm's weights assume the Gaussian-shift proposal of the fused ps step, whose correction the pgdm "
+                   "step does not compute")
+        elif not (self.hip_posterior and isinstance(self, (DDPM, DDIM))):
+            why = ("it needs a DDPM / DDIM sampler with the epsilon / learned_range / clip_denoised posterior (the HIP S1 and "
+                   "its clamp gate; a fixed-variance model has none)")
+        elif self.particle_groups > 1:
+            why = f"particle_groups = {self.particle_groups}: groups exist under a fused plan only, pgdm runs one chain"
+        elif project:
+            why = ("a DiffStateGrad projection (project=True) projects the step's gradient as a tensor of its own, which the "
+                   "pgdm step does not form (K3 applies its two terms directly)")
+        elif method.operator.name == 'inpainting' and kw.get('mask', None) is None:
+            why = "inpainting needs its mask bound to the conditioning function"
+        if why is not None:
+            raise NotImplementedError(f"pgdm is not supported here: {why}")
+
+    def _pgdm_record(self, idx):
+        """the step's record in float64, from the sampler's tables -> (a, b, c1, c2, ddim, abar, abar_prev)"""
+        return (self.sqrt_recip_alphas_cumprod[idx], self.sqrt_recipm1_alphas_cumprod[idx], self.posterior_mean_coef1[idx],
+                self.posterior_mean_coef2[idx], False, self.alphas_cumprod[idx], self.alphas_cumprod_prev[idx])
+
+    def pgdm_scalars(self, idx, method):
+        """(rho_t, gain_t) of the pgdm step at loop index idx: float64 from the tables, one fp32 rounding each
+        (kernels.pgdm_scalars)"""
+        key = (idx, float(getattr(self, "eta", 0.0)), method.noise_sigma, method.weighting, method.weight)
+        cache = self.__dict__.setdefault('_pgdm_scalars', {})
+        if key not in cache:
+            *rec, abar, abar_prev = self._pgdm_record(idx)
+            cache[key] = kernels.pgdm_scalars(abar, abar_prev, rec, method.noise_sigma, method.weighting, method.weight)
+        return cache[key]
+
+    def pgdm_step(self, model, x_prev, idx, measurement, method, cond_kw, noise=None, rng=None):
+        """One `pgdm` step at loop index idx: the model forward with a graph, S1 with its clamp gate, the CG solve ended in
+        the cotangent on the model's eps output (OpHandle.cg_pullback), the model VJP, K3.  Returns (x_next, dist[N]) in the
+        operator handle's persistent buffers (valid until the next step; the loops clone what they hand out)."""
+        x_prev = x_prev.detach().requires_grad_()
+        with torch.enable_grad():
+            model_out = self._call_model(model, x_prev, idx)
+        mo = kernels.f32c(model_out.detach(), "model output")
+        if mo.shape[1] != 2 * x_prev.shape[1]:
+            raise ValueError("the pgdm step needs a learned-sigma model ([N, 2C, H, W] output)")
+        coefs = self.sample_coefs(idx)
+        if noise is None and rng is None:
+            noise = self._randn(x_prev)
+        x0_hat, sample, inside = kernels.posterior_fwd(kernels.f32c(x_prev.detach(), "x_t"), mo, noise, coefs,
+                                                       want_inside=True, rng=rng)
+        handle = self._op_handle(method.operator, cond_kw.get('mask', None), x0_hat)
+        rho, gain = self.pgdm_scalars(idx, method)
+        g_mo, dist = handle.cg_pullback(x0_hat, inside, kernels.f32c(measurement, "measurement"), rho, method.iters, gain)
+        g_unet = None
+        if model_out.requires_grad:
+            (g_unet,) = torch.autograd.grad(model_out, x_prev, grad_outputs=g_mo.to(model_out.dtype))
+            g_unet = kernels.f32c(g_unet, "UNet VJP")
+        buf = handle.cg_buffers(*x0_hat.shape, x0_hat.device)
+        buf.sample = sample
+        return kernels.step_update(buf, g_unet, coefs), dist
+
     # -- the Jacobian-free step ('cg') -----------------------------------------
     def _cg_plan(self, measurement_cond_fn):
-        """-> (method, bound keyword arguments) when measurement_cond_fn is the `cg` method's conditioning, else None"""
+        """-> (method, bound keyword arguments) when measurement_cond_fn is the `cg` method's conditioning or `pgdm`'s
+        (which runs on the same route: _check_pgdm has passed), else None"""
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        if isinstance(method, PseudoInverseGuidance):
+            return method, kw
         if not isinstance(method, ConjugateGradientConsistency):
             return None
         if self._no_plan_reason(method, kw) == "sampler":
@@ -765,7 +840,8 @@ class GaussianDiffusion:
         if self.rng_parity:
             self._randn(y, self.parity_measurement_stride)      # the reference's q_sample draw (:224, :668), result unused
         if cg is not None:
-            return self.cg_step(model, img, idx, y, cg[0], cg[1], noise=noise, rng=rng)
+            step = self.pgdm_step if isinstance(cg[0], PseudoInverseGuidance) else self.cg_step
+            return step(model, img, idx, y, cg[0], cg[1], noise=noise, rng=rng)
         if pg is not None:
             return self.dps_step_grouped(model, img, idx, y, plan[0], plan[1], pg, noise, rng=rng, **step_kw)
         return self.dps_step(model, img, idx, y, plan[0], plan[1], plan[2], noise=noise, rng=rng, **step_kw)
@@ -796,6 +872,7 @@ class GaussianDiffusion:
         img = x_start.detach()
         n = img.shape[0]
         self._check_dsg(measurement_cond_fn, img)
+        self._check_pgdm(measurement_cond_fn, project)
         self._check_solver(measurement_cond_fn, img, project)
         self._check_repulsion(n, measurement, n_images)
         kernels.require_cuda(img, "x_start")
@@ -1007,6 +1084,12 @@ class DDIM(SpacedDiffusion):
                                                  self.sqrt_recipm1_alphas_cumprod[idx], self.alphas_cumprod[idx],
                                                  self.alphas_cumprod_prev[idx], eta, idx != 0)
         return cache[key]
+
+    def _pgdm_record(self, idx):
+        abar, abar_prev, eta = self.alphas_cumprod[idx], self.alphas_cumprod_prev[idx], np.float64(self.eta)
+        sigma = eta * np.sqrt((1.0 - abar_prev) / (1.0 - abar)) * np.sqrt(1.0 - abar / abar_prev)
+        return (self.sqrt_recip_alphas_cumprod[idx], self.sqrt_recipm1_alphas_cumprod[idx], np.sqrt(abar_prev),
+                np.sqrt(max(1.0 - abar_prev - sigma ** 2, 0.0)), True, abar, abar_prev)
 
     def p_sample(self, model, x, t, eta=None, noise=None):
         """reference :479-509.  The noise is drawn whether or not it is used, as there (:493)."""
@@ -1386,6 +1469,7 @@ class SMC_DDPM(DDPM):
         self._check_repulsion()
         scale, power, weight, every, scheme, ess = self._smc_options()
         method, kw = self._unwrap_cond_fn(measurement_cond_fn)
+        self._check_pgdm(measurement_cond_fn)
         if self._no_plan_reason(method, kw) in ("sampler", "method"):
             name = type(method).__name__ if method is not None else "this conditioning function"
             raise NotImplementedError(f"smc_ddpm needs the fused ps / ps_anneal / ps_semantic step under the epsilon / "

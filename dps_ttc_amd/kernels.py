@@ -414,9 +414,7 @@ class OpHandle:
         if sample.shape != x0_hat.shape:
             raise ValueError(f"sample {tuple(sample.shape)} and x0_hat {tuple(x0_hat.shape)} differ in shape")
         n, c, h, w = x0_hat.shape
-        buf = self._cg
-        if buf is None or buf.shape != (n, c, h, w) or buf.dist.device != x0_hat.device:
-            buf = self._cg = CgBuffers(self, n, c, h, w, x0_hat.device)
+        buf = self.cg_buffers(n, c, h, w, x0_hat.device)
         out = buf.x_next[buf.flip]
         buf.flip ^= 1
         d = buf.d_buffer() if want_d else None
@@ -424,6 +422,33 @@ class OpHandle:
                                      byref(coefs), ptr(out), ptr(buf.dist), ptr(d), n, c, h, w, ptr(buf.ws),
                                      buf.ws.numel(), stream_of(x0_hat)), "dpsx_cg_step_f32")
         return (out, buf.dist, d) if want_d else (out, buf.dist)
+
+    def cg_buffers(self, n, c, h, w, device):
+        """this handle's CgBuffers for (N, C, H, W) on `device` (one set: another shape replaces it)"""
+        buf = self._cg
+        if buf is None or buf.shape != (n, c, h, w) or buf.dist.device != torch.device(device):
+            buf = self._cg = CgBuffers(self, n, c, h, w, device)
+        return buf
+
+    def cg_pullback(self, x0_hat, inside, y, rho, iters, gain, want_d=False):
+        """Pseudoinverse guidance's cotangent (include/dpsx.h: dpsx_cg_pullback_f32): cg_step's solve for d, ended in
+        g_model_out[:, :C] = inside ? gain d : +0 in place of x_next = sample + kappa d.  inside: S1's clamp gate
+        (posterior_fwd(..., want_inside=True)); rho, gain: the step's host scalars (pgdm_scalars).
+        -> (g_model_out [N, 2C, H, W] with a zero variance half, dist [N] = ||y - A x0_hat||_2 [, d]) in this handle's
+        persistent CgBuffers (overwritten by the next call): callers clone what they keep."""
+        x0_hat, y = _nchw(f32c(x0_hat, "x0_hat")), f32c(y, "measurement")
+        require_cuda(inside, "clamp gate")
+        if inside.dtype != torch.uint8 or inside.numel() != x0_hat.numel() or not inside.is_contiguous():
+            raise ValueError(f"the clamp gate must be a contiguous uint8 tensor of x0_hat's size (got {inside.dtype}, "
+                             f"{tuple(inside.shape)})")
+        n, c, h, w = x0_hat.shape
+        buf = self.cg_buffers(n, c, h, w, x0_hat.device)
+        g = buf.g_model_out_buffer()
+        d = buf.d_buffer() if want_d else None
+        check(lib().dpsx_cg_pullback_f32(self._h, ptr(x0_hat), ptr(inside), ptr(y), y.shape[0], float(rho), int(iters),
+                                         float(gain), ptr(g), ptr(buf.dist), ptr(d), n, c, h, w, ptr(buf.ws),
+                                         buf.ws.numel(), stream_of(x0_hat)), "dpsx_cg_pullback_f32")
+        return (g, buf.dist, d) if want_d else (g, buf.dist)
 
     def resample_cost(self, x, y, prev_costs=None, potential_type='min'):
         """SearchDDPM.resample_update's cost update (gaussian_diffusion.py:556-585) in one launch:
@@ -796,9 +821,10 @@ class StepBuffers:
 
 
 class CgBuffers:
-    """Persistent device buffers of OpHandle.cg_step for one (N, C, H, W): the two x_next buffers it alternates between,
-    dist, the solve's workspace (dpsx_cg_workspace_bytes) and, on first request, d.  One allocation per (handle, shape),
-    reused across steps and trajectories."""
+    """Persistent device buffers of OpHandle.cg_step / cg_pullback for one (N, C, H, W): the two x_next buffers they
+    alternate between, dist, the solve's workspace (dpsx_cg_workspace_bytes) and, on first request, d and g_model_out
+    ([N, 2C, H, W], zeroed once: the pullback writes the eps half only).  `sample` is the pgdm step's S1 sample, which
+    step_update reads beside g_model_out.  One allocation per (handle, shape), reused across steps and trajectories."""
 
     def __init__(self, handle, n, c, h, w, device):
         self.shape = (n, c, h, w)
@@ -811,11 +837,19 @@ class CgBuffers:
         self.dist = torch.empty(n, **f)
         self.flip = 0
         self._d = None
+        self.g_model_out = None
+        self.sample = None
 
     def d_buffer(self):
         if self._d is None:
             self._d = torch.empty(self.shape, dtype=torch.float32, device=self.dist.device)
         return self._d
+
+    def g_model_out_buffer(self):
+        if self.g_model_out is None:
+            n, c, h, w = self.shape
+            self.g_model_out = torch.zeros((n, 2 * c, h, w), dtype=torch.float32, device=self.dist.device)
+        return self.g_model_out
 
 
 def cg_kappa(coefs):
@@ -823,6 +857,24 @@ def cg_kappa(coefs):
     DDPM record, c1 - c2 / b for a DDIM record (eps is re-derived from x0_hat; the variance does not depend on it)"""
     c1, c2, b = np.float32(coefs.c1), np.float32(coefs.c2), np.float32(coefs.b)
     return float(c1 - c2 / b) if coefs.add_noise & 2 else float(c1)
+
+
+def pgdm_scalars(abar, abar_prev, coefs_f64, sigma_y, weighting="score", weight=1.0):
+    """Pseudoinverse guidance's host scalars of one step (include/dpsx.h: dpsx_cg_pullback_f32), formed in float64 and
+    rounded to fp32 once each -> (rho, gain).  abar, abar_prev: the sampler's abar_t and the abar the step lands on;
+    coefs_f64: the step's record in float64, (a, b, c1, c2, ddim) with ddim = the record re-derives eps (bit 1 of add_noise).
+        rho  = sigma_y^2 / (1 - abar)
+        gain = weight w b ,  w = kappa a ("score": kappa = c1, or c1 - c2 / b for a DDIM record) | sqrt(abar_prev) / a ("paper")"""
+    a, b, c1, c2, ddim = coefs_f64
+    a, b, c1, c2 = np.float64(a), np.float64(b), np.float64(c1), np.float64(c2)
+    if weighting == "score":
+        w = (c1 - c2 / b if ddim else c1) * a
+    elif weighting == "paper":
+        w = np.sqrt(np.float64(abar_prev)) / a
+    else:
+        raise ValueError(f"pgdm: weighting must be 'score' or 'paper' (got {weighting!r})")
+    rho = np.float64(sigma_y) ** 2 / (1.0 - np.float64(abar))
+    return float(np.float32(rho)), float(np.float32(np.float64(weight) * w * b))
 
 
 def _stream_arg(stream, t):

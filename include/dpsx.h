@@ -256,6 +256,41 @@ int dpsx_cg_step_f32(dpsx_op *op, const float *x0_hat, const float *sample, cons
                      int64_t n, int64_t c, int64_t h, int64_t w,
                      void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- pseudoinverse guidance (PiGDM; Song, Vahdat, Mardani, Kautz 2023) on the CG solve: the measurement's noise-aware,
+ * preconditioned residual pulled back through the model.  By the push-through identity, with rho_t = sigma_y^2 / r_t^2 and
+ * r_t^2 = 1 - abar_t (the paper's unit-variance prior),
+ *     r_t^2 A^T (r_t^2 A A^T + sigma_y^2 I)^-1 (y - A x0_hat)  =  (A^T A + rho_t I)^-1 A^T (y - A x0_hat)  =  d,
+ * the vector dpsx_cg_step_f32 iterates on.  Per step, with the step's dpsx_coefs record and the sampler's float64 tables:
+ *     d       = iters CG iterations from d = 0                      (dpsx_cg_step_f32's recurrence and launches, unchanged)
+ *     rho_t   = sigma_y^2 / (1 - abar_t)                            (sigma_y = 0 for a clean measurement; no floor)
+ *     x_next  = sample + weight w_t J^T d ,   J = d x0_hat / d x_t = gate (a I - b d eps / d x_t)
+ *     w_t     = kappa a                  weighting "score" (kappa: dpsx_cg_step_f32's slope, c1 or c1 - c2 / b)
+ *     w_t     = sqrt(abar_prev) / a      weighting "paper" (the paper's update with eps kept: "score" times abar_t on the
+ *                                        x0_hat term only)
+ * "score" is the step that is consistent with eps' = eps - sqrt(1 - abar_t) grad log p(y | x_t): x0_hat is shifted by
+ * a J^T d and eps is re-derived from it, hence kappa; its error against the exact posterior of a Gaussian prior shrinks at
+ * first order in the step count, while "paper" has a per-step weight that does not shrink with the step.
+ * The caller forms rho = rho_t and gain = weight w_t b in float64 and rounds each to fp32 once.  This entry runs the chain
+ * of dpsx_cg_step_f32 with one other last launch: per element, with D = d + alpha p of the last iteration (two fp32
+ * roundings: the bits dpsx_cg_step_f32 leaves in d_out),
+ *     g_model_out[p, e] = inside[p, e] ? gain * D : +0.0f           e < c h w: the eps half of [n, 2c, h, w]
+ * one fp32 multiply.  The variance half of g_model_out is not touched (the caller zeroes it once, as for
+ * dpsx_step_bwd_f32).  dpsx_step_update_f32 on it and on the model's VJP of it then gives
+ *     sample - ((-a / b) g_eps + g_unet)  =  sample + weight w_t J^T d.
+ * inside: dpsx_posterior_fwd_f32's clamp gate, uint8 [n, c, h, w].  dist, d_out, workspace (dpsx_cg_workspace_bytes), y_n:
+ * as for dpsx_cg_step_f32, same bits.  iters = 0 zeroes the eps half (and d_out) and still reports dist.  No atomics; one
+ * linear chain of launches on `stream`: no allocation, no host read, no branch on data (graph-capturable).
+ * The last launch takes the 16-byte form where c h w is a multiple of 4, g_model_out and d_out are 16-byte aligned and
+ * inside is 4-byte aligned, else the scalar form: same bits.
+ * DPSX_EUNSUPPORTED: phase retrieval, n > 65535.  DPSX_EINVAL: iters < 0 or > 64, rho negative or not finite, gain not
+ * finite, y_n not dividing n, a null pointer.  All of them return before anything is launched or written. */
+int dpsx_cg_pullback_f32(dpsx_op *op, const float *x0_hat, const uint8_t *inside, const float *y, int64_t y_n,
+                         float rho, int iters, float gain,
+                         float *g_model_out /* [n,2c,h,w] */, float *dist /* [n] */,
+                         float *d_out /* [n,c,h,w], may be NULL */,
+                         int64_t n, int64_t c, int64_t h, int64_t w,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- best-of-N scoring / select (gaussian_diffusion.py:626-633, 687-698;
  *      best_of_n_simple.py:32-40) */
 /* costs[p] = ||y - A(x_p)||_2 without materialising the residual */

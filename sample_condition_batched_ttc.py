@@ -23,6 +23,7 @@ global: RCCL all-gather of the distances, winner broadcast from its owner.  `sam
 all ranks' particles at every step and `sampler: ttc_ddim` resamples over all of them (SURVEY.md 8e ii-iii).
 """
 import argparse
+import math
 import os
 from functools import partial
 from typing import NamedTuple
@@ -135,6 +136,13 @@ def parse_args(argv=None):
     p.add_argument('--dsg_guidance_rate', type=float, default=None,
                    help='dsg: overrides the task config\'s guidance_rate in [0, 1] (0: the drawn noise direction, 1: the '
                         'steepest-descent direction)')
+    p.add_argument('--pgdm_iters', type=int, default=None,
+                   help='pgdm: overrides the task config\'s iters, the CG iterations of the solve per step, in [0, 64]')
+    p.add_argument('--pgdm_weighting', type=str, default=None, choices=('score', 'paper'),
+                   help='pgdm: overrides the task config\'s weighting (score: consistent with the guided score; paper: '
+                        'the weights of the PiGDM paper)')
+    p.add_argument('--pgdm_weight', type=float, default=None,
+                   help='pgdm: overrides the task config\'s weight, a multiplier on the guidance term (1: the method\'s own)')
     p.add_argument('--solver_order', type=int, default=None, choices=(1, 2),
                    help='ddim / ttc_ddim: overrides the diffusion config\'s solver_order (1: the DDIM rule, 2: the '
                         'DPM-Solver++(2M) multistep update; eta 0 or 1, ps-type methods, one rank for ttc_ddim)')
@@ -316,6 +324,31 @@ def check_dsg(args, method_name):
         raise SystemExit(f"--dsg_guidance_rate must be in [0, 1] (got {g})")
 
 
+def pgdm_flags(args):
+    return [(f"--pgdm_{k}", getattr(args, f"pgdm_{k}")) for k in ("iters", "weighting", "weight")
+            if getattr(args, f"pgdm_{k}") is not None]
+
+
+def check_pgdm(args, method_name, sampler_name=None):
+    """--pgdm_*: options of conditioning method pgdm; reject them for another method, values outside their range, and what
+    the pgdm step does not run under, before any GPU work (one-line message)"""
+    for flag, value in pgdm_flags(args):
+        if method_name != 'pgdm':
+            raise SystemExit(f"{flag} {value} is an option of conditioning method pgdm (the task config names {method_name})")
+    if method_name != 'pgdm':
+        return
+    if args.pgdm_iters is not None and not 0 <= args.pgdm_iters <= 64:
+        raise SystemExit(f"--pgdm_iters must be in [0, 64] (got {args.pgdm_iters})")
+    if args.pgdm_weight is not None and not math.isfinite(args.pgdm_weight):
+        raise SystemExit(f"--pgdm_weight must be finite (got {args.pgdm_weight})")
+    if sampler_name == 'smc_ddpm':
+        raise SystemExit("conditioning method pgdm does not run under sampler smc_ddpm (its weights assume the fused ps "
+                         "step's proposal)")
+    if args.particle_groups > 1:
+        raise SystemExit("conditioning method pgdm does not run with --particle_groups > 1 (groups exist under a fused plan "
+                         "only, pgdm runs one chain)")
+
+
 def check_solver(args, sampler_name, method_name, world=1, eta=None):
     """--solver_order / --guidance_gain: reject what the sampling loops would refuse, before any GPU work (one-line
     message).  eta: the diffusion config's (None: the sampler's default 0)"""
@@ -326,7 +359,7 @@ def check_solver(args, sampler_name, method_name, world=1, eta=None):
         raise SystemExit(f"--solver_order {order} is an option of samplers ddim and ttc_ddim (the diffusion config names "
                          f"{sampler_name})")
     if order == 2:
-        if method_name in ('cg', 'dsg'):
+        if method_name in ('cg', 'dsg', 'pgdm'):
             raise SystemExit(f"--solver_order 2 is not supported with conditioning method {method_name} (it has its own "
                              "update)")
         if float(eta or 0.0) not in (0.0, 1.0):
@@ -334,7 +367,7 @@ def check_solver(args, sampler_name, method_name, world=1, eta=None):
         if sampler_name == 'ttc_ddim' and world > 1:
             raise SystemExit("--solver_order 2 with ttc_ddim on several ranks is not supported (the history does not "
                              "travel between ranks)")
-    if gain == 'span' and method_name in ('cg', 'dsg'):
+    if gain == 'span' and method_name in ('cg', 'dsg', 'pgdm'):
         raise SystemExit(f"--guidance_gain span is not supported with conditioning method {method_name} (it has no scale "
                          "per step)")
 
@@ -564,6 +597,7 @@ def preflight(args, world):
     check_resample_scheme(args, sampler_name)
     check_smc(args, sampler_name, world)
     check_dsg(args, method_name)
+    check_pgdm(args, method_name, sampler_name)
     check_solver(args, sampler_name, method_name, world, diffusion_config.get('eta') if args.diffusion_config else None)
     check_beam_width(args, sampler_name, world)
     check_repulsion(args, sampler_name, world)
@@ -616,6 +650,8 @@ def main(argv=None):
     cond_params = dict(cond_config['params'])
     if args.dsg_guidance_rate is not None:       # check_dsg: the method is dsg
         cond_params['guidance_rate'] = args.dsg_guidance_rate
+    for flag, value in pgdm_flags(args):         # check_pgdm: the method is pgdm
+        cond_params[flag[len("--pgdm_"):]] = value
     embedder = None
     if args.embedder is not None:
         import importlib
@@ -665,6 +701,9 @@ def main(argv=None):
         dir_name = (f"{op_name}_noise_sigma_{sigma}_cg_rho_scale_{cond_method.rho_scale}_iters_{cond_method.iters}")
     elif cond_config['method'] == 'dsg':
         dir_name = f"{op_name}_noise_sigma_{sigma}_dsg_guidance_rate_{cond_method.guidance_rate}"
+    elif cond_config['method'] == 'pgdm':
+        dir_name = (f"{op_name}_noise_sigma_{sigma}_pgdm_{cond_method.weighting}_iters_{cond_method.iters}_weight_"
+                    f"{cond_method.weight}")
     else:
         dir_name = f"{op_name}_noise_sigma_{sigma}_dps_scale_{cond_config['params']['scale']}"
     out_path = os.path.join(args.save_dir, dir_name)

@@ -4,7 +4,7 @@
 
     python tools/e2e_unet.py [--particles 16] [--steps 5] [--operator gaussian_blur]
 The last line is the same loop with the `cg` method (model forward under no_grad, S1, the CG solve): the whole-step time
-of `ps` (forward + VJP) against `cg` (forward only).
+of `ps` (forward + VJP) against `cg` (forward only), and then with `pgdm` (forward + VJP + the CG solve).
 """
 import argparse
 import os
@@ -80,6 +80,18 @@ def main():
     dc = (time.perf_counter() - t0) / args.steps
     print(f"N={n} {args.operator}: full cg step (iters=5) {dc * 1e3:.1f} ms ({n / dc:.1f} particle-steps/s) = "
           f"{dc / dt:.2f} x the ps step; dist[0]={float(dist[0]):.3f}")
+    pg = get_conditioning_method("pgdm", op, get_noise("gaussian", sigma=0.05), iters=5)
+    for i in range(2):
+        x, _ = smp.pgdm_step(model, x, 999 - i, y, pg, fkw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        x, dist = smp.pgdm_step(model, x, 997 - i, y, pg, fkw)
+    torch.cuda.synchronize()
+    dp = (time.perf_counter() - t0) / args.steps
+    print(f"N={n} {args.operator}: full pgdm step (iters=5) {dp * 1e3:.1f} ms ({n / dp:.1f} particle-steps/s) = "
+          f"{dp / dt:.2f} x the ps step (ps + cg = {(dt + dc) * 1e3:.1f} ms, which holds one model forward more); "
+          f"dist[0]={float(dist[0]):.3f}")
 
 
 if __name__ == "__main__":

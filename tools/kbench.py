@@ -21,6 +21,7 @@ one process: (a) torch.randn + the pointer launch (noise_draw = "torch"), (b) ke
 launch, (c) the draw inside the launch (step_fwd(rng=) / search_step_one(rng=)); a route without an in-kernel form is
 marked and its (c) is the front end's fallback, which is (b).
     python tools/kbench.py --cg                                                       (the CG data-consistency step, 256^2)
+    python tools/kbench.py --pgdm                                                     (cg_pullback beside cg_step, 256^2)
 --cg: OpHandle.cg_step at iters = 1 and 5 beside the fused `ps` step (K1 + K2 + K3) and the plain A / A^T / K3 launches,
 N = 64 and 16, Gaussian / motion / SR x4 / inpainting, 3 x --reps repetitions alternated in one process.  Per launch: the
 step's time over its enqueued launches (5 + 5 iters - 1).  The vector side of one middle iteration (||t||^2, the d / r
@@ -96,6 +97,7 @@ def main():
     ap.add_argument("--resample", action="store_true", help="time the resampling step (multinomial / draw + gathers / fused)")
     ap.add_argument("--noise-draw", action="store_true", help="time the step noise: torch.randn / device fill / in-kernel draw")
     ap.add_argument("--cg", action="store_true", help="time the CG data-consistency step beside the fused ps step")
+    ap.add_argument("--pgdm", action="store_true", help="time OpHandle.cg_pullback beside cg_step (iters = 5) and K3")
     ap.add_argument("--smc", action="store_true", help="time K3 beside step_update_corr (pointer / rng / torch ops) and smc_accum")
     ap.add_argument("--dsg", action="store_true", help="time step_update_dsg's two launches (pointer / rng) beside K3")
     ap.add_argument("--dpmpp", action="store_true", help="time step_update_ms (c != 0 / c = 0 / torch ops) beside K3, and K1's x0_hat store")
@@ -125,6 +127,8 @@ def main():
         return dsg_step(args)
     if args.smc:
         return smc_step(args)
+    if args.pgdm:
+        return pgdm_step(args)
     if args.cg:
         return cg_step(args)
     if args.noise_draw:
@@ -331,6 +335,63 @@ def cg_step(args):
                   f"   vector side of one iteration {vec_us:7.1f} us = {vec_bytes / max(vec_us, 1e-3) / 1e3:7.1f} GB/s "
                   f"({9 + m_over_e:.2f} P/particle) = {vec_bytes / max(vec_us, 1e-3) / (k3_bytes / t['K3']):4.2f} x K3's rate",
                   flush=True)
+
+
+def pgdm_step(args):
+    """OpHandle.cg_pullback beside OpHandle.cg_step at iters = 5 (the chains differ in the last launch only: k_cg_pullback
+    in k_cg_final's place) and K3, 3 x --reps alternated.  The last launch alone is the difference of the iters = 1 chains
+    from their common part, so it is read from a kernel trace (rocprofv3 --kernel-trace --stats) of this same run instead:
+    bytes per particle 3.25 P with d_out off (d, p, the gate; g_eps), K3's from bench.algo_p."""
+    from dps_ttc_amd import kernels
+    from dps_ttc_amd.gaussian_diffusion import create_sampler
+    dev = torch.device("cuda", 0)
+    smp = create_sampler(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                         model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True,
+                         rescale_timesteps=True, timestep_respacing="")
+    ck = smp.step_coefs[500]
+    P = bench.P_BYTES
+    rho, gain = kernels.pgdm_scalars(smp.alphas_cumprod[500], smp.alphas_cumprod_prev[500], smp._pgdm_record(500)[:5], 0.05)
+
+    def timed(fn):
+        for i in range(3):
+            fn(i)
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.reps)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            fn(i)
+            b.record()
+        torch.cuda.synchronize()
+        return np.array([a.elapsed_time(b) for a, b in evs]) * 1e3
+
+    for n in (64, 16):
+        for name in ("gaussian_blur", "motion_blur", "super_resolution", "inpainting"):
+            op, fkw = bench.build_operator(name, dev, sigma=args.sigma)
+            x_t, ring, truth, meas_noise = bench.synth_inputs(n, 2, dev, 1234)
+            yy = op.forward(truth.to(dev), **fkw).detach()
+            y = (yy + meas_noise.to(dev)[..., :yy.shape[-2], :yy.shape[-1]]).contiguous()
+            handle = op.hip_handle_for(fkw["mask"]) if name == "inpainting" else op.hip_handle(x_t)
+            buf = kernels.StepBuffers(handle, n, 3, 256, 256, dev)
+            x0_hat, sample, inside = kernels.posterior_fwd(x_t, ring[0]["model_out"], ring[0]["noise"], ck, want_inside=True)
+            buf.sample.copy_(sample)
+            forms = {"cg5": lambda i: handle.cg_step(x0_hat, sample, y, rho, 5, ck),
+                     "pgdm5": lambda i: handle.cg_pullback(x0_hat, inside, y, rho, 5, gain),
+                     "K3": lambda i: kernels.step_update(buf, ring[i % 2]["g_unet"], ck)}
+            res = {}
+            for rep in range(3):                       # alternated: every form sees the same box state
+                for key, fn in forms.items():
+                    res.setdefault(key, []).append(timed(fn))
+            t = {key: float(np.concatenate(v).mean()) for key, v in res.items()}
+            lo = {key: float(np.concatenate(v).min()) for key, v in res.items()}
+            runs = {key: " / ".join(f"{r.mean():.1f}" for r in v) for key, v in res.items()}
+            spread = max(max(r.mean() for r in res[k]) - min(r.mean() for r in res[k]) for k in ("cg5", "pgdm5"))
+            k3_bytes = bench.algo_p(name, x0_store=False)["algorithmic"]["upd"] * P * n
+            tag = f"pgdm {name:16s} N={n:2d}"
+            for key, label in (("cg5", "cg_step     iters=5"), ("pgdm5", "cg_pullback iters=5")):
+                print(f"{tag} {label} avg {t[key]:8.1f} us  min {lo[key]:8.1f}  (runs {runs[key]})", flush=True)
+            print(f"{tag} cg_pullback - cg_step {t['pgdm5'] - t['cg5']:+7.1f} us (the rounds' spread {spread:.1f} us)   "
+                  f"K3 {t['K3']:7.1f} us = {k3_bytes / t['K3'] / 1e3:7.1f} GB/s   inside: {100 * float(inside.float().mean()):.1f} % "
+                  f"of the elements", flush=True)
 
 
 def smc_step(args):
