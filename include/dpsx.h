@@ -111,6 +111,12 @@ int dpsx_posterior_bwd_f32(const float *g_x0, const float *g_sample, const float
 /* ---- measurement operators A (measurements.py) ---------------------------- */
 typedef struct dpsx_op dpsx_op; /* opaque; owns only its constant tables */
 
+/* DPSX_BLUR_AUTO: a kernel K that is rank 1 takes the separable path.  With col = K[:, pj] and
+ * row = K[pi, :] / K[pi, pj] through the tap of largest magnitude (pi, pj), both rounded to fp32,
+ * K counts as rank 1 when   sum |col[i] row[j] - K[i][j]| <= 1e-6 * sum |K[i][j]|   (evaluated in
+ * double): the separable operator then differs from the given one by at most 1e-6 max|x| per
+ * output pixel, relative to an operator of gain sum |K|.  Every other kernel, and every kernel
+ * under DPSX_BLUR_FORCE_TAPS, runs as the list of its non-zero taps. */
 enum { DPSX_BLUR_AUTO = 0, DPSX_BLUR_FORCE_TAPS = 1 };
 
 /* GaussialBlurOperator / MotionBlurOperator: ReflectionPad2d(ks/2) + depthwise
